@@ -14,11 +14,18 @@ All of it is inside the timed region.  Inputs are resident in HBM before it star
 
     python bench.py [--gpus N --steps K --warmup W]          # N>1 under torch.distributed.run
 
+A plain run sets up, warms up, times the K steps and prints the result line (metric, value,
+ms_per_step, the last reporting interval's aggregates).  `--dump-outputs DIR` also writes what the
+timed path handed back in its last step (dump_outputs below).  Everything else the benchmark
+measures — the roofline of the pod sweep, the PMC traffic passes, the CPU baselines, the
+PCIe-inclusive rate, device patch emission, the C2-mix HBM working set — runs only with `--full`
+(the options that narrow those legs, --no-pmc, --pcie-steps 0, ..., apply within it).
+
 Multi-GPU (one process per GPU): rank r owns the contiguous node block [r*n/N, (r+1)*n/N) and
 every pod on those nodes (no data-path collective).  Default "scaling": "strong" — the C5
 cluster (--nodes total) is split over the ranks; --scaling weak keeps --nodes per rank.
 
-The JSON line carries `roofline` for the pod sweep kernel (algorithmic bytes per launch /
+With --full the JSON line carries `roofline` for the pod sweep kernel (algorithmic bytes per launch /
 its HIP-event duration on the engine's stream; `traffic` = HBM bytes per launch from two
 rocprofv3 PMC passes of this same workload run as child processes at N=1, FETCH_SIZE x 2 —
 the gfx950 correction of MI355X_MICROARCH.md — + WRITE_SIZE, or null when they cannot run),
@@ -551,6 +558,57 @@ def cpu_baseline_c4(sample_s: float, seed: int):
                       f"(ResourceUsage lookup, usage-from-annotation, Quantity parse), 1 thread; CPU {_cpu_model()}"}
 
 
+DUMP_BUDGET = 60 * 10**6  # bytes of array data over all files of one --dump-outputs directory
+
+
+def dump_outputs(outdir, pods, nodes, agg, handback, seed):
+    """--dump-outputs: what a caller of the timed path holds after its last step, one .npy per array:
+    each engine's fired hand-back of that step, read from the device list the step compacted it into
+    (no further launch), and the last reporting interval's aggregates.
+
+      pod_fired.npy        the pod list in the --handback format: 2-byte records (float32), the bitmap
+                           hand-back's 32-bit words, 4-byte packed records or kwk_fired_rec as
+                           [slot, stage | flags << 16] rows (float64)
+      pod_fired_segments   records per 2048-slot segment (--handback packed16 only; float32)
+      node_fired.npy       the node list: 4-byte packed records (kwk_fired_rec rows with rec; float64)
+      aggregates.npy       Aggregates.pack() of the last interval: transitions per stage, counts per mask (the
+                           pod engine's, then the node engine's), cluster cpu and memory usage (float64);
+                           absent when no reporting interval ended inside the timed steps
+      lengths.npy          the full length of pod_fired, pod_fired_segments, node_fired (float64)
+
+    The values are exact in those types.  The files hold at most DUMP_BUDGET bytes of data: an array
+    over its share of it is cut to a fixed sample, the sorted indices drawn from default_rng(seed)."""
+    if handback == "packed16":
+        rec, cnt, _ = pods.fired_packed16()
+        arrays = {"pod_fired": rec.astype(np.float32), "pod_fired_segments": cnt.astype(np.float32)}
+    elif handback == "bits":
+        arrays = {"pod_fired": pods.fired_bits()[0].astype(np.float64)}
+    elif handback == "packed":
+        arrays = {"pod_fired": pods.fired_packed().astype(np.float64)}
+    else:
+        arrays = {"pod_fired": np.ascontiguousarray(pods.fired()).view(np.uint32).reshape(-1, 2).astype(np.float64)}
+    if handback == "rec":
+        arrays["node_fired"] = np.ascontiguousarray(nodes.fired()).view(np.uint32).reshape(-1, 2).astype(np.float64)
+    else:
+        arrays["node_fired"] = nodes.fired_packed().astype(np.float64)
+    arrays["lengths"] = np.asarray([len(arrays["pod_fired"]), len(arrays.get("pod_fired_segments", ())),
+                                    len(arrays["node_fired"])], dtype=np.float64)
+    if agg is not None:
+        arrays["aggregates"] = agg.result().pack()
+    os.makedirs(outdir, exist_ok=True)
+    left = DUMP_BUDGET
+    order = sorted(arrays, key=lambda k: arrays[k].nbytes)
+    for i, name in enumerate(order):
+        a = arrays[name]
+        share = left // (len(order) - i)
+        if a.nbytes > share:
+            keep = share // (a.nbytes // len(a))
+            a = a[np.sort(np.random.default_rng(seed).choice(len(a), keep, replace=False))]
+            log(f"--dump-outputs: {name} cut to a sample of {keep} of {len(arrays[name])} rows")
+        left -= a.nbytes
+        np.save(os.path.join(outdir, name + ".npy"), a)
+
+
 def _cpu_model():
     try:
         for line in open("/proc/cpuinfo"):
@@ -561,11 +619,55 @@ def _cpu_model():
     return "unknown"
 
 
+def pod_roofline(args, sweep_ms, s1p, pod_n_stages, report_every, first_bytes, first_lines, pbytes, fused_first,
+                 pod_kernel, traffic, pmc_err):
+    """--full: the `roofline` entry of the C5 line, from the sampled pod sweep launches (HIP events), the bytes
+    of one such launch counted alone after the timed region and the PMC child passes' traffic."""
+    pod_kernel_s = statistics.mean(sweep_ms) / 1e3
+    # the engine fuses the 1-byte pod sweep when its program allows (pod-fast: <= 4 stages, no delayed
+    # stage) — decided from the engine, not from the last launch's steps (a 1-step tail launch)
+    fuse_max = (args.fuse_steps if (args.fuse_steps >= 2 and int(s1p["state_bytes"]) == 1 and pod_n_stages <= 4)
+                else 1)
+    launches = sweep_launches(args.steps, report_every, fuse_max)
+    spl = args.steps / launches  # steps per pod sweep launch (mean)
+    achieved = first_bytes / pod_kernel_s / 1e9  # the sampled launches' bytes / their duration
+    sb = int(s1p["state_bytes"])
+    tr = None if traffic is None else traffic["read"] + traffic["write"]
+    roof = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": tr,
+            "traffic_note": (f"rocprofv3 PMC child passes of this workload ({traffic['launches']} pod-sweep launches): "
+                             f"FETCH_SIZE x 2 = {traffic['read']} B read + WRITE_SIZE = {traffic['write']} B written "
+                             "per launch" if traffic else f"null: {pmc_err}"),
+            "kernel": SWEEP_NAMES.get(pod_kernel["kernel"], "?") + (" persistent" if pod_kernel["persistent"] else "")
+                      + " (pods)",
+            "bytes_per_launch": int(first_bytes), "state_bytes_per_object": sb,
+            "steps_per_launch": fused_first, "launches": launches,
+            "mean_bytes_per_launch": int(pbytes / launches), "mean_steps_per_launch": round(spl, 3),
+            "launch_note": "avg_launch_us = the sampled launches (the first of each reporting interval: "
+                           f"{fused_first} step(s)); bytes_per_launch = the bytes of one such launch, counted "
+                           "alone after the timed region (mean_bytes_per_launch: the timed region's bytes over "
+                           "all its launches of every size)",
+            "avg_launch_us": round(pod_kernel_s * 1e6, 2),
+            # the same count with state writes as the whole 128-byte lines the sweep stores
+            "line_bytes_per_launch": int(first_lines),
+            "line_frac": round(first_lines / pod_kernel_s / 1e9 / HBM_PEAK_GBS, 4)}
+    if tr:
+        roof["traffic_GBps"] = round(tr / pod_kernel_s / 1e9, 1)
+    return roof
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline figure: the pod sweep's roofline (+ PMC child passes), "
+                         "the CPU baselines, the PCIe-inclusive rate, device patch emission, the C2-mix HBM working set "
+                         "(--config C1..C4: the CPU baseline and C4's Metric CR leg)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path handed back in its last step as DIR/<name>.npy "
+                         "(C5 line only; see dump_outputs)")
     ap.add_argument("--nodes", type=int, default=1_000_000, help="nodes in total (strong) or per GPU (weak)")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="strong")
     ap.add_argument("--config", choices=("C1", "C2", "C3", "C4", "C5"), default="C5",
@@ -619,17 +721,20 @@ def main():
                     help="aggregate all-reduce: torch.distributed (default) or libkwok_comm (RCCL, no torch; N > 1)")
     args = ap.parse_args()
 
+    if args.dump_outputs and (args.config != "C5" or args.metrics_pods or args.hbm_only or args.pmc_child):
+        ap.error("--dump-outputs writes the C5 line's hand-back: not with --config C1..C4 or the diagnostic legs")
+
     if args.config != "C5":
         from kwok_amd import build as kbuild
         from kwok_amd import configs
         if not os.path.exists(kbuild.OUT):
             kbuild.build()
         r = configs.run(args.config, args.steps, args.warmup, args.seed)
-        if args.config == "C4":  # the Metric CR on the same cluster size
+        if args.config == "C4" and args.full:  # the Metric CR on the same cluster size
             r["metric_cr"] = configs.run_metrics(10_000, 1_000_000, scrapes=10, warmup=3, seed=args.seed)
         roof = r.pop("roofline", None)
         cpu = None
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             cpu = {"C1": lambda: cpu_baseline(args.cpu_sample_s / 2, args.seed),
                    "C2": lambda: cpu_baseline_c2(args.cpu_sample_s / 2, args.seed),
                    "C3": lambda: cpu_baseline_c3(args.cpu_sample_s / 2, args.seed),
@@ -671,7 +776,7 @@ def main():
 
     # PMC child passes first, while this process has not touched the GPU (N=1 only)
     traffic, pmc_err = None, "not collected (N>1, --no-pmc or --no-harness)"
-    if world == 1 and not args.pmc_child and not args.no_pmc and not args.no_harness:
+    if args.full and world == 1 and not args.pmc_child and not args.no_pmc and not args.no_harness:
         log("PMC passes (FETCH_SIZE, WRITE_SIZE) as child processes")
         traffic, pmc_err = pmc_traffic(args)
 
@@ -748,13 +853,15 @@ def main():
     s1p, s1n = pods.stats(), nodes.stats()
     pod_kernel = pods.last_sweep()
     pod_n_stages = len(pods.p.stages)
+    if args.dump_outputs and rank == 0:  # before anything else steps the engines: the timed path's last step
+        dump_outputs(args.dump_outputs, pods, nodes, agg, args.handback, args.seed)
     n_ev = (args.steps + EV_EVERY - 1) // EV_EVERY
-    if world > 1:  # sampled after the timed region (the same steps continued)
+    if world > 1 and args.full:  # sampled after the timed region (the same steps continued)
         k0 = args.warmup + args.steps
         run_steps(pods, nodes, args.seed, dt, k0, k0 + args.steps, ev_base=0, handback=args.handback)
         pods.sync()
         nodes.sync()
-    sweep_ms = [pods.event_elapsed_ms(2 * i, 2 * i + 1) for i in range(n_ev)]
+    sweep_ms = [pods.event_elapsed_ms(2 * i, 2 * i + 1) for i in range(n_ev)] if world == 1 or args.full else []
 
     fired = (s1p["fired"] - s0p["fired"]) + (s1n["fired"] - s0n["fired"])
     pbytes, plines = sweep_bytes(s0p, s1p)
@@ -783,16 +890,18 @@ def main():
         fused_first = args.fuse_steps if args.fuse_steps >= 2 and len(pods.p.stages) <= 4 else 1
         while fused_first > max(1, report_every or args.steps):
             fused_first >>= 1
-    k0 = args.warmup + args.steps
-    sa = pods.stats()
-    pods.step_n_pair(nodes, fused_first, NOW0 + k0 * dt, dt, args.seed, k0, HANDBACK[args.handback])
-    pods.sync()
-    nodes.sync()
-    first_bytes, first_lines = sweep_bytes(sa, pods.stats())
+    first_bytes = first_lines = None
+    if args.full:
+        k0 = args.warmup + args.steps
+        sa = pods.stats()
+        pods.step_n_pair(nodes, fused_first, NOW0 + k0 * dt, dt, args.seed, k0, HANDBACK[args.handback])
+        pods.sync()
+        nodes.sync()
+        first_bytes, first_lines = sweep_bytes(sa, pods.stats())
 
     # PCIe-inclusive rate: the same steps with every fired record copied to pinned host memory
     pcie = None
-    if args.pcie_steps > 0 and world == 1:
+    if args.full and args.pcie_steps > 0 and world == 1:
         from kwok_amd.host.engine import PinnedBuffer
         pod_list = {"bits": 2, "packed16": 2, "packed": 4, "rec": 8}[args.pcie_handback] * pods.capacity + 64
         node_list = (8 if args.pcie_handback == "rec" else 4) * nodes.capacity + 64
@@ -835,7 +944,7 @@ def main():
     else:
         k_after = args.warmup + args.steps
     patch_emit = None
-    if args.emit_steps > 0 and world == 1:
+    if args.full and args.emit_steps > 0 and world == 1:
         log("device patch emission run")
         patch_emit = measure_patch_emit(pods, pvars, pidx, args, dt, k_after)
     del pidx
@@ -845,7 +954,7 @@ def main():
     nodes.close()
 
     hbm = None
-    if rank == 0 and world == 1 and args.hbm_nodes > 0 and not args.no_harness:
+    if args.full and rank == 0 and world == 1 and args.hbm_nodes > 0 and not args.no_harness:
         log("HBM working-set run: C2 stage mix at 100M pods")
         hbm = measure_hbm_working_set(args, local_rank)
         if not args.no_cpu_baseline:
@@ -853,40 +962,15 @@ def main():
 
     if rank == 0:
         value = total_fired / max_s
-        pod_kernel_s = statistics.mean(sweep_ms) / 1e3
-        # the engine fuses the 1-byte pod sweep when its program allows (pod-fast: <= 4 stages, no delayed
-        # stage) — decided from the engine, not from the last launch's steps (a 1-step tail launch)
-        fuse_max = (args.fuse_steps if (args.fuse_steps >= 2 and int(s1p["state_bytes"]) == 1 and pod_n_stages <= 4)
-                    else 1)
-        launches = sweep_launches(args.steps, report_every, fuse_max)
-        spl = args.steps / launches  # steps per pod sweep launch (mean)
-        achieved = first_bytes / pod_kernel_s / 1e9  # the sampled launches' bytes / their duration
+        roof = None
+        if args.full:
+            roof = pod_roofline(args, sweep_ms, s1p, pod_n_stages, report_every, first_bytes, first_lines, pbytes,
+                                fused_first, pod_kernel, traffic, pmc_err)
         sb = int(s1p["state_bytes"])
-        tr = None if traffic is None else traffic["read"] + traffic["write"]
-        roof = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": tr,
-                "traffic_note": (f"rocprofv3 PMC child passes of this workload ({traffic['launches']} pod-sweep launches): "
-                                 f"FETCH_SIZE x 2 = {traffic['read']} B read + WRITE_SIZE = {traffic['write']} B written "
-                                 "per launch" if traffic else f"null: {pmc_err}"),
-                "kernel": SWEEP_NAMES.get(pod_kernel["kernel"], "?") + (" persistent" if pod_kernel["persistent"] else "")
-                          + " (pods)",
-                "bytes_per_launch": int(first_bytes), "state_bytes_per_object": sb,
-                "steps_per_launch": fused_first, "launches": launches,
-                "mean_bytes_per_launch": int(pbytes / launches), "mean_steps_per_launch": round(spl, 3),
-                "launch_note": "avg_launch_us = the sampled launches (the first of each reporting interval: "
-                               f"{fused_first} step(s)); bytes_per_launch = the bytes of one such launch, counted "
-                               "alone after the timed region (mean_bytes_per_launch: the timed region's bytes over "
-                               "all its launches of every size)",
-                "avg_launch_us": round(pod_kernel_s * 1e6, 2),
-                # the same count with state writes as the whole 128-byte lines the sweep stores
-                "line_bytes_per_launch": int(first_lines),
-                "line_frac": round(first_lines / pod_kernel_s / 1e9 / HBM_PEAK_GBS, 4)}
-        if tr:
-            roof["traffic_GBps"] = round(tr / pod_kernel_s / 1e9, 1)
         cpu = None
         log(f"timed {args.steps} steps in {max_s:.3f} s")
         cpu_soa = None
-        if not args.no_cpu_baseline and world == 1:  # the CPU leg runs on rank 0 at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # the CPU leg runs on rank 0 at N=1 only
             cpu = cpu_baseline(args.cpu_sample_s, args.seed)
             cpu_soa = cpu_baseline_soa(args.cpu_sample_s / 2, args.seed)
         total_nodes = args.nodes * world if weak else args.nodes
@@ -912,11 +996,11 @@ def main():
             "hbm_working_set": hbm,
             "aggregates": agg_dict,
             "detail": {"transitions_per_step": total_fired / args.steps, "per_stage_rank0": per_stage,
-                       "pod_sweep_us_mean": round(statistics.mean(sweep_ms) * 1e3, 2),
-                       "pod_sweep_us_median": round(statistics.median(sweep_ms) * 1e3, 2),
+                       "pod_sweep_us_mean": round(statistics.mean(sweep_ms) * 1e3, 2) if sweep_ms else None,
+                       "pod_sweep_us_median": round(statistics.median(sweep_ms) * 1e3, 2) if sweep_ms else None,
                        "pod_sweep_launches_timed": len(sweep_ms),
                        "pod_sweep_events": "inside the timed region" if world == 1 else
-                                           "after the timed region (the same steps continued)",
+                                           "after the timed region (the same steps continued)" if sweep_ms else None,
                        "setup_s": round(setup_s, 1)},
         }
         print(json.dumps(line), flush=True)

@@ -5,7 +5,7 @@
 # Usage: bash tools/gpu.sh <tag> <step> [<step> ...]      outputs under gpurun_out/<tag>/
 #   tests[=<pytest -k expr>]   GPU test suite (or a selection; '+' between names: any of them)
 #   smoke                      __graft_entry__.smoke()
-#   bench[=<bench.py args>]    the driver's bench command (default --gpus 1 --steps 20 --warmup 5)
+#   bench[=<bench.py args>]    the bench command with every leg (default --gpus 1 --steps 20 --warmup 5 --full)
 #   prof                       kernel trace + stats of the driver's bench command (kernel_stats.csv)
 #   timeline[=<bench args>]    kernel trace of the C5 bench (timed steps only): one reporting interval's dispatches and
 #                              gaps (from pod sweep launch TL_N, 2, for TL_SPAN, 3, launches: fused groups 4 + 4 + 2)
@@ -25,7 +25,7 @@ set -o pipefail
 R=${GRAFT_REPO_ROOT:-$(pwd)}; T=$1; shift; O=$R/gpurun_out/$T
 mkdir -p $O && cd $R
 TRACE() { cd /tmp && export TMPDIR=/tmp; }
-B1="--gpus 1 --steps 20 --warmup 5"
+B1="--gpus 1 --steps 20 --warmup 5 --full"
 for step in "$@"; do
   name=${step%%=*}; arg=""; [ "$name" != "$step" ] && arg=${step#*=}
   echo "== $name $arg"
@@ -69,13 +69,13 @@ h=d.get('hbm_working_set') or {};print('hbm',h.get('kernel'),h.get('avg_launch_u
       cat $O/agg_sq.txt ;;
     configs)
       for c in C1 C2 C3 C4; do
-        timeout -k 10 300 python -u bench.py --config $c --steps 20 --warmup 5 >> $O/configs_C1_C4.jsonl 2> $O/config_$c.err || { tail -30 $O/config_$c.err; exit 1; }
+        timeout -k 10 300 python -u bench.py --config $c --steps 20 --warmup 5 --full >> $O/configs_C1_C4.jsonl 2> $O/config_$c.err || { tail -30 $O/config_$c.err; exit 1; }
         tail -1 $O/configs_C1_C4.jsonl | cut -c1-300
       done ;;
     metrics)
       # the Metric CR at C4 size (bench --config C4's metric_cr) and at 100M pods (--metrics-pods), plus a
       # kernel trace of the 100M leg
-      timeout -k 10 400 python -u bench.py --config C4 --steps 20 --warmup 5 > $O/c4_metrics.json 2> $O/c4_metrics.err \
+      timeout -k 10 400 python -u bench.py --config C4 --steps 20 --warmup 5 --full > $O/c4_metrics.json 2> $O/c4_metrics.err \
         || { tail -30 $O/c4_metrics.err; exit 1; }
       python -c "import json,sys; d=json.load(open('$O/c4_metrics.json'))['detail']['metric_cr']; print(json.dumps(d)[:900])"
       timeout -k 10 600 python -u bench.py --metrics-pods ${arg:-100000000} > $O/metrics_100m.json 2> $O/metrics_100m.err \
@@ -114,7 +114,7 @@ h=d.get('hbm_working_set') or {};print('hbm',h.get('kernel'),h.get('avg_launch_u
       cat $O/c5_sq.txt $O/c2_sq.txt ;;
     emitprof)  # the patch emitter alone: kernel trace (size / scan / write split) + SQ and TA passes over emit_write
       TRACE
-      E="$R/bench.py --gpus 1 --steps 2 --warmup 2 --no-pmc --no-cpu-baseline --hbm-nodes 0 --pcie-steps 0 --emit-steps 3"
+      E="$R/bench.py --gpus 1 --steps 2 --warmup 2 --full --no-pmc --no-cpu-baseline --hbm-nodes 0 --pcie-steps 0 --emit-steps 3"
       timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/emit_trace -o run -- python3 $E > $O/emit_trace.json 2> $O/emit_trace.err \
         || { tail -20 $O/emit_trace.err; exit 1; }
       S1="SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU"
@@ -129,7 +129,7 @@ h=d.get('hbm_working_set') or {};print('hbm',h.get('kernel'),h.get('avg_launch_u
       for d in emsq1 emsq2 emsq3; do [ -d $O/$d ] && python tools/rocpd_summary.py pmc $(find $O/$d -name '*.db' | head -1) emit_write; done \
         > $O/emit_sq.txt; cat $O/emit_sq.txt ;;
     shards)
-      S="--no-cpu-baseline --no-pmc --hbm-nodes 0 --pcie-steps 0 --steps 40 --warmup 5"
+      S="--full --no-cpu-baseline --no-pmc --hbm-nodes 0 --pcie-steps 0 --steps 40 --warmup 5"
       for n in 125000 250000 500000; do
         timeout -k 10 200 python -u bench.py --nodes $n $S > $O/shard_$n.json 2> $O/shard_$n.err || { tail -20 $O/shard_$n.err; exit 1; }
         python -c "import json; d=json.load(open('$O/shard_$n.json')); print($n, d['value'], d['ms_per_step'], d['roofline']['avg_launch_us'])"
@@ -140,7 +140,7 @@ h=d.get('hbm_working_set') or {};print('hbm',h.get('kernel'),h.get('avg_launch_u
       cd $R && python tools/rocpd_summary.py stats $(find $O/shard_prof -name '*.db' | head -1) $O/shard_kernel_stats.csv \
         && cut -c1-150 $O/shard_kernel_stats.csv | head -14 ;;
     shardtune)  # the 125k-node shard under pod-sweep grid / hand-back tunings: "<label>:<bench args>;..."
-      S="--nodes 125000 --no-cpu-baseline --no-pmc --hbm-nodes 0 --pcie-steps 0 --steps 40 --warmup 5"
+      S="--nodes 125000 --full --no-cpu-baseline --no-pmc --hbm-nodes 0 --pcie-steps 0 --steps 40 --warmup 5"
       IFS=';' read -ra V <<< "${arg:-base:}"
       for i in 1 2; do
         for v in "${V[@]}"; do
@@ -208,7 +208,7 @@ h=d.get('hbm_working_set') or {};print('hbm',h.get('kernel'),h.get('avg_launch_u
       for i in 1 2; do
         for v in cur ${arg//,/ }; do
           if [ $v = cur ]; then cp $O/cur_emit.so $L; else cp tools/ab/$v $L; fi
-          timeout -k 10 200 python -u bench.py --gpus 1 --steps 5 --warmup 3 --no-pmc --no-cpu-baseline --hbm-nodes 0 --pcie-steps 0 \
+          timeout -k 10 200 python -u bench.py --gpus 1 --steps 5 --warmup 3 --full --no-pmc --no-cpu-baseline --hbm-nodes 0 --pcie-steps 0 \
             --emit-steps 8 > $O/emit_${v}_$i.json 2> $O/emit_${v}_$i.err || { cp $O/cur_emit.so $L; tail -20 $O/emit_${v}_$i.err; exit 1; }
           python -c "import json; e=json.load(open('$O/emit_${v}_$i.json'))['patch_emit']; print('$v', $i, e['patches_per_s'], 'us', e['avg_emit_us'], 'GBps', e['written_GBps'])"
         done
@@ -217,7 +217,7 @@ h=d.get('hbm_working_set') or {};print('hbm',h.get('kernel'),h.get('avg_launch_u
     emittrace)  # kernel trace of the emitter per variant: in-tree libkwok_emit.so and tools/ab/<so>[,<so>...]
       TRACE
       L=$R/kwok_amd/lib/libkwok_emit.so; cp $L $O/cur_emit.so
-      E="$R/bench.py --gpus 1 --steps 2 --warmup 2 --no-pmc --no-cpu-baseline --hbm-nodes 0 --pcie-steps 0 --emit-steps 3"
+      E="$R/bench.py --gpus 1 --steps 2 --warmup 2 --full --no-pmc --no-cpu-baseline --hbm-nodes 0 --pcie-steps 0 --emit-steps 3"
       for v in cur ${arg//,/ }; do
         if [ $v = cur ]; then cp $O/cur_emit.so $L; else cp $R/tools/ab/$v $L; fi
         timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/et_$v -o run -- python3 $E > $O/et_$v.json 2> $O/et_$v.err \

@@ -226,7 +226,7 @@ def child_c5(name, steps, nodes=0):
     from kwok_amd.host import abi
     abi.LIB_PATH = os.path.join(OUT, f"libkwok_engine_{name}.so")
     import bench
-    sys.argv = ["bench.py", "--steps", str(steps), "--warmup", "5", "--no-pmc", "--no-cpu-baseline", "--hbm-nodes", "0",
+    sys.argv = ["bench.py", "--steps", str(steps), "--warmup", "5", "--full", "--no-pmc", "--no-cpu-baseline", "--hbm-nodes", "0",
                 "--pcie-steps", "0", "--emit-steps", "0"] + (["--nodes", str(nodes)] if nodes else [])
     bench.main()
 
