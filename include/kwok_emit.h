@@ -81,8 +81,8 @@ typedef struct {
   uint8_t reserved;
 } kwk_emit_item;
 
-#define KWK_EMIT_FROM_RECORDS 0u /* kwk_fired_device's list (kwk_fired_compact) */
-#define KWK_EMIT_FROM_PACKED 1u  /* kwk_fired_packed_device's list (kwk_fired_compact_packed) */
+#define KWK_EMIT_FROM_RECORDS 0u /* kwk_fired_device(KWK_COMPACT_REC)'s list */
+#define KWK_EMIT_FROM_PACKED 1u  /* kwk_fired_device(KWK_COMPACT_PACKED)'s list */
 /* (round 5: the wave-per-record writers selected by bits 8 / 9 are retired — measured slower than
  * the lane-per-record writer; any other bit of source is KWK_EINVAL) */
 

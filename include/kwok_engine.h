@@ -16,7 +16,7 @@
  *     pkg/utils/queue/weight_delaying_queue.go:73-174
  *   (node: node_controller.go:262-319; generic: stage_controller.go:174-232)
  *   playStage's state change (finalizers, delete,         applied on device as delta ops;
- *     patches) pod_controller.go:290-360,                   the fired list (kwk_fired) is
+ *     patches) pod_controller.go:290-360,                   the fired list (kwk_fired_read) is
  *     pkg/utils/lifecycle/next.go:43-88,                    what Go renders text patches for
  *     pkg/utils/lifecycle/finalizers.go:83-111
  *   informer Added/Modified events -> preprocessChan      kwk_load / kwk_upsert (pre-interned
@@ -299,28 +299,99 @@ kwk_status kwk_step(kwk_engine* eng, int64_t now_ns, uint64_t seed, uint64_t ste
  * time are then readable with kwk_read (the reference-interface mirror's Match). */
 kwk_status kwk_match(kwk_engine* eng, int64_t now_ns, uint64_t seed, uint64_t step);
 
-/* Fired hand-back (the objects Go renders patches for, pod_controller.go:290-360).  The sweep
- * leaves per-(tile, wave) segments; kwk_fired_compact enqueues their scan + compaction into one
- * dense device list (enqueue only: call it after kwk_step to keep the list on the device, e.g.
- * for an in-process consumer through kwk_fired_device).  kwk_fired copies the LAST step's list
- * (compacting first if needed) into host memory — a kwk_alloc_host buffer makes the copy a
- * direct DMA — and synchronises.  Records are grouped by sweep region (ascending regions: a
- * wave's 512-2048 slots in the 2-byte sweeps, a tile's 2048 / 4096 slots in the 8- / 4-byte word
- * sweep), unordered within a region; each fired slot appears once.  A step that swept nothing
- * (no active slots) leaves an empty list.
- * Every compaction writes a list of its own in a ring of device lists tagged with the step it
- * compacted (DESIGN.md §5 "Hand-back"): the last one is the engine's list the readers below
- * return, and the lists of the last kwk_fired_keep() compactions stay readable by step number
- * through kwk_fired_fetch_step — every step of a kwk_step_n / _pair call, fused or not. */
-kwk_status kwk_fired_compact(kwk_engine* eng);
-/* n steps (now0 + k * dt, step0 + k for k < n), each with its hand-back in the given format when
+/* ------------------------------------------------------------------ fired hand-back */
+/* The objects Go renders patches for (pod_controller.go:290-360).  The sweep leaves per-(tile, wave)
+ * segments of fired records; a compaction (kwk_fired_compact, or every step of kwk_step_n / _pair /
+ * kwk_tick with a compact argument) enqueues their scan + copy into one dense device list in one of
+ * four formats.  One code names a format everywhere: the `compact` argument of kwk_step_n / _pair,
+ * kwk_fetch_info.format, and the `format` argument of kwk_fired_compact / _read / _device.  In every
+ * format the records are grouped by sweep region (ascending regions: a wave's 512-2048 slots in the
+ * 2-byte sweeps, a tile's 2048 / 4096 slots in the 8- / 4-byte word sweep), unordered within a
+ * region, each fired slot once, and the (slot, stage) sequence is the same.  A step that swept
+ * nothing (no active slots) leaves an empty list.
+ *
+ * KWK_COMPACT_REC: kwk_fired_rec, 8 bytes per transition, all three KWK_FIRED_* flags.
+ *
+ * KWK_COMPACT_PACKED: 4-byte records, half the bytes over HBM and PCIe: KWK_FIRED_PACKED_STAGE(r) =
+ * r >> 27 (stage index), KWK_FIRED_PACKED_SLOT(r) = r & (2^27 - 1).  The flags of kwk_fired_rec are
+ * not carried: DELETED is the stage's KWK_NEXT_DELETE, DELTA_UNKNOWN the (class, stage) delta the
+ * host loaded, REMATCH is the device's own business.  Engines of at most 2^27 slots (KWK_ECAP
+ * otherwise). */
+#define KWK_COMPACT_REC 1u
+#define KWK_COMPACT_PACKED 2u
+#define KWK_FIRED_PACKED_STAGE(r) ((uint32_t)(r) >> 27)
+#define KWK_FIRED_PACKED_SLOT(r) ((uint32_t)(r) & 0x7FFFFFFu)
+/* KWK_COMPACT_PACKED16: 2 bytes per transition, for engines on the 1-byte dictionary sweep with at
+ * most 4 stages (the C1 / C5 pod-fast shape): the sweep's own records {offset: 11, stage: 2,
+ * flags: 3} copied into one dense list, grouped by segment, plus the records per segment
+ * (seg_counts).  Segment s (in order) covers slots [s * region_slots, (s + 1) * region_slots); a
+ * record r of it is slot s * region_slots + KWK_FIRED16_SLOT(r), stage KWK_FIRED16_STAGE(r), flags
+ * KWK_FIRED16_FLAGS(r) (the KWK_FIRED_* bits). */
+#define KWK_COMPACT_PACKED16 3u
+#define KWK_FIRED16_STAGE(r) (((uint32_t)(r) >> 11) & 3u)
+#define KWK_FIRED16_FLAGS(r) (((uint32_t)(r) >> 13) & 7u)
+#define KWK_FIRED16_SLOT(r)                                                                                   \
+  (((((uint32_t)(r) & 0x7FFu) >> 8) >> 2) * 1024u + (((((uint32_t)(r) & 0x7FFu) >> 2) & 63u) ^ (((uint32_t)(r) & 0x7FFu) >> 8)) * 16u + \
+   ((((uint32_t)(r) & 0x7FFu) >> 8) & 3u) * 4u + ((uint32_t)(r) & 3u))
+/* KWK_COMPACT_BITS: ~1.1 bytes per transition (C5's 10 % firing), for the same engines as the 2-byte
+ * records: per segment s of n (slots [s * region_slots, (s + 1) * region_slots)) a 2048-bit fired
+ * map, bit i set when the object of KWK_BITS_SLOT(i) fired, kept byte-sparse, and the 2-bit stage
+ * codes of its set bits in bit order.  Words:
+ *   s < n                 segment s: records c (bits 0-15), nonzero map bytes z (bits 16-31)
+ *   n + P(s) ...          segment s: 8 summary words (bit t of word w: map byte 32 w + t is
+ *                         nonzero), its z nonzero map bytes in order (padded to a word), its c
+ *                         codes, 16 per word (code j at bits 2 (j % 16) of word j / 16; padded)
+ * with P(s) = sum over t < s of (8 + ceil(z_t / 4) + ceil(c_t / 16)).  The flags are not carried (as
+ * KWK_COMPACT_PACKED). */
+#define KWK_COMPACT_BITS 4u
+#define KWK_BITS_SLOT(i) KWK_FIRED16_SLOT(((((uint32_t)(i) & 7u) << 8) | ((((uint32_t)(i) >> 5) & 63u) << 2 ^ (((uint32_t)(i) & 7u) << 2)) | (((uint32_t)(i) >> 3) & 3u)))
+
+/* The shape of a list handed to the host (kwk_fired_read, kwk_fired_fetch) */
+typedef struct {
+  uint32_t n_records;      /* transitions in the list (records; the bitmap hand-back: its set bits) */
+  uint32_t record_bytes;   /* 2 (KWK_COMPACT_PACKED16), 4 (KWK_COMPACT_PACKED), 8 (KWK_COMPACT_REC), 0 (KWK_COMPACT_BITS) */
+  uint32_t n_segs;         /* 2-byte records / bitmap hand-back: segments (seg_counts entries copied), else 0 */
+  uint32_t region_slots;   /* 2-byte records / bitmap hand-back: slots per segment, else 0 */
+  uint32_t format;         /* KWK_COMPACT_REC, _PACKED, _PACKED16 or _BITS */
+  uint32_t reserved;
+  uint64_t bytes;          /* bytes of the list (copied into out; the bitmap hand-back: 4 x its words) */
+  uint64_t step;           /* the step whose list it is */
+} kwk_fetch_info;
+
+/* Every compaction writes a list of its own in a ring of device lists tagged with the step it
+ * compacted (DESIGN.md §5 "Hand-back"): the last one is the engine's list, and the lists of the last
+ * kwk_fired_keep() compactions stay readable by step number through kwk_fired_fetch — every step of
+ * a kwk_step_n / _pair call, fused or not.
+ *
+ * kwk_fired_compact: the last step's list compacted in `format` (enqueue only: call it after kwk_step
+ * to keep the list on the device, e.g. for an in-process consumer through kwk_fired_device).  Like
+ * kwk_step_n, it falls back to KWK_COMPACT_PACKED when KWK_COMPACT_PACKED16 or _BITS is asked of a
+ * sweep without 2-byte records (the list's format is then kwk_fetch_info.format of a fetch); the
+ * explicit reader kwk_fired_read refuses instead. */
+kwk_status kwk_fired_compact(kwk_engine* eng, uint32_t format);
+/* The LAST step's list in `format` copied into host memory on the engine's stream, then a
+ * synchronise — a kwk_alloc_host buffer makes the copy a direct DMA.  When the engine's list is in
+ * another format (or not compacted) it is compacted first from the sweep's intact segments, so
+ * KWK_COMPACT_REC after a packed compaction still returns the full records, flags included.
+ * out = NULL (and seg_counts = NULL): sizes only, in *info; the usual protocol is that call, then one
+ * with a buffer of info->bytes.  seg_counts (KWK_COMPACT_PACKED16 only; may be NULL): the records per
+ * segment, info->n_segs entries.  info->n_segs and region_slots are set for KWK_COMPACT_PACKED16 and
+ * _BITS, also after a step that swept nothing.  KWK_ECAP: cap_bytes or seg_cap too small, or
+ * KWK_COMPACT_PACKED on an engine of more than 2^27 slots.  KWK_ESTATE: KWK_COMPACT_PACKED16 or _BITS
+ * when the last sweep has no 2-byte records (use KWK_COMPACT_PACKED). */
+kwk_status kwk_fired_read(kwk_engine* eng, uint32_t format, void* out, uint64_t cap_bytes, uint32_t* seg_counts,
+                          uint32_t seg_cap, kwk_fetch_info* info);
+/* device pointers of the engine's list and of its u32 length (records; KWK_COMPACT_BITS: {words,
+ * records}), valid until the next kwk_step; KWK_ESTATE unless the list is compacted in `format` */
+kwk_status kwk_fired_device(kwk_engine* eng, uint32_t format, const void** list, const uint32_t** count);
+/* n steps (now0 + k * dt, step0 + k for k < n), each with its hand-back in the format `compact` when
  * compact != 0 (enqueue only): the per-tick loop of kwk_step / kwk_fired_compact in one call.
  * On 1-byte engines with <= 4 stages and no delayed stage (KWK_TUNE_FUSE_STEPS) the steps are swept
  * in launches of up to 4 steps (each id read and written once per launch) and the launch's
  * hand-backs run as one launch: results are those of the per-step calls, and every step's list is
- * compacted into its own ring slot (tag step0 + k), so kwk_fired_fetch_step(eng, step0 + k, ...)
- * reads it while the ring holds it.  The engine's readers (kwk_fired*, kwk_fired_fetch_async) return
- * the call's last step.  With ev_every > 0, events 2i / 2i + 1 (kwk_event_record) bracket the sweep
+ * compacted into its own ring slot (tag step0 + k), so kwk_fired_fetch(eng, step0 + k, ...)
+ * reads it while the ring holds it.  The engine's list (kwk_fired_read, kwk_fired_fetch(KWK_STEP_LAST))
+ * is the call's last step's.  With ev_every > 0, events 2i / 2i + 1 (kwk_event_record) bracket the sweep
  * LAUNCH containing the first step j = ev_j0 + k that is a multiple of ev_every (i = j / ev_every):
  * that launch sweeps kwk_last_sweep().steps steps (1, 2 or 4; ev_every 2 or 3 caps launches at 2
  * steps, 1 disables the fusion), so a caller turning an event pair into per-step time divides by
@@ -334,95 +405,29 @@ kwk_status kwk_step_n(kwk_engine* eng, uint32_t n, int64_t now0_ns, int64_t dt_n
  * Messages: eng's handle. */
 kwk_status kwk_step_n_pair(kwk_engine* eng, kwk_engine* other, uint32_t n, int64_t now0_ns, int64_t dt_ns, uint64_t seed,
                            uint64_t step0, uint32_t compact, uint32_t ev_every, uint32_t ev_j0);
-kwk_status kwk_fired(kwk_engine* eng, kwk_fired_rec* out, uint32_t cap, uint32_t* n_out);
-/* device pointers of the compacted list and of its u32 count (valid until the next kwk_step) */
-kwk_status kwk_fired_device(kwk_engine* eng, const kwk_fired_rec** recs, const uint32_t** count);
-/* The same hand-back as 4-byte packed records, half the bytes over HBM and PCIe:
- * KWK_FIRED_PACKED_STAGE(r) = r >> 27 (stage index), KWK_FIRED_PACKED_SLOT(r) = r & (2^27 - 1); same
- * order as kwk_fired.  The flags of kwk_fired_rec are not carried: DELETED is the stage's
- * KWK_NEXT_DELETE, DELTA_UNKNOWN the (class, stage) delta the host loaded, REMATCH is the device's
- * own business (kwk_fired still returns all three).  Engines of at most 2^27 slots (KWK_ECAP
- * otherwise).  kwk_step_n(..., compact = KWK_COMPACT_PACKED, ...) / KWK_TICK_COMPACT_PACKED enqueue
- * it per step. */
-#define KWK_COMPACT_PACKED 2u
-#define KWK_FIRED_PACKED_STAGE(r) ((uint32_t)(r) >> 27)
-#define KWK_FIRED_PACKED_SLOT(r) ((uint32_t)(r) & 0x7FFFFFFu)
-kwk_status kwk_fired_compact_packed(kwk_engine* eng);
-/* The hand-back at 2 bytes per transition, for engines on the 1-byte dictionary sweep with at most 4
- * stages (the C1 / C5 pod-fast shape; KWK_ESTATE otherwise: use kwk_fired_packed): the sweep's
- * own records {offset: 11, stage: 2, flags: 3} copied into one dense list, grouped by segment, plus
- * the records per segment.  Segment s (in order) covers slots [s * region_slots, (s + 1) *
- * region_slots); a record r of it is slot s * region_slots + KWK_FIRED16_SLOT(r), stage
- * KWK_FIRED16_STAGE(r), flags KWK_FIRED16_FLAGS(r) (the KWK_FIRED_* bits).  Same (slot, stage)
- * sequence as kwk_fired.  kwk_step_n(..., KWK_COMPACT_PACKED16, ...) enqueues it per step (an engine
- * without 2-byte records then leaves the 4-byte packed list). */
-#define KWK_COMPACT_PACKED16 3u
-#define KWK_FIRED16_STAGE(r) (((uint32_t)(r) >> 11) & 3u)
-#define KWK_FIRED16_FLAGS(r) (((uint32_t)(r) >> 13) & 7u)
-#define KWK_FIRED16_SLOT(r)                                                                                   \
-  (((((uint32_t)(r) & 0x7FFu) >> 8) >> 2) * 1024u + (((((uint32_t)(r) & 0x7FFu) >> 2) & 63u) ^ (((uint32_t)(r) & 0x7FFu) >> 8)) * 16u + \
-   ((((uint32_t)(r) & 0x7FFu) >> 8) & 3u) * 4u + ((uint32_t)(r) & 3u))
-kwk_status kwk_fired_compact_packed16(kwk_engine* eng);
-kwk_status kwk_fired_packed16(kwk_engine* eng, uint16_t* out, uint32_t cap, uint32_t* n_out, uint32_t* seg_counts,
-                              uint32_t seg_cap, uint32_t* n_segs, uint32_t* region_slots);
-/* The hand-back at ~1.1 bytes per transition (C5's 10 % firing), for the same engines as the 2-byte
- * records: per segment s of n (slots [s * region_slots, (s + 1) * region_slots)) a 2048-bit fired
- * map, bit i set when the object of KWK_BITS_SLOT(i) fired, kept byte-sparse, and the 2-bit stage
- * codes of its set bits in bit order.  Words:
- *   s < n                 segment s: records c (bits 0-15), nonzero map bytes z (bits 16-31)
- *   n + P(s) ...          segment s: 8 summary words (bit t of word w: map byte 32 w + t is
- *                         nonzero), its z nonzero map bytes in order (padded to a word), its c
- *                         codes, 16 per word (code j at bits 2 (j % 16) of word j / 16; padded)
- * with P(s) = sum over t < s of (8 + ceil(z_t / 4) + ceil(c_t / 16)).  Same (slot, stage) sequence
- * as kwk_fired; the flags are not carried (as KWK_COMPACT_PACKED).  n_words: the list's words,
- * n_records: its transitions.  kwk_step_n(..., KWK_COMPACT_BITS, ...) enqueues it per step (an
- * engine without 2-byte records then leaves the 4-byte packed list). */
-#define KWK_COMPACT_BITS 4u
-#define KWK_BITS_SLOT(i) KWK_FIRED16_SLOT(((((uint32_t)(i) & 7u) << 8) | ((((uint32_t)(i) >> 5) & 63u) << 2 ^ (((uint32_t)(i) & 7u) << 2)) | (((uint32_t)(i) >> 3) & 3u)))
-kwk_status kwk_fired_compact_bits(kwk_engine* eng);
-kwk_status kwk_fired_bits(kwk_engine* eng, uint32_t* out, uint64_t cap_words, uint64_t* n_words, uint32_t* n_records,
-                          uint32_t* n_segs, uint32_t* region_slots);
-kwk_status kwk_fired_packed(kwk_engine* eng, uint32_t* out, uint32_t cap, uint32_t* n_out);
-kwk_status kwk_fired_packed_device(kwk_engine* eng, const uint32_t** recs, const uint32_t** count);
-/* Overlapped hand-back to the host (the playStage workers' input, pod_controller.go:257-290): the
- * last step's compacted list (whatever kwk_fired_compact* / kwk_step_n left: 2-, 4- or 8-byte
- * records) and, for the 2-byte records, the records per segment, copied by the engine's copy
- * stream while the device goes on.  The call waits for the list's length only (the compaction of
- * that step), enqueues the copies and returns: call it after enqueuing the NEXT step's sweep and
- * the copy overlaps that sweep.  The engine's next compaction waits for the copy on the device
- * (the list is rewritten in place); the host buffers hold the copy after kwk_fired_fetch_wait (or
- * the engine's next fetch).  Buffers from kwk_alloc_host make the copies DMA; double-buffer them
- * to read one step's records while the next step's copy runs.  seg_counts may be NULL. */
-typedef struct {
-  uint32_t n_records;      /* transitions in the list (records; the bitmap hand-back: its set bits) */
-  uint32_t record_bytes;   /* 2 (KWK_COMPACT_PACKED16), 4 (KWK_COMPACT_PACKED), 8 (kwk_fired_rec), 0 (KWK_COMPACT_BITS) */
-  uint32_t n_segs;         /* 2-byte records / bitmap hand-back: segments (seg_counts entries copied), else 0 */
-  uint32_t region_slots;   /* 2-byte records / bitmap hand-back: slots per segment, else 0 */
-  uint32_t format;         /* KWK_COMPACT_PACKED16, _PACKED, _BITS or 1 (kwk_fired_rec) */
-  uint32_t reserved;
-  uint64_t bytes;          /* bytes copied into out */
-  uint64_t step;           /* the step whose list was copied */
-} kwk_fetch_info;
-kwk_status kwk_fired_fetch_async(kwk_engine* eng, void* out, uint64_t cap_bytes, uint32_t* seg_counts, uint32_t seg_cap,
-                                 kwk_fetch_info* info);
-kwk_status kwk_fired_fetch_wait(kwk_engine* eng);
-
-/* Every step's hand-back to the host, fused steps included (the playStage workers' input for each
- * step, pod_controller.go:257-290).  kwk_fired_keep(eng, depth) keeps the lists of the last `depth`
+/* Overlapped hand-back to the host, every step's, fused steps included (the playStage workers'
+ * input, pod_controller.go:257-290).  kwk_fired_keep(eng, depth) keeps the lists of the last `depth`
  * compactions (1..64, at least 4: a fused launch's steps; 0 = the default: the last 4, no per-step
- * completion signal) in the device
- * ring and makes every compaction signal its own completion and write its length to pinned host
- * memory.  kwk_fired_fetch_step(eng, step, ...) is kwk_fired_fetch_async for the list of step
- * `step` (the step argument of kwk_step / kwk_step_n's step0 + k): it waits for THAT step's
- * compaction only (later steps go on running), enqueues the copies on the copy stream and returns;
- * the ring slot is rewritten only after its copy (the compaction waits on the device).  So a host
- * calls kwk_step_n(eng, n, ...) and then kwk_fired_fetch_step for step0 .. step0 + n - 1, each copy
- * overlapping the later steps' sweeps, and reads the buffers after kwk_fired_fetch_wait.  KWK_ESTATE
- * when the ring no longer holds that step. */
+ * completion signal) in the device ring and makes every compaction signal its own completion and
+ * write its length to pinned host memory.
+ * kwk_fired_fetch(eng, step, ...) copies the list of step `step` (the step argument of kwk_step /
+ * kwk_step_n's step0 + k; whatever format its compaction left) and, for the 2-byte records, the
+ * records per segment (seg_counts may be NULL) on the engine's copy stream while the device goes
+ * on: it waits for THAT step's compaction only (later steps go on running), enqueues the copies and
+ * returns the list's shape; the ring slot is rewritten only after its copy (the compaction waits on
+ * the device).  The host buffers hold the copy after kwk_fired_fetch_wait (or the engine's next
+ * fetch); buffers from kwk_alloc_host make the copies DMA.  So a host calls kwk_step_n(eng, n, ...)
+ * and then kwk_fired_fetch for step0 .. step0 + n - 1, each copy overlapping the later steps'
+ * sweeps.  KWK_ESTATE when the ring no longer holds that step.
+ * step = KWK_STEP_LAST: the engine's last list — KWK_ESTATE when the last step's list is not
+ * compacted, a zeroed *info after a step that swept nothing.  Called after enqueuing the NEXT
+ * step's sweep, the copy overlaps that sweep. */
+#define KWK_STEP_LAST UINT64_MAX
 kwk_status kwk_fired_keep(kwk_engine* eng, uint32_t depth);
-kwk_status kwk_fired_fetch_step(kwk_engine* eng, uint64_t step, void* out, uint64_t cap_bytes, uint32_t* seg_counts,
-                                uint32_t seg_cap, kwk_fetch_info* info);
-/* pinned (page-locked) host buffers for kwk_fired / kwk_read / usage outputs, reused across steps */
+kwk_status kwk_fired_fetch(kwk_engine* eng, uint64_t step, void* out, uint64_t cap_bytes, uint32_t* seg_counts,
+                           uint32_t seg_cap, kwk_fetch_info* info);
+kwk_status kwk_fired_fetch_wait(kwk_engine* eng);
+/* pinned (page-locked) host buffers for kwk_fired_read / kwk_read / usage outputs, reused across steps */
 kwk_status kwk_alloc_host(uint64_t bytes, void** out);
 kwk_status kwk_free_host(void* p);
 /* cumulative counters (synchronises) */
@@ -619,16 +624,16 @@ kwk_status kwk_lease_sync_pods(kwk_engine* pods, const kwk_engine* nodes, uint32
 
 /* The fused reconciliation tick (C3 and any node + pod deployment): the per-tick sequence of
  *   kwk_lease_step(nodes) -> kwk_lease_sync_pods(pods, nodes, node_ptr) -> kwk_step(nodes) ->
- *   kwk_step(pods)   (+ kwk_fired_compact on both with KWK_TICK_COMPACT)
+ *   kwk_step(pods)   (+ kwk_fired_compact(KWK_COMPACT_REC) on both with KWK_TICK_COMPACT)
  * enqueued by one call, with the two engines' streams ordered by HIP events instead of host
  * synchronisations (kwk_lease_sync_pods synchronises the node stream each call).  Results are
  * those of the separate calls.  Lease ops / fired lists / stats are read as after the separate
- * calls (kwk_lease_ops, kwk_fired on either engine).  kwk_tick_bind registers the pods' node_ptr
+ * calls (kwk_lease_ops, kwk_fired_read on either engine).  kwk_tick_bind registers the pods' node_ptr
  * (node-sorted pods, as kwk_lease_sync_pods) once; pods = NULL runs the node engine alone (its
  * lease step only if kwk_lease_config was called).  kwk_tick_n: n ticks at now0 + k * dt,
  * step0 + k (enqueue only; the last tick's lease ops / fired lists are readable). */
 #define KWK_TICK_COMPACT (1u << 0)
-#define KWK_TICK_COMPACT_PACKED (1u << 1) /* the hand-back as packed 4-byte records (kwk_fired_compact_packed) */
+#define KWK_TICK_COMPACT_PACKED (1u << 1) /* the hand-back as packed 4-byte records (KWK_COMPACT_PACKED) */
 kwk_status kwk_tick_bind(kwk_engine* pods, const kwk_engine* nodes, uint32_t n_nodes, const uint32_t* node_ptr);
 kwk_status kwk_tick(kwk_engine* nodes, kwk_engine* pods, int64_t now_ns, uint64_t seed, uint64_t step, uint32_t flags);
 kwk_status kwk_tick_n(kwk_engine* nodes, kwk_engine* pods, uint32_t n, int64_t now0_ns, int64_t dt_ns, uint64_t seed,
@@ -658,7 +663,7 @@ kwk_status kwk_aggregate_read(kwk_engine* eng, double* host_out, uint32_t n);
 
 /* raw device pointers for in-process consumers (RCCL aggregates, profiling): state = the
  * state stream (kwk_step_stats.state_bytes per slot); fired / wave_counts = the sweep's
- * internal fired segments and per-segment counts (valid after kwk_fired) */
+ * internal fired segments and per-segment counts (valid after kwk_fired_read) */
 kwk_status kwk_device_ptrs(kwk_engine* eng, void** state, void** fired, void** wave_counts);
 
 /* the engine's HIP stream (hipStream_t): in-process consumers order their own work after the
@@ -687,9 +692,11 @@ typedef struct {
   uint32_t steps;        /* steps the launch swept: 2 or 4 when fused (KWK_TUNE_FUSE_STEPS), else 1 (0: unset) */
 } kwk_sweep_info;
 kwk_status kwk_last_sweep(kwk_engine* eng, kwk_sweep_info* out);
-/* 2 since round 6: the hand-back ring (kwk_fired_keep / kwk_fired_fetch_step, kwk_fetch_info.step),
- * KWK_TUNE_FOLD_HB and kwk_fired_fold16 retired, kwk_sweep_info.steps (was reserved) */
-#define KWK_ABI_VERSION 2u
+/* 2 since round 6: the hand-back ring (kwk_fired_keep, kwk_fetch_info.step), KWK_TUNE_FOLD_HB and
+ * kwk_fired_fold16 retired, kwk_sweep_info.steps (was reserved).
+ * 3: the fourteen per-format kwk_fired* entry points became six taking a KWK_COMPACT_* format
+ * (kwk_fired_compact / _read / _device / _keep / _fetch / _fetch_wait), KWK_COMPACT_REC, KWK_STEP_LAST */
+#define KWK_ABI_VERSION 3u
 uint32_t kwk_abi_version(void);
 uint32_t kwk_tile_objects(void); /* objects per sweep workgroup */
 

@@ -9,7 +9,7 @@
  * structure resolved, mapping keys in encoding/json's sorted order, literals as their final
  * JSON bytes — and this library fills the slots from each object's JSON.
  *
- * A Go host binds it next to kwok_engine.h: after kwk_fired, it renders the
+ * A Go host binds it next to kwok_engine.h: after kwk_fired_read, it renders the
  * patches of the fired objects in one call and sends them; objects whose status is
  * KWK_PATCH_NEEDS_RENDER go through the existing gotpl renderer.
  */

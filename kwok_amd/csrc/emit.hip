@@ -1208,15 +1208,14 @@ kwk_status kwk_emit(kwk_emitter* em, int64_t now_ns, uint32_t source) {
   EmitArgs a{};
   a.p = em->p;
   const uint32_t from = source & 0xFFu;
-  if (from == KWK_EMIT_FROM_RECORDS) {
-    if (kwk_fired_device(em->eng, &a.recs, &a.count) != KWK_OK)
-      return fail(KWK_ESTATE, std::string("kwk_fired_device: ") + kwk_last_error(em->eng));
-  } else if (from == KWK_EMIT_FROM_PACKED) {
-    if (kwk_fired_packed_device(em->eng, &a.packed, &a.count) != KWK_OK)
-      return fail(KWK_ESTATE, std::string("kwk_fired_packed_device: ") + kwk_last_error(em->eng));
-  } else {
+  if (from != KWK_EMIT_FROM_RECORDS && from != KWK_EMIT_FROM_PACKED)
     return fail(KWK_EINVAL, "source must be KWK_EMIT_FROM_RECORDS or KWK_EMIT_FROM_PACKED");
-  }
+  const void* list = nullptr;
+  if (kwk_fired_device(em->eng, from == KWK_EMIT_FROM_PACKED ? KWK_COMPACT_PACKED : KWK_COMPACT_REC, &list, &a.count) !=
+      KWK_OK)
+    return fail(KWK_ESTATE, std::string("kwk_fired_device: ") + kwk_last_error(em->eng));
+  if (from == KWK_EMIT_FROM_PACKED) a.packed = static_cast<const uint32_t*>(list);
+  else a.recs = static_cast<const kwk_fired_rec*>(list);
   if (source & ~0xFFu) return fail(KWK_EINVAL, "unknown source flags");
   if (kwk_status st = bind(em)) return st;
   if (!em->d_offsets)

@@ -2366,7 +2366,7 @@ __device__ __forceinline__ void store_rec_nt(kwk_fired_rec* p, uint32_t slot, ui
   __builtin_nontemporal_store(u32x2{slot, ((x >> 13) & 31u) | ((x >> 18) & 7u) << 16}, reinterpret_cast<u32x2*>(p));
 }
 
-// the packed 4-byte record {stage: 31..27, slot: 26..0} (kwk_fired_packed), nontemporal
+// the packed 4-byte record {stage: 31..27, slot: 26..0} (KWK_COMPACT_PACKED), nontemporal
 __device__ __forceinline__ void store_packed_nt(uint32_t* p, uint32_t slot, uint32_t x) {
   __builtin_nontemporal_store(((x >> 13) & 31u) << 27 | slot, p);
 }
@@ -2381,7 +2381,7 @@ __device__ __forceinline__ void store_out(const CompactArgs& a, uint32_t at, uin
 // and offset (a segment holds at least 64 * 16 + 31 words, so the loads stay inside it), all the
 // wave's segments' loads in flight at once: at C5 (48k segments) one segment per wave ran six
 // dispatch rounds of a ~3.5 us load chain (21 us); four per wave keep every wave resident.
-// kPacked: 4-byte records (kwk_fired_packed) instead of kwk_fired_rec — half the bytes written
+// kPacked: 4-byte records (KWK_COMPACT_PACKED) instead of kwk_fired_rec — half the bytes written
 constexpr uint32_t kCompactSpw = 4;
 constexpr uint32_t kCompact16Spw = 8;  // segments per wave of the 2-byte compaction (4 before round 6: C5 1.83 -> 1.90-1.92e11, r6af)
 template <int kRec, bool kPacked = false, uint32_t kSpw = 1>
@@ -2428,7 +2428,7 @@ __global__ __launch_bounds__(kBlock) void compact_kernel(CompactArgs a) {
   }
 }
 
-// The 2-byte hand-back (kwk_fired_compact_packed16): the 1-byte sweep's <= 4-stage records
+// The 2-byte hand-back (KWK_COMPACT_PACKED16): the 1-byte sweep's <= 4-stage records
 // {LDS offset: 11, stage: 2, flags: 3} copied as they are into one dense list at their segment's
 // offset; the host maps a record to its slot with its segment's region (KWK_FIRED16_SLOT)
 template <uint32_t kSpw>
@@ -2550,7 +2550,7 @@ __global__ __launch_bounds__(kBlock) void compact16_small_multi_kernel(CompactAr
   compact16_small_block<kSmall16Spw>(m.a[blockIdx.y], blockIdx.x);
 }
 
-// The bitmap hand-back (kwk_fired_compact_bits): the 1-byte sweep's <= 4-stage records as one
+// The bitmap hand-back (KWK_COMPACT_BITS): the 1-byte sweep's <= 4-stage records as one
 // 2048-bit map per segment — bit i = lane * 32 + k for the id at lds_id8(k, lane * 4), the order
 // the sweep's work list (lane-major, k ascending) writes its records in — kept byte-sparse, plus
 // the records' 2-bit stage codes in that same order.  For n segments:
@@ -4529,6 +4529,11 @@ __global__ void lease_fail_kernel(LeaseArgs a, const uint32_t* __restrict__ slot
 }  // namespace
 
 // ------------------------------------------------------------------ engine object
+// The format of a hand-back list (the ABI's KWK_COMPACT_* codes: hb_fmt_of / hb_code): kwk_fired_rec,
+// packed 4-byte records, the 2-byte records or the bitmap hand-back where the sweep wrote 2-byte
+// records (enqueue_compact leaves the 4-byte packed list where it did not)
+enum class HbFmt : uint8_t { Rec, Packed, Packed16, Bits };
+
 struct kwk_engine {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -4540,16 +4545,14 @@ struct kwk_engine {
   uint32_t last_objs = 16;    // words per lane of the last sweep (fired segment stride = 64 * last_objs + 32)
   uint32_t last_region_shift = 0;  // fired segments per record region = 1 << shift (wave: 0, tile: 2)
   int last_rec = 0;                // record kind of the last sweep's segments (kRecSlot / kRecId8 / kRecId8Half)
-  bool compacted = false;     // the last sweep's fired list is compacted on the device
-  bool compacted_packed = false;  // ... as 4-byte packed records (kwk_fired_compact_packed)
-  bool compacted_16 = false;      // ... as the 1-byte sweep's 2-byte records (kwk_fired_compact_packed16)
-  bool compacted_bits = false;    // ... as its per-segment maps + stage codes (kwk_fired_compact_bits)
+  bool compacted = false;     // the last sweep's fired list is compacted on the device: hb[hb_cur], in its mode
+                              // (set by hb_commit, cleared by the next sweep)
   // The hand-back ring (DESIGN.md §5 "Hand-back"): every compaction writes a slot of its own, in
   // turn — the step's dense list, its scan offsets ([0] = the length) and group totals, the bitmap
   // hand-back's {words, records} and, for 2-byte / bitmap lists, the step's records per segment
   // (the next sweep rewrites d_wave_counts) — tagged with the step it compacted.  So the lists of
-  // the last hb.size() compactions stay readable by step (kwk_fired_fetch_step: every step of a
-  // kwk_step_n call, fused or not), hb[hb_cur] is the engine's last list (kwk_fired*), and a
+  // the last hb.size() compactions stay readable by step (kwk_fired_fetch: every step of a
+  // kwk_step_n call, fused or not), hb[hb_cur] is the engine's last list (kwk_fired_read / _device), and a
   // compaction waits on the device only for the copy of the slot it rewrites.
   struct HbSlot {
     void* list = nullptr;
@@ -4564,7 +4567,7 @@ struct kwk_engine {
     bool copy_pending = false;       // ev_copied recorded and not yet waited for by a compaction
     bool valid = false;
     uint64_t step = 0;               // the step whose list the slot holds
-    int mode = 0;                    // enqueue_compact's mode
+    HbFmt mode = HbFmt::Rec;         // the format of the slot's list
     uint32_t n_segs = 0, region_slots = 0;
   };
   std::vector<HbSlot> hb = std::vector<HbSlot>(kHbMin);
@@ -4574,7 +4577,7 @@ struct kwk_engine {
   uint32_t* h_len_dev = nullptr;
   uint64_t last_step_no = 0;   // the step number of the last sweep's (last) step
   hipStream_t copy_stream = nullptr;
-  hipEvent_t ev_count = nullptr;  // kwk_fired_fetch_async without kwk_fired_keep: the length's copy
+  hipEvent_t ev_count = nullptr;  // kwk_fired_fetch(KWK_STEP_LAST) without kwk_fired_keep: the length's copy
   uint32_t* h_count = nullptr;
   bool copy_recorded = false;  // a copy was enqueued (kwk_fired_fetch_wait)
   kwk_sweep_info last_sweep{};  // kwk_last_sweep
@@ -5670,12 +5673,12 @@ static kwk_status build_fsm(kwk_engine* e) {
   return KWK_OK;
 }
 
-// a hand-back the sweep may do itself (tail_handback): ring slot `slot` in `mode` (0 / 1); `done`
+// a hand-back the sweep may do itself (tail_handback): ring slot `slot` in `mode` (Rec / Packed); `done`
 // tells the caller whether it did (a one-tile-per-block 2-byte table-only sweep) or the caller
 // still has to compact
 struct TailReq {
   uint32_t slot;
-  int mode;
+  HbFmt mode;
   bool done;
 };
 static void hb_tail_args(kwk_engine* e, const TailReq& t, SweepArgs& a);
@@ -5877,23 +5880,55 @@ kwk_status kwk_sync(kwk_engine* e) {
 
 // fired hand-back on the device: per-(tile, wave) counts -> exclusive scan -> dense list in the
 // next ring slot, its length at the slot's offsets[0] (enqueue only)
-// mode: 0 kwk_fired_rec, 1 packed 4-byte records, 2 the 2-byte records where the sweep wrote them
-// (else the 4-byte packed ones), 3 the bitmap hand-back (likewise)
+
+// HbFmt <-> the ABI's KWK_COMPACT_* code (kwk_step_n's compact, kwk_fetch_info.format, the format
+// argument of kwk_fired_compact / _read / _device)
+static bool hb_fmt_of(uint32_t code, HbFmt* f) {
+  switch (code) {
+    case KWK_COMPACT_REC: *f = HbFmt::Rec; return true;
+    case KWK_COMPACT_PACKED: *f = HbFmt::Packed; return true;
+    case KWK_COMPACT_PACKED16: *f = HbFmt::Packed16; return true;
+    case KWK_COMPACT_BITS: *f = HbFmt::Bits; return true;
+  }
+  return false;
+}
+static uint32_t hb_code(HbFmt f) {
+  switch (f) {
+    case HbFmt::Packed: return KWK_COMPACT_PACKED;
+    case HbFmt::Packed16: return KWK_COMPACT_PACKED16;
+    case HbFmt::Bits: return KWK_COMPACT_BITS;
+    case HbFmt::Rec: break;
+  }
+  return KWK_COMPACT_REC;
+}
+// kwk_step_n's compact: any other nonzero value has always meant kwk_fired_rec
+static HbFmt hb_fmt_of_compact(uint32_t compact) {
+  HbFmt f = HbFmt::Rec;
+  hb_fmt_of(compact, &f);
+  return f;
+}
+// bytes per element of a list: a record, or a 32-bit word of the bitmap hand-back
+static uint32_t hb_record_bytes(HbFmt f) {
+  return f == HbFmt::Packed16 ? 2u : f == HbFmt::Rec ? (uint32_t)sizeof(kwk_fired_rec) : 4u;
+}
+// the 2-byte and bitmap lists: grouped by segment, only where the sweep wrote 2-byte records
+static bool hb_segmented(HbFmt f) { return f == HbFmt::Packed16 || f == HbFmt::Bits; }
+// the format of the engine's last list (meaningful while e->compacted)
+static HbFmt current_fmt(const kwk_engine* e) { return e->hb[e->hb_cur].mode; }
 
 // the ring slot `k` compactions after the engine's last list
 static uint32_t hb_next(const kwk_engine* e, uint32_t k = 1) { return (e->hb_cur + k) % (uint32_t)e->hb.size(); }
 
 // bytes of a slot's list in `mode` at the engine's capacity (the bitmap hand-back: at most
 // 1 + 8 + 64 + 128 words per 2048-slot segment)
-static size_t hb_list_bytes(const kwk_engine* e, int mode) {
-  if (mode == 3) return 4u * ((size_t)e->n_blocks_cap * kWavesPerBlock * 201u + 64u);
-  const size_t rb = mode == 2 ? 2u : mode == 1 ? 4u : sizeof(kwk_fired_rec);
-  return rb * (size_t)e->capacity + 64u;
+static size_t hb_list_bytes(const kwk_engine* e, HbFmt mode) {
+  if (mode == HbFmt::Bits) return 4u * ((size_t)e->n_blocks_cap * kWavesPerBlock * 201u + 64u);
+  return (size_t)hb_record_bytes(mode) * (size_t)e->capacity + 64u;
 }
 
 // slot i made ready for a compaction in `mode` on `stream`: the copy stream's last copy out of it
 // waited for on the device, its buffers (re)sized
-static kwk_status hb_prepare(kwk_engine* e, uint32_t i, int mode, hipStream_t stream) {
+static kwk_status hb_prepare(kwk_engine* e, uint32_t i, HbFmt mode, hipStream_t stream) {
   kwk_engine::HbSlot& h = e->hb[i];
   if (h.copy_pending) {
     HIP_TRY(hipStreamWaitEvent(stream, h.ev_copied, 0));
@@ -5918,8 +5953,9 @@ static kwk_status hb_prepare(kwk_engine* e, uint32_t i, int mode, hipStream_t st
   return KWK_OK;
 }
 
-// slot i now holds step `step`'s list (written by the compaction just enqueued on `stream`)
-static kwk_status hb_commit(kwk_engine* e, uint32_t i, uint64_t step, int mode, uint32_t n_segs, int done_slot,
+// slot i now holds step `step`'s list (written by the compaction just enqueued on `stream`) and is
+// the engine's last list
+static kwk_status hb_commit(kwk_engine* e, uint32_t i, uint64_t step, HbFmt mode, uint32_t n_segs, int done_slot,
                             hipStream_t stream, bool record) {
   kwk_engine::HbSlot& h = e->hb[i];
   h.valid = true;
@@ -5929,16 +5965,17 @@ static kwk_status hb_commit(kwk_engine* e, uint32_t i, uint64_t step, int mode, 
   h.region_slots = n_segs ? 64u * e->last_objs << e->last_region_shift : 0u;
   h.done_slot = done_slot;
   e->hb_cur = i;
+  e->compacted = true;
   if (e->hb_track && record) HIP_TRY(hipEventRecord(h.ev_done, stream));
   return KWK_OK;
 }
 
-static void hb_args(const kwk_engine* e, uint32_t i, int mode, CompactArgs& a) {
+static void hb_args(const kwk_engine* e, uint32_t i, HbFmt mode, CompactArgs& a) {
   const kwk_engine::HbSlot& h = e->hb[i];
   a.out = reinterpret_cast<kwk_fired_rec*>(h.list);
   a.offsets = h.offsets;
   a.group_tot = h.groups;
-  a.counts_out = mode == 2 ? h.counts : nullptr;
+  a.counts_out = mode == HbFmt::Packed16 ? h.counts : nullptr;
   a.host_len = e->hb_track ? e->h_len_dev + 2u * i : nullptr;
   a.n_segs = e->last_blocks * kWavesPerBlock;
   a.seg_region_shift = e->last_region_shift;
@@ -5950,21 +5987,17 @@ static void hb_tail_args(kwk_engine* e, const TailReq& t, SweepArgs& a) {
   const kwk_engine::HbSlot& h = e->hb[t.slot];
   if (++e->tail_seq == 0) e->tail_seq = 1;  // 0 never tags a launch (the status words start at 0)
   a.tail = SweepArgs::TailHb{h.list, h.offsets, e->hb_track ? e->h_len_dev + 2u * t.slot : nullptr, e->d_tail_status,
-                             e->tail_seq, t.mode == 1 ? 1u : 0u};
+                             e->tail_seq, t.mode == HbFmt::Packed ? 1u : 0u};
 }
 
-static kwk_status enqueue_compact(kwk_engine* e, int mode = 0, hipStream_t stream = nullptr) {
-  if (!stream) stream = e->stream;
+static kwk_status enqueue_compact(kwk_engine* e, HbFmt mode) {
+  const hipStream_t stream = e->stream;
   const uint32_t n_waves = e->last_blocks * kWavesPerBlock;
-  if ((mode == 2 || mode == 3) && e->last_rec != kRecId8Half) mode = 1;
-  const bool packed = mode == 1;
+  if (hb_segmented(mode) && e->last_rec != kRecId8Half) mode = HbFmt::Packed;
+  const bool packed = mode == HbFmt::Packed, m16 = mode == HbFmt::Packed16, bits = mode == HbFmt::Bits;
   const uint32_t i = hb_next(e);
   if (kwk_status st = hb_prepare(e, i, mode, stream)) return st;
   kwk_engine::HbSlot& h = e->hb[i];
-  e->compacted = true;
-  e->compacted_packed = packed;
-  e->compacted_16 = mode == 2;
-  e->compacted_bits = mode == 3;
   if (n_waves == 0) {  // nothing swept: the device list is empty (never the previous step's count)
     HIP_TRY(hipMemsetAsync(h.offsets, 0, sizeof(uint32_t), stream));
     HIP_TRY(hipMemsetAsync(h.tot, 0, 2 * sizeof(uint32_t), stream));
@@ -5979,13 +6012,13 @@ static kwk_status enqueue_compact(kwk_engine* e, int mode = 0, hipStream_t strea
   const int rk = e->last_rec;
   void* args[] = {&a};
   const uint32_t groups = (n_waves + kScanGroup - 1) / kScanGroup;
-  if (mode == 2 && n_waves <= e->compact_small) {
+  if (m16 && n_waves <= e->compact_small) {
     hipLaunchKernelGGL(compact16_small_kernel, dim3((n_waves + kSmall16Spb - 1) / kSmall16Spb), dim3(kBlock), 0, stream, a);
-  } else if (mode == 3 && n_waves <= e->compact_small) {
+  } else if (bits && n_waves <= e->compact_small) {
     hipLaunchKernelGGL(bits_size_kernel, dim3(blocks), dim3(kBlock), 0, stream, a, e->d_bits_wc, e->d_bits_bsum);
     hipLaunchKernelGGL(bits_write_kernel<true>, dim3(blocks), dim3(kBlock), 0, stream, a, e->d_bits_wc, e->d_bits_bsum,
                        h.tot);
-  } else if (mode != 2 && mode != 3 && n_waves <= e->compact_small) {  // one launch: prefix sums inside the expansion
+  } else if (!m16 && !bits && n_waves <= e->compact_small) {  // one launch: prefix sums inside the expansion
     const void* k = packed ? (rk == kRecId8Half ? (const void*)compact_small_kernel<kRecId8Half, true>
                               : rk == kRecId8   ? (const void*)compact_small_kernel<kRecId8, true>
                                                 : (const void*)compact_small_kernel<kRecSlot, true>)
@@ -5993,7 +6026,7 @@ static kwk_status enqueue_compact(kwk_engine* e, int mode = 0, hipStream_t strea
                               : rk == kRecId8   ? (const void*)compact_small_kernel<kRecId8>
                                                 : (const void*)compact_small_kernel<kRecSlot>);
     HIP_TRY(hipLaunchKernel(k, dim3(blocks), dim3(kBlock), args, 0, stream));
-  } else if (mode == 3) {
+  } else if (bits) {
     hipLaunchKernelGGL(bits_size_kernel, dim3(blocks), dim3(kBlock), 0, stream, a, e->d_bits_wc, e->d_bits_bsum);
     hipLaunchKernelGGL(seg_scan_kernel, dim3(groups), dim3(kBlock), 0, stream, e->d_bits_wc, n_waves, h.offsets, h.groups);
     hipLaunchKernelGGL(bits_write_kernel<false>, dim3(blocks), dim3(kBlock), 0, stream, a, e->d_bits_wc, e->d_bits_bsum,
@@ -6001,7 +6034,7 @@ static kwk_status enqueue_compact(kwk_engine* e, int mode = 0, hipStream_t strea
   } else {
     hipLaunchKernelGGL(seg_scan_kernel, dim3(groups), dim3(kBlock), 0, stream, e->d_wave_counts, n_waves, h.offsets,
                        h.groups);
-    if (mode == 2) {
+    if (m16) {
       constexpr uint32_t W16 = kCompact16Spw;
       hipLaunchKernelGGL(compact16_kernel<W16>, dim3((n_waves + W16 * kWavesPerBlock - 1) / (W16 * kWavesPerBlock)),
                          dim3(kBlock), 0, stream, a);
@@ -6021,133 +6054,8 @@ static kwk_status enqueue_compact(kwk_engine* e, int mode = 0, hipStream_t strea
   return hb_commit(e, i, e->last_step_no, mode, n_waves, (int)i, stream, true);
 }
 
-kwk_status kwk_fired_compact(kwk_engine* e) {
-  ErrScope es_(e);
-  if (!e) return fail(KWK_EINVAL, "null engine");
-  if (kwk_status st = set_dev(e)) return st;
-  return enqueue_compact(e);
-}
-
 static kwk_status packed_ok(const kwk_engine* e) {
   if (e->capacity > kPackedSlots) return fail(KWK_ECAP, "packed fired records hold 27-bit slots: engine capacity > 2^27");
-  return KWK_OK;
-}
-
-kwk_status kwk_fired_compact_packed(kwk_engine* e) {
-  ErrScope es_(e);
-  if (!e) return fail(KWK_EINVAL, "null engine");
-  if (kwk_status st = packed_ok(e)) return st;
-  if (kwk_status st = set_dev(e)) return st;
-  return enqueue_compact(e, 1);
-}
-
-kwk_status kwk_fired_packed_device(kwk_engine* e, const uint32_t** recs, const uint32_t** count) {
-  ErrScope es_(e);
-  if (!e || !recs || !count) return fail(KWK_EINVAL, "null argument");
-  if (!e->compacted || !e->compacted_packed) return fail(KWK_ESTATE, "kwk_fired_compact_packed must follow kwk_step");
-  *recs = reinterpret_cast<const uint32_t*>(e->hb[e->hb_cur].list);
-  *count = e->hb[e->hb_cur].offsets;
-  return KWK_OK;
-}
-
-// the length (or the bitmap hand-back's {words, records}) of the engine's last list (synchronises)
-static kwk_status hb_len(kwk_engine* e, uint32_t* t) {
-  const kwk_engine::HbSlot& h = e->hb[e->hb_cur];
-  HIP_TRY(hipMemcpyAsync(t, h.mode == 3 ? h.tot : h.offsets, h.mode == 3 ? 2 * sizeof(uint32_t) : sizeof(uint32_t),
-                         hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  return KWK_OK;
-}
-
-kwk_status kwk_fired_packed(kwk_engine* e, uint32_t* out, uint32_t cap, uint32_t* n_out) {
-  ErrScope es_(e);
-  if (!e || !n_out) return fail(KWK_EINVAL, "null argument");
-  if (kwk_status st = packed_ok(e)) return st;
-  if (kwk_status st = set_dev(e)) return st;
-  const uint32_t n_waves = e->last_blocks * kWavesPerBlock;
-  if (n_waves == 0) { *n_out = 0; return KWK_OK; }
-  if (!e->compacted || !e->compacted_packed)
-    if (kwk_status st = enqueue_compact(e, 1)) return st;
-  uint32_t total = 0;
-  if (kwk_status st = hb_len(e, &total)) return st;
-  *n_out = total;
-  if (!out || total == 0) return KWK_OK;
-  if (total > cap) return fail(KWK_ECAP, "fired buffer too small: need " + std::to_string(total));
-  HIP_TRY(hipMemcpyAsync(out, e->hb[e->hb_cur].list, sizeof(uint32_t) * total, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  return KWK_OK;
-}
-
-static int compact_mode(uint32_t compact) {
-  return compact == KWK_COMPACT_BITS ? 3 : compact == KWK_COMPACT_PACKED16 ? 2 : compact == KWK_COMPACT_PACKED ? 1 : 0;
-}
-
-kwk_status kwk_fired_compact_bits(kwk_engine* e) {
-  ErrScope es_(e);
-  if (!e) return fail(KWK_EINVAL, "null engine");
-  if (kwk_status st = set_dev(e)) return st;
-  return enqueue_compact(e, 3);
-}
-
-kwk_status kwk_fired_bits(kwk_engine* e, uint32_t* out, uint64_t cap_words, uint64_t* n_words, uint32_t* n_records,
-                          uint32_t* n_segs, uint32_t* region_slots) {
-  ErrScope es_(e);
-  if (!e || !n_words || !n_records || !n_segs || !region_slots) return fail(KWK_EINVAL, "null argument");
-  if (kwk_status st = set_dev(e)) return st;
-  const uint32_t n_waves = e->last_blocks * kWavesPerBlock;
-  *n_segs = n_waves;
-  *region_slots = 64u * e->last_objs << e->last_region_shift;
-  *n_words = 0;
-  *n_records = 0;
-  if (n_waves == 0) return KWK_OK;
-  if (!e->compacted || !e->compacted_bits) {
-    if (e->last_rec != kRecId8Half)
-      return fail(KWK_ESTATE, "the bitmap hand-back is the 1-byte sweep's with at most 4 stages: use kwk_fired_packed");
-    if (kwk_status st = enqueue_compact(e, 3)) return st;
-  }
-  uint32_t t[2] = {0, 0};
-  if (kwk_status st = hb_len(e, t)) return st;
-  *n_words = t[0];
-  *n_records = t[1];
-  if (!out) return KWK_OK;
-  if (t[0] > cap_words) return fail(KWK_ECAP, "fired buffer too small: need " + std::to_string(t[0]) + " words");
-  HIP_TRY(hipMemcpyAsync(out, e->hb[e->hb_cur].list, sizeof(uint32_t) * (size_t)t[0], hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  return KWK_OK;
-}
-
-kwk_status kwk_fired_compact_packed16(kwk_engine* e) {
-  ErrScope es_(e);
-  if (!e) return fail(KWK_EINVAL, "null engine");
-  if (kwk_status st = set_dev(e)) return st;
-  return enqueue_compact(e, 2);
-}
-
-kwk_status kwk_fired_packed16(kwk_engine* e, uint16_t* out, uint32_t cap, uint32_t* n_out, uint32_t* seg_counts,
-                              uint32_t seg_cap, uint32_t* n_segs, uint32_t* region_slots) {
-  ErrScope es_(e);
-  if (!e || !n_out || !n_segs || !region_slots) return fail(KWK_EINVAL, "null argument");
-  if (kwk_status st = set_dev(e)) return st;
-  const uint32_t n_waves = e->last_blocks * kWavesPerBlock;
-  *n_segs = n_waves;
-  *region_slots = 64u * e->last_objs << e->last_region_shift;
-  if (n_waves == 0) { *n_out = 0; return KWK_OK; }
-  if (!e->compacted || !e->compacted_16) {
-    if (e->last_rec != kRecId8Half)
-      return fail(KWK_ESTATE, "2-byte records are the 1-byte sweep's with at most 4 stages: use kwk_fired_packed");
-    if (kwk_status st = enqueue_compact(e, 2)) return st;
-  }
-  uint32_t total = 0;
-  if (kwk_status st = hb_len(e, &total)) return st;
-  *n_out = total;
-  if (!out && !seg_counts) return KWK_OK;
-  if (out && total > cap) return fail(KWK_ECAP, "fired buffer too small: need " + std::to_string(total));
-  if (seg_counts && n_waves > seg_cap) return fail(KWK_ECAP, "segment buffer too small: need " + std::to_string(n_waves));
-  const kwk_engine::HbSlot& h = e->hb[e->hb_cur];
-  if (out && total) HIP_TRY(hipMemcpyAsync(out, h.list, sizeof(uint16_t) * total, hipMemcpyDeviceToHost, e->stream));
-  if (seg_counts)
-    HIP_TRY(hipMemcpyAsync(seg_counts, h.counts, sizeof(uint32_t) * n_waves, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
   return KWK_OK;
 }
 
@@ -6157,12 +6065,14 @@ kwk_status kwk_fired_packed16(kwk_engine* e, uint16_t* out, uint32_t cap, uint32
 // 78.4-78.7 us per C5 step, the persistent sweep holding the CUs the two latency-bound launches
 // then wait for; r5p / r5r.  Round 5's folded hand-back — the next sweep copying a step's 2-byte
 // list — is superseded by fused steps at the shard size and was removed in round 6.)
-// the sweep of one step and its hand-back in `mode` (< 0: none) into the next ring slot — inside
+// the sweep of one step and, with `compact`, its hand-back in `mode` into the next ring slot — inside
 // the sweep (tail_handback) when it is a one-tile-per-block 2-byte table-only sweep, else by
 // enqueue_compact.  ev_a >= 0: events ev_a, ev_a + 1 bracket the sweep launch
-static kwk_status sweep_compact(kwk_engine* e, int64_t now, uint64_t seed, uint64_t step, int mode, int ev_a = -1) {
-  TailReq tr{0u, mode == 0 ? 0 : 1, false};  // a 2-byte sweep's records: the 2-byte / bitmap modes fall to packed
-  const bool try_tail = mode >= 0 && e->tail_hb && e->fmt.half && !e->fmt.byte && e->loaded_table;
+static kwk_status sweep_compact(kwk_engine* e, int64_t now, uint64_t seed, uint64_t step, bool compact, HbFmt mode,
+                                int ev_a = -1) {
+  // a 2-byte sweep's records: the 2-byte / bitmap modes fall to packed
+  TailReq tr{0u, mode == HbFmt::Rec ? HbFmt::Rec : HbFmt::Packed, false};
+  const bool try_tail = compact && e->tail_hb && e->fmt.half && !e->fmt.byte && e->loaded_table;
   if (try_tail) {
     tr.slot = hb_next(e);
     if (kwk_status st = hb_prepare(e, tr.slot, tr.mode, e->stream)) return st;
@@ -6172,20 +6082,15 @@ static kwk_status sweep_compact(kwk_engine* e, int64_t now, uint64_t seed, uint6
   if (kwk_status st = launch_sweep(e, now, seed, step, true, 1, 0, try_tail ? &tr : nullptr)) return st;
   if (ev_a >= 0)
     if (kwk_status st = kwk_event_record(e, (uint32_t)ev_a + 1u)) return st;
-  if (mode < 0) return KWK_OK;
-  if (tr.done) {
-    e->compacted = true;
-    e->compacted_packed = tr.mode == 1;
-    e->compacted_16 = false;
-    e->compacted_bits = false;
+  if (!compact) return KWK_OK;
+  if (tr.done)
     return hb_commit(e, tr.slot, e->last_step_no, tr.mode, e->last_blocks * kWavesPerBlock, (int)tr.slot, e->stream,
                      true);
-  }
   return enqueue_compact(e, mode);
 }
 
 static kwk_status step_one(kwk_engine* e, int64_t now, uint64_t seed, uint64_t step, uint32_t compact, int ev_a = -1) {
-  return sweep_compact(e, now, seed, step, compact ? compact_mode(compact) : -1, ev_a);
+  return sweep_compact(e, now, seed, step, compact != 0, hb_fmt_of_compact(compact), ev_a);
 }
 
 // several steps in one sweep launch (KWK_TUNE_FUSE_STEPS): a 1-byte engine whose table writes no
@@ -6204,7 +6109,7 @@ static uint32_t fuse_group(const kwk_engine* e, uint32_t left, uint32_t ev_every
 
 // steps k .. k + m - 1 of kwk_step_n / _pair (now, now + dt, ...) in one launch, then every step's
 // hand-back into a ring slot of its own (the next m slots, in step order, so each step's list stays
-// readable by kwk_fired_fetch_step): step 0's segments in d_fired, step s's in d_firedx[s - 1],
+// readable by kwk_fired_fetch): step 0's segments in d_fired, step s's in d_firedx[s - 1],
 // rotated so that the last step's stay in d_fired / d_wave_counts (the engine's last step); ev_a
 // brackets the launch (the sample of whichever step it is)
 static kwk_status step_group(kwk_engine* e, uint32_t m, int64_t now, int64_t dt, uint64_t seed, uint64_t step,
@@ -6227,12 +6132,12 @@ static kwk_status step_group(kwk_engine* e, uint32_t m, int64_t now, int64_t dt,
     // segments), blockIdx.y = the step, step i's list into ring slot hb_next(i + 1)
     CompactArgs4 c4;
     for (uint32_t i = 0; i < m; ++i)
-      if (kwk_status st = hb_prepare(e, hb_next(e, i + 1), 2, e->stream)) return st;
+      if (kwk_status st = hb_prepare(e, hb_next(e, i + 1), HbFmt::Packed16, e->stream)) return st;
     for (uint32_t i = 0; i < m; ++i) {
       CompactArgs& a = c4.a[i];
       a.fired32 = reinterpret_cast<const uint32_t*>(i ? e->d_firedx[i - 1] : e->d_fired);
       a.counts = i ? e->d_countsx[i - 1] : e->d_wave_counts;
-      hb_args(e, hb_next(e, i + 1), 2, a);
+      hb_args(e, hb_next(e, i + 1), HbFmt::Packed16, a);
     }
     const uint32_t blocks = (n_waves + kSegsPerBlock - 1) / kSegsPerBlock;
     if (n_waves <= e->compact_small) {
@@ -6253,12 +6158,9 @@ static kwk_status step_group(kwk_engine* e, uint32_t m, int64_t now, int64_t dt,
     const uint32_t last = hb_next(e, m);
     for (uint32_t i = 0; i < m; ++i) {
       const uint32_t slot = hb_next(e, 1);  // hb_commit advances hb_cur: slots in step order
-      if (kwk_status st = hb_commit(e, slot, step + i, 2, n_waves, (int)last, e->stream, i + 1 == m)) return st;
+      if (kwk_status st = hb_commit(e, slot, step + i, HbFmt::Packed16, n_waves, (int)last, e->stream, i + 1 == m))
+        return st;
     }
-    e->compacted = true;
-    e->compacted_packed = false;
-    e->compacted_16 = true;
-    e->compacted_bits = false;
     return KWK_OK;
   }
   for (uint32_t i = 0; i < m; ++i) {
@@ -6269,7 +6171,7 @@ static kwk_status step_group(kwk_engine* e, uint32_t m, int64_t now, int64_t dt,
     }
     if (compact) {
       e->last_step_no = step + i;  // the tag of this step's list
-      if (kwk_status st = enqueue_compact(e, compact_mode(compact))) return st;
+      if (kwk_status st = enqueue_compact(e, hb_fmt_of_compact(compact))) return st;
     }
   }
   e->last_step_no = step + m - 1;
@@ -6339,34 +6241,6 @@ kwk_status kwk_step_n_pair(kwk_engine* e, kwk_engine* other, uint32_t n, int64_t
   return KWK_OK;
 }
 
-kwk_status kwk_fired_device(kwk_engine* e, const kwk_fired_rec** recs, const uint32_t** count) {
-  ErrScope es_(e);
-  if (!e || !recs || !count) return fail(KWK_EINVAL, "null argument");
-  if (!e->compacted || e->compacted_packed || e->compacted_16 || e->compacted_bits)
-    return fail(KWK_ESTATE, "kwk_fired_compact must follow kwk_step");
-  *recs = reinterpret_cast<const kwk_fired_rec*>(e->hb[e->hb_cur].list);
-  *count = e->hb[e->hb_cur].offsets;
-  return KWK_OK;
-}
-
-kwk_status kwk_fired(kwk_engine* e, kwk_fired_rec* out, uint32_t cap, uint32_t* n_out) {
-  ErrScope es_(e);
-  if (!e || !n_out) return fail(KWK_EINVAL, "null argument");
-  if (kwk_status st = set_dev(e)) return st;
-  const uint32_t n_waves = e->last_blocks * kWavesPerBlock;
-  if (n_waves == 0) { *n_out = 0; return KWK_OK; }
-  if (!e->compacted || e->compacted_packed || e->compacted_16 || e->compacted_bits)  // the segments are intact: expand them
-    if (kwk_status st = enqueue_compact(e)) return st;
-  uint32_t total = 0;
-  if (kwk_status st = hb_len(e, &total)) return st;
-  *n_out = total;
-  if (!out || total == 0) return KWK_OK;
-  if (total > cap) return fail(KWK_ECAP, "fired buffer too small: need " + std::to_string(total));
-  HIP_TRY(hipMemcpyAsync(out, e->hb[e->hb_cur].list, sizeof(kwk_fired_rec) * total, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  return KWK_OK;
-}
-
 kwk_status kwk_fired_keep(kwk_engine* e, uint32_t depth) {
   ErrScope es_(e);
   if (!e) return fail(KWK_EINVAL, "null engine");
@@ -6392,7 +6266,7 @@ kwk_status kwk_fired_keep(kwk_engine* e, uint32_t depth) {
   e->hb[0].done_slot = 0;
   if (e->hb_track && e->hb[0].offsets) {  // the current list's length where a fetch reads it
     if (!e->hb[0].ev_done) HIP_TRY(hipEventCreateWithFlags(&e->hb[0].ev_done, hipEventDisableTiming));
-    const bool bits = e->hb[0].mode == 3;
+    const bool bits = e->hb[0].mode == HbFmt::Bits;
     e->h_len[1] = 0u;
     HIP_TRY(hipMemcpy(e->h_len, bits ? e->hb[0].tot : e->hb[0].offsets, (bits ? 2 : 1) * sizeof(uint32_t),
                       hipMemcpyDeviceToHost));
@@ -6401,7 +6275,7 @@ kwk_status kwk_fired_keep(kwk_engine* e, uint32_t depth) {
   return KWK_OK;
 }
 
-// slot i's list to host memory on the copy stream (kwk_fired_fetch_async / _step)
+// slot i's list to host memory on the copy stream (kwk_fired_fetch)
 static kwk_status hb_fetch(kwk_engine* e, uint32_t i, void* out, uint64_t cap_bytes, uint32_t* seg_counts,
                            uint32_t seg_cap, kwk_fetch_info* info) {
   kwk_engine::HbSlot& h = e->hb[i];
@@ -6413,8 +6287,8 @@ static kwk_status hb_fetch(kwk_engine* e, uint32_t i, void* out, uint64_t cap_by
     HIP_TRY(hipHostMalloc((void**)&e->h_count, 64, hipHostMallocDefault));
   }
   if (!h.ev_copied) HIP_TRY(hipEventCreateWithFlags(&h.ev_copied, hipEventDisableTiming));
-  const bool bits = h.mode == 3, b16 = h.mode == 2;
-  const uint32_t rb = bits ? 4u : b16 ? 2u : h.mode == 1 ? 4u : (uint32_t)sizeof(kwk_fired_rec);
+  const bool bits = h.mode == HbFmt::Bits, b16 = h.mode == HbFmt::Packed16;
+  const uint32_t rb = hb_record_bytes(h.mode);
   const bool segs = b16 && seg_counts && h.n_segs;
   if (segs && h.n_segs > seg_cap) return fail(KWK_ECAP, "segment buffer too small: need " + std::to_string(h.n_segs));
   uint32_t t[2] = {0u, 0u};
@@ -6438,7 +6312,7 @@ static kwk_status hb_fetch(kwk_engine* e, uint32_t i, void* out, uint64_t cap_by
   const uint32_t total = t[0];  // records, or the bitmap hand-back's 32-bit words
   info->n_records = bits ? t[1] : total;
   info->record_bytes = bits ? 0u : rb;
-  info->format = bits ? KWK_COMPACT_BITS : b16 ? KWK_COMPACT_PACKED16 : h.mode == 1 ? KWK_COMPACT_PACKED : 1u;
+  info->format = hb_code(h.mode);
   info->bytes = (uint64_t)total * rb;
   info->step = h.step;
   if (b16 || bits) {
@@ -6457,25 +6331,90 @@ static kwk_status hb_fetch(kwk_engine* e, uint32_t i, void* out, uint64_t cap_by
   return KWK_OK;
 }
 
-kwk_status kwk_fired_fetch_async(kwk_engine* e, void* out, uint64_t cap_bytes, uint32_t* seg_counts, uint32_t seg_cap,
-                                 kwk_fetch_info* info) {
-  ErrScope es_(e);
-  if (!e || !info) return fail(KWK_EINVAL, "null argument");
-  if (kwk_status st = set_dev(e)) return st;
-  memset(info, 0, sizeof(*info));
-  const uint32_t n_waves = e->last_blocks * kWavesPerBlock;
-  if (n_waves == 0) return KWK_OK;
-  if (!e->compacted) return fail(KWK_ESTATE, "kwk_fired_fetch_async needs the step's list compacted (kwk_fired_compact*)");
-  return hb_fetch(e, e->hb_cur, out, cap_bytes, seg_counts, seg_cap, info);
+// the shared prologue of the entry points that take a format: the engine, the format's code, the
+// 27-bit slots of the packed records, the device
+static kwk_status fired_prologue(kwk_engine* e, uint32_t format, HbFmt* f) {
+  if (!hb_fmt_of(format, f)) return fail(KWK_EINVAL, "format: KWK_COMPACT_REC, _PACKED, _PACKED16 or _BITS");
+  if (*f == HbFmt::Packed)
+    if (kwk_status st = packed_ok(e)) return st;
+  return set_dev(e);
 }
 
-kwk_status kwk_fired_fetch_step(kwk_engine* e, uint64_t step, void* out, uint64_t cap_bytes, uint32_t* seg_counts,
-                                uint32_t seg_cap, kwk_fetch_info* info) {
+kwk_status kwk_fired_compact(kwk_engine* e, uint32_t format) {
+  ErrScope es_(e);
+  if (!e) return fail(KWK_EINVAL, "null engine");
+  HbFmt f;
+  if (kwk_status st = fired_prologue(e, format, &f)) return st;
+  return enqueue_compact(e, f);
+}
+
+kwk_status kwk_fired_device(kwk_engine* e, uint32_t format, const void** list, const uint32_t** count) {
+  ErrScope es_(e);
+  if (!e || !list || !count) return fail(KWK_EINVAL, "null argument");
+  HbFmt f;
+  if (!hb_fmt_of(format, &f)) return fail(KWK_EINVAL, "format: KWK_COMPACT_REC, _PACKED, _PACKED16 or _BITS");
+  if (!e->compacted || current_fmt(e) != f)
+    return fail(KWK_ESTATE, "kwk_fired_compact in this format must follow kwk_step");
+  *list = e->hb[e->hb_cur].list;
+  *count = f == HbFmt::Bits ? e->hb[e->hb_cur].tot : e->hb[e->hb_cur].offsets;
+  return KWK_OK;
+}
+
+kwk_status kwk_fired_read(kwk_engine* e, uint32_t format, void* out, uint64_t cap_bytes, uint32_t* seg_counts,
+                          uint32_t seg_cap, kwk_fetch_info* info) {
+  ErrScope es_(e);
+  if (!e || !info) return fail(KWK_EINVAL, "null argument");
+  HbFmt f;
+  if (kwk_status st = fired_prologue(e, format, &f)) return st;
+  const bool bits = f == HbFmt::Bits;
+  const uint32_t rb = hb_record_bytes(f);
+  const uint32_t n_waves = e->last_blocks * kWavesPerBlock;
+  memset(info, 0, sizeof(*info));
+  info->format = format;
+  info->record_bytes = bits ? 0u : rb;
+  info->step = e->last_step_no;
+  if (hb_segmented(f)) {
+    info->n_segs = n_waves;
+    info->region_slots = 64u * e->last_objs << e->last_region_shift;
+  }
+  if (n_waves == 0) return KWK_OK;  // nothing swept: an empty list
+  if (!e->compacted || current_fmt(e) != f) {  // the segments are intact: compact them in this format
+    if (hb_segmented(f) && e->last_rec != kRecId8Half)
+      return fail(KWK_ESTATE, std::string(bits ? "the bitmap hand-back is" : "2-byte records are") +
+                                  " the 1-byte sweep's with at most 4 stages: use KWK_COMPACT_PACKED");
+    if (kwk_status st = enqueue_compact(e, f)) return st;
+  }
+  const kwk_engine::HbSlot& h = e->hb[e->hb_cur];
+  uint32_t t[2] = {0u, 0u};  // the length: records, or the bitmap hand-back's {words, records}
+  HIP_TRY(hipMemcpyAsync(t, bits ? h.tot : h.offsets, (bits ? 2 : 1) * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                         e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  const uint32_t total = t[0];
+  info->n_records = bits ? t[1] : total;
+  info->bytes = (uint64_t)total * rb;
+  const bool segs = f == HbFmt::Packed16 && seg_counts;
+  if (!out && !segs) return KWK_OK;  // sizes only
+  if (out && info->bytes > cap_bytes)
+    return fail(KWK_ECAP, "fired buffer too small: need " + std::to_string(total) + (bits ? " words" : ""));
+  if (segs && n_waves > seg_cap) return fail(KWK_ECAP, "segment buffer too small: need " + std::to_string(n_waves));
+  if (out && total) HIP_TRY(hipMemcpyAsync(out, h.list, (size_t)total * rb, hipMemcpyDeviceToHost, e->stream));
+  if (segs) HIP_TRY(hipMemcpyAsync(seg_counts, h.counts, sizeof(uint32_t) * n_waves, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return KWK_OK;
+}
+
+kwk_status kwk_fired_fetch(kwk_engine* e, uint64_t step, void* out, uint64_t cap_bytes, uint32_t* seg_counts,
+                           uint32_t seg_cap, kwk_fetch_info* info) {
   ErrScope es_(e);
   if (!e || !info) return fail(KWK_EINVAL, "null argument");
   if (kwk_status st = set_dev(e)) return st;
   memset(info, 0, sizeof(*info));
   const uint32_t n = (uint32_t)e->hb.size();
+  if (step == KWK_STEP_LAST) {  // the engine's last list
+    if (e->last_blocks == 0) return KWK_OK;  // nothing swept
+    if (!e->compacted) return fail(KWK_ESTATE, "kwk_fired_fetch needs the step's list compacted (kwk_fired_compact)");
+    return hb_fetch(e, e->hb_cur, out, cap_bytes, seg_counts, seg_cap, info);
+  }
   for (uint32_t k = 0; k < n; ++k) {  // newest first
     const uint32_t i = (e->hb_cur + n - k) % n;
     if (e->hb[i].valid && e->hb[i].step == step) return hb_fetch(e, i, out, cap_bytes, seg_counts, seg_cap, info);
@@ -7569,9 +7508,9 @@ static kwk_status enqueue_tick(kwk_engine* nodes, kwk_engine* pods, int64_t now_
     HIP_TRY(hipEventRecord(pods->ev_podsync, pods->stream));
     pods->tick_pending = true;
   }
-  if (kwk_status st = sweep_compact(nodes, now_ns, seed, step, compact ? (packed ? 1 : 0) : -1)) return st;
+  if (kwk_status st = sweep_compact(nodes, now_ns, seed, step, compact, packed ? HbFmt::Packed : HbFmt::Rec)) return st;
   if (pods)
-    if (kwk_status st = sweep_compact(pods, now_ns, seed, step, compact ? (packed ? 1 : 0) : -1)) return st;
+    if (kwk_status st = sweep_compact(pods, now_ns, seed, step, compact, packed ? HbFmt::Packed : HbFmt::Rec)) return st;
   return KWK_OK;
 }
 

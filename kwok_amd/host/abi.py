@@ -77,7 +77,7 @@ class StepStats(C.Structure):
 
 
 class FetchInfo(C.Structure):
-    """kwk_fetch_info (kwk_fired_fetch_async / kwk_fired_fetch_step)."""
+    """kwk_fetch_info (kwk_fired_read / kwk_fired_fetch)."""
     _fields_ = [("n_records", C.c_uint32), ("record_bytes", C.c_uint32), ("n_segs", C.c_uint32),
                 ("region_slots", C.c_uint32), ("format", C.c_uint32), ("reserved", C.c_uint32), ("bytes", C.c_uint64),
                 ("step", C.c_uint64)]
@@ -178,7 +178,7 @@ assert HOT_DTYPE.itemsize == 16 and VALUE_DTYPE.itemsize == 16 and FIRED_DTYPE.i
 # every symbol include/kwok_engine.h declares (checked by the CPU test suite)
 EXPORTS = [
     "kwk_last_error", "kwk_engine_create", "kwk_engine_destroy", "kwk_load_stages", "kwk_set_harness", "kwk_load",
-    "kwk_upsert", "kwk_set_records", "kwk_delete", "kwk_step", "kwk_match", "kwk_fired", "kwk_stats", "kwk_read", "kwk_sync",
+    "kwk_upsert", "kwk_set_records", "kwk_delete", "kwk_step", "kwk_match", "kwk_fired_read", "kwk_stats", "kwk_read", "kwk_sync",
     "kwk_usage_config", "kwk_usage", "kwk_usage_read", "kwk_device_ptrs", "kwk_event_record", "kwk_event_elapsed", "kwk_stream", "kwk_step_n", "kwk_step_n_pair",
     "kwk_abi_version", "kwk_tile_objects", "kwk_count", "kwk_lease_config", "kwk_lease_set", "kwk_lease_step",
     "kwk_lease_ops", "kwk_lease_read", "kwk_lease_stats", "kwk_lease_sync_pods", "kwk_usage_pods",
@@ -186,17 +186,18 @@ EXPORTS = [
     "kwk_alloc_host", "kwk_free_host", "kwk_replace", "kwk_usage_mixed", "kwk_usage_read_containers",
     "kwk_metrics_load", "kwk_metrics_inputs", "kwk_metrics_eval", "kwk_aggregate", "kwk_aggregate_read",
     "kwk_last_sweep", "kwk_tick_bind", "kwk_tick", "kwk_tick_n", "kwk_histograms_load", "kwk_histograms_eval",
-    "kwk_fired_compact_packed", "kwk_fired_packed", "kwk_fired_packed_device", "kwk_fired_compact_packed16",
-    "kwk_fired_packed16", "kwk_fired_fetch_async", "kwk_fired_fetch_wait",
-    "kwk_fired_compact_bits", "kwk_fired_bits", "kwk_fired_keep", "kwk_fired_fetch_step",
+    "kwk_fired_fetch", "kwk_fired_fetch_wait", "kwk_fired_keep",
     "kwk_metrics_eval_device", "kwk_histograms_eval_device",
 ]
-ABI_VERSION = 2  # KWK_ABI_VERSION of include/kwok_engine.h: the library must match the structs above
+ABI_VERSION = 3  # KWK_ABI_VERSION of include/kwok_engine.h: the library must match the structs above
 TICK_COMPACT = 1 << 0  # KWK_TICK_COMPACT
 TICK_COMPACT_PACKED = 1 << 1  # KWK_TICK_COMPACT_PACKED
-COMPACT_PACKED = 2  # kwk_step_n compact = KWK_COMPACT_PACKED
-COMPACT_PACKED16 = 3  # kwk_step_n compact = KWK_COMPACT_PACKED16 (2-byte records where the sweep has them)
-COMPACT_BITS = 4  # kwk_step_n compact = KWK_COMPACT_BITS (per-segment fired maps + 2-bit stage codes, same engines)
+# KWK_COMPACT_*: a hand-back format (kwk_step_n's compact, kwk_fetch_info.format, kwk_fired_compact / _read / _device)
+COMPACT_REC = 1  # kwk_fired_rec
+COMPACT_PACKED = 2  # 4-byte packed records
+COMPACT_PACKED16 = 3  # 2-byte records where the sweep has them
+COMPACT_BITS = 4  # per-segment fired maps + 2-bit stage codes, same engines
+STEP_LAST = (1 << 64) - 1  # KWK_STEP_LAST: kwk_fired_fetch of the engine's last list
 AGG_USAGE = 1 << 0  # KWK_AGG_USAGE
 
 _lib = None
@@ -247,27 +248,16 @@ def lib():
                             C.c_void_p, C.c_void_p, C.c_void_p, _p(Backoff)]
     L.kwk_step.argtypes = [C.c_void_p, C.c_int64, C.c_uint64, C.c_uint64]
     L.kwk_match.argtypes = [C.c_void_p, C.c_int64, C.c_uint64, C.c_uint64]
-    L.kwk_fired.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, _p(C.c_uint32)]
-    L.kwk_fired_compact.argtypes = [C.c_void_p]
+    L.kwk_fired_compact.argtypes = [C.c_void_p, C.c_uint32]
+    L.kwk_fired_read.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, _p(FetchInfo)]
+    L.kwk_fired_device.argtypes = [C.c_void_p, C.c_uint32, _p(C.c_void_p), _p(C.c_void_p)]
+    L.kwk_fired_keep.argtypes = [C.c_void_p, C.c_uint32]
+    L.kwk_fired_fetch.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, _p(FetchInfo)]
+    L.kwk_fired_fetch_wait.argtypes = [C.c_void_p]
     L.kwk_step_n.argtypes = [C.c_void_p, C.c_uint32, C.c_int64, C.c_int64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32,
                              C.c_uint32]
     L.kwk_step_n_pair.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int64, C.c_int64, C.c_uint64, C.c_uint64,
                                   C.c_uint32, C.c_uint32, C.c_uint32]
-    L.kwk_fired_device.argtypes = [C.c_void_p, _p(C.c_void_p), _p(C.c_void_p)]
-    L.kwk_fired_compact_packed.argtypes = [C.c_void_p]
-    L.kwk_fired_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, _p(C.c_uint32)]
-    L.kwk_fired_compact_packed16.argtypes = [C.c_void_p]
-    L.kwk_fired_packed16.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, _p(C.c_uint32), C.c_void_p, C.c_uint32,
-                                     _p(C.c_uint32), _p(C.c_uint32)]
-    L.kwk_fired_packed_device.argtypes = [C.c_void_p, _p(C.c_void_p), _p(C.c_void_p)]
-    L.kwk_fired_fetch_async.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, _p(FetchInfo)]
-    L.kwk_fired_fetch_wait.argtypes = [C.c_void_p]
-    L.kwk_fired_compact_bits.argtypes = [C.c_void_p]
-    L.kwk_fired_bits.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, _p(C.c_uint64), _p(C.c_uint32), _p(C.c_uint32),
-                                 _p(C.c_uint32)]
-    L.kwk_fired_keep.argtypes = [C.c_void_p, C.c_uint32]
-    L.kwk_fired_fetch_step.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32,
-                                       _p(FetchInfo)]
     L.kwk_alloc_host.argtypes = [C.c_uint64, _p(C.c_void_p)]
     L.kwk_free_host.argtypes = [C.c_void_p]
     L.kwk_set_tuning.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
@@ -334,7 +324,7 @@ def bits_slot(i: np.ndarray) -> np.ndarray:
 
 
 def bits_decode(words: np.ndarray, n_segs: int, region_slots: int):
-    """(slot, stage) arrays of a kwk_fired_bits list (KWK_COMPACT_BITS in kwok_engine.h): per segment
+    """(slot, stage) arrays of a KWK_COMPACT_BITS list (kwok_engine.h): per segment
     {records c, nonzero map bytes z} up front, then its 8 summary words, its z nonzero map bytes
     and its c stage codes at the running offset."""
     words = np.asarray(words, dtype=np.uint32)
@@ -365,7 +355,7 @@ def bits_decode(words: np.ndarray, n_segs: int, region_slots: int):
 
 
 def fired16_decode(recs: np.ndarray, seg_counts: np.ndarray, region_slots: int):
-    """(slot, stage, flags) arrays of a kwk_fired_packed16 list (KWK_FIRED16_* in kwok_engine.h)."""
+    """(slot, stage, flags) arrays of a KWK_COMPACT_PACKED16 list (KWK_FIRED16_* in kwok_engine.h)."""
     r = recs.astype(np.uint32)
     x = r & np.uint32(0x7FF)
     jj = x >> np.uint32(8)

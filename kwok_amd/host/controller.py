@@ -124,7 +124,7 @@ class KindController:
         return fired
 
     def handle(self, fired, now_ns: int):
-        """The hand-back of one step's fired list (kwk_fired records): patches applied to the
+        """The hand-back of one step's fired list (kwk_fired_rec records): patches applied to the
         cache, the DELTA_UNKNOWN rows written back."""
         slots, rows = [], []
         if self.native:

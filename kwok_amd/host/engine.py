@@ -139,7 +139,7 @@ def _compact_code(compact) -> int:
         return abi.COMPACT_BITS
     if compact == "packed":
         return abi.COMPACT_PACKED
-    return 1 if compact else 0
+    return abi.COMPACT_REC if compact else 0
 
 
 class Engine:
@@ -263,42 +263,49 @@ class Engine:
                     "kwk_step_n_pair")
 
     def fired_compact(self, packed=False):
-        """kwk_fired_compact (/ _packed, packed = True; / _packed16, packed = "16"): the last step's fired
-        list compacted on the device (enqueue only)."""
-        if packed == "16":
-            self._check(abi.lib().kwk_fired_compact_packed16(self.h), "kwk_fired_compact_packed16")
-        elif packed == "bits":
-            self._check(abi.lib().kwk_fired_compact_bits(self.h), "kwk_fired_compact_bits")
-        elif packed:
-            self._check(abi.lib().kwk_fired_compact_packed(self.h), "kwk_fired_compact_packed")
-        else:
-            self._check(abi.lib().kwk_fired_compact(self.h), "kwk_fired_compact")
+        """kwk_fired_compact: the last step's fired list compacted on the device (enqueue only) as
+        kwk_fired_rec (packed = False), 4-byte records (True), 2-byte records ("16") or maps ("bits")."""
+        fmt = {"16": abi.COMPACT_PACKED16, "bits": abi.COMPACT_BITS}.get(packed) or \
+            (abi.COMPACT_PACKED if packed else abi.COMPACT_REC)
+        self._check(abi.lib().kwk_fired_compact(self.h, fmt), "kwk_fired_compact")
+
+    def _read(self, fmt: int, dtype, pinned: Optional["PinnedBuffer"] = None,
+              pinned_counts: Optional["PinnedBuffer"] = None):
+        """kwk_fired_read in two calls (the sizes, then the copy): the last step's list in format `fmt`
+        as an array of `dtype`, the records per segment (KWK_COMPACT_PACKED16) and the kwk_fetch_info.
+        With PinnedBuffers the copies land in page-locked memory and the arrays are views of it."""
+        L, info = abi.lib(), abi.FetchInfo()
+        self._check(L.kwk_fired_read(self.h, fmt, None, 0, None, 0, C.byref(info)), "kwk_fired_read")
+        n = info.bytes // np.dtype(dtype).itemsize
+        ns = info.n_segs if fmt == abi.COMPACT_PACKED16 else 0
+        out = pinned.array(dtype, n) if pinned is not None else np.zeros(n, dtype=dtype)
+        cnt = pinned_counts.array(np.uint32, ns) if pinned_counts is not None else np.zeros(ns, dtype=np.uint32)
+        if n or ns:
+            self._check(L.kwk_fired_read(self.h, fmt, abi.ptr(out) if n else None, out.nbytes,
+                                         abi.ptr(cnt) if ns else None, ns, C.byref(info)), "kwk_fired_read")
+        return out, cnt, info
+
+    def fired(self, pinned: Optional["PinnedBuffer"] = None) -> np.ndarray:
+        """The last step's fired records (kwk_fired_rec; KWK_COMPACT_REC)."""
+        return self._read(abi.COMPACT_REC, abi.FIRED_DTYPE, pinned)[0]
 
     def fired_packed(self, pinned: Optional["PinnedBuffer"] = None) -> np.ndarray:
-        """The last step's fired list as packed u32 records (kwk_fired_packed): stage = r >> 27,
+        """The last step's list as packed u32 records (KWK_COMPACT_PACKED): stage = r >> 27,
         slot = r & (2**27 - 1)."""
-        n = C.c_uint32()
-        L = abi.lib()
-        self._check(L.kwk_fired_packed(self.h, None, 0, C.byref(n)), "kwk_fired_packed")
-        out = pinned.array(np.uint32, n.value) if pinned is not None else np.zeros(n.value, dtype=np.uint32)
-        if n.value:
-            self._check(L.kwk_fired_packed(self.h, abi.ptr(out), n.value, C.byref(n)), "kwk_fired_packed")
-        return out
+        return self._read(abi.COMPACT_PACKED, np.uint32, pinned)[0]
 
-    def fetch_async(self, out: "PinnedBuffer", counts: Optional["PinnedBuffer"] = None) -> dict:
-        """kwk_fired_fetch_async: the last step's compacted list (and, for 2-byte records, the records per
-        segment) copied into `out` / `counts` on the engine's copy stream; returns the list's shape
-        at once ({n_records, record_bytes, n_segs, region_slots}).  The buffers hold the copy after
-        fetch_wait() (or the next fetch)."""
-        info = abi.FetchInfo()
-        self._check(abi.lib().kwk_fired_fetch_async(self.h, out.p, out.nbytes, counts.p if counts is not None else None,
-                                                   counts.nbytes // 4 if counts is not None else 0, C.byref(info)),
-                    "kwk_fired_fetch_async")
-        return {k: getattr(info, k) for k, _ in abi.FetchInfo._fields_}
+    def fired_packed16(self, pinned=None):
+        """The last step's list as 2-byte records (KWK_COMPACT_PACKED16) -> (records u16, records per
+        segment u32, region_slots); abi.EngineError (KWK_ESTATE) when the sweep has no 2-byte records.
+        pinned: (PinnedBuffer for the records, PinnedBuffer for the counts)."""
+        out, cnt, info = self._read(abi.COMPACT_PACKED16, np.uint16, *(pinned or (None, None)))
+        return out, cnt, int(info.region_slots)
 
-    def fetch_wait(self):
-        """kwk_fired_fetch_wait: the last fetch's copies are in the host buffers."""
-        self._check(abi.lib().kwk_fired_fetch_wait(self.h), "kwk_fired_fetch_wait")
+    def fired_bits(self):
+        """The last step's list as per-segment fired maps + 2-bit stage codes (KWK_COMPACT_BITS) ->
+        (words u32, transitions, segments, region_slots); abi.bits_decode gives (slot, stage)."""
+        out, _, info = self._read(abi.COMPACT_BITS, np.uint32)
+        return out, info.n_records, info.n_segs, info.region_slots
 
     def fired_keep(self, depth: int):
         """kwk_fired_keep: keep the lists of the last `depth` compactions readable by step
@@ -306,44 +313,23 @@ class Engine:
         self._check(abi.lib().kwk_fired_keep(self.h, depth), "kwk_fired_keep")
 
     def fetch_step(self, step: int, out: "PinnedBuffer", counts: Optional["PinnedBuffer"] = None) -> dict:
-        """kwk_fired_fetch_step: step `step`'s list (any step of a kwk_step_n call still in the ring)
-        copied into `out` / `counts` on the copy stream, as fetch_async; the buffers hold it after
-        fetch_wait()."""
+        """kwk_fired_fetch: step `step`'s list (any step of a kwk_step_n call still in the ring) and,
+        for 2-byte records, the records per segment copied into `out` / `counts` on the engine's copy
+        stream; returns the list's shape at once (the kwk_fetch_info fields).  The buffers hold the
+        copy after fetch_wait() (or the next fetch)."""
         info = abi.FetchInfo()
-        self._check(abi.lib().kwk_fired_fetch_step(self.h, step, out.p, out.nbytes,
-                                                  counts.p if counts is not None else None,
-                                                  counts.nbytes // 4 if counts is not None else 0, C.byref(info)),
-                    "kwk_fired_fetch_step")
+        self._check(abi.lib().kwk_fired_fetch(self.h, step, out.p, out.nbytes, counts.p if counts is not None else None,
+                                              counts.nbytes // 4 if counts is not None else 0, C.byref(info)),
+                    "kwk_fired_fetch")
         return {k: getattr(info, k) for k, _ in abi.FetchInfo._fields_}
 
-    def fired_bits(self):
-        """The last step's list as per-segment fired maps + 2-bit stage codes (kwk_fired_bits) ->
-        (words u32, transitions, segments, region_slots); abi.bits_decode gives (slot, stage)."""
-        nw, nr, ns, rs = C.c_uint64(), C.c_uint32(), C.c_uint32(), C.c_uint32()
-        L = abi.lib()
-        self._check(L.kwk_fired_bits(self.h, None, 0, C.byref(nw), C.byref(nr), C.byref(ns), C.byref(rs)), "kwk_fired_bits")
-        out = np.zeros(nw.value, dtype=np.uint32)
-        if nw.value:
-            self._check(L.kwk_fired_bits(self.h, abi.ptr(out), nw.value, C.byref(nw), C.byref(nr), C.byref(ns), C.byref(rs)),
-                        "kwk_fired_bits")
-        return out, nr.value, ns.value, rs.value
+    def fetch_async(self, out: "PinnedBuffer", counts: Optional["PinnedBuffer"] = None) -> dict:
+        """fetch_step of the engine's last compacted list (KWK_STEP_LAST)."""
+        return self.fetch_step(abi.STEP_LAST, out, counts)
 
-    def fired_packed16(self, pinned=None):
-        """The last step's list as 2-byte records (kwk_fired_packed16) -> (records u16, records per
-        segment u32, region_slots); abi.EngineError (KWK_ESTATE) when the sweep has no 2-byte records.
-        pinned: (PinnedBuffer for the records, PinnedBuffer for the counts)."""
-        n, ns, rs = C.c_uint32(), C.c_uint32(), C.c_uint32()
-        L = abi.lib()
-        self._check(L.kwk_fired_packed16(self.h, None, 0, C.byref(n), None, 0, C.byref(ns), C.byref(rs)),
-                    "kwk_fired_packed16")
-        if pinned is not None:
-            out, cnt = pinned[0].array(np.uint16, n.value), pinned[1].array(np.uint32, ns.value)
-        else:
-            out, cnt = np.zeros(n.value, dtype=np.uint16), np.zeros(ns.value, dtype=np.uint32)
-        self._check(L.kwk_fired_packed16(self.h, abi.ptr(out) if n.value else None, n.value, C.byref(n),
-                                         abi.ptr(cnt) if ns.value else None, ns.value, C.byref(ns), C.byref(rs)),
-                    "kwk_fired_packed16")
-        return out, cnt, int(rs.value)
+    def fetch_wait(self):
+        """kwk_fired_fetch_wait: the last fetch's copies are in the host buffers."""
+        self._check(abi.lib().kwk_fired_fetch_wait(self.h), "kwk_fired_fetch_wait")
 
     def set_tuning(self, key: int, value: int):
         """kwk_set_tuning: an explicit kernel choice (abi.TUNE_*)."""
@@ -361,20 +347,6 @@ class Engine:
 
     def sync(self):
         self._check(abi.lib().kwk_sync(self.h), "kwk_sync")
-
-    def fired(self, pinned: Optional["PinnedBuffer"] = None) -> np.ndarray:
-        """The last step's fired records (kwk_fired).  With `pinned` (a PinnedBuffer) the copy
-        lands in page-locked memory and the returned array is a view of it."""
-        n = C.c_uint32()
-        L = abi.lib()
-        self._check(L.kwk_fired(self.h, None, 0, C.byref(n)), "kwk_fired")
-        if pinned is not None:
-            out = pinned.array(abi.FIRED_DTYPE, n.value)
-        else:
-            out = np.zeros(n.value, dtype=abi.FIRED_DTYPE)
-        if n.value:
-            self._check(L.kwk_fired(self.h, abi.ptr(out), n.value, C.byref(n)), "kwk_fired")
-        return out
 
     def stats(self) -> dict:
         s = abi.StepStats()

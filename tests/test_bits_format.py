@@ -1,7 +1,7 @@
 """The bitmap hand-back's layout (KWK_COMPACT_BITS, include/kwok_engine.h) on the CPU: the header's
 KWK_BITS_SLOT against the 2-byte records' KWK_FIRED16_SLOT of the same id (compiled with gcc), and
 abi.bits_decode on lists laid out as bits_kernel writes them (engine.hip).  The device path itself
-is checked against kwk_fired in tests/test_scale_properties.py (GPU)."""
+is checked against kwk_fired_read in tests/test_scale_properties.py (GPU)."""
 import os
 import subprocess
 

@@ -1,5 +1,5 @@
 """The host libraries in the GPU-checked loop: KindController on its native
-path — the fired hand-back of the engine (kwk_step / kwk_fired) rendered by libkwok_patch
+path — the fired hand-back of the engine (kwk_step / kwk_fired_read) rendered by libkwok_patch
 (kwk_patch_render, the precompiled merge-patch byte templates) and every fired object's new
 state re-encoded by libkwok_encoder (kwk_encode) — stepped beside the oracle.  At every step:
 the fired set equals the oracle's, the host's object cache equals the oracle's objects (so every

@@ -1,6 +1,6 @@
 """Device patch emission on the GPU (include/kwok_emit.h): the native controller loop of
 tests/test_controller_native.py with libkwok_emit beside it.  Every step, kwk_emit expands the
-engine's fired list (kwk_fired records on even steps, 4-byte packed records on odd ones) on the
+engine's fired list (kwk_fired_rec records on even steps, 4-byte packed records on odd ones) on the
 device (each record written by one lane through a 16-byte register window: records sharing a
 16-byte window at both ends of every record, patches of every length); each item it emits equals, byte for byte, the patch the controller rendered for that
 object with kwk_patch_render (itself checked against the oracle's next state there), and each

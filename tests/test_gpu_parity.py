@@ -275,7 +275,7 @@ def test_device_list_empty_after_sweeping_nothing():
 
         def device_count():
             recs, cnt = C.c_void_p(), C.c_void_p()
-            abi.check(L.kwk_fired_device(eng.h, C.byref(recs), C.byref(cnt)), "kwk_fired_device", eng.h)
+            abi.check(L.kwk_fired_device(eng.h, abi.COMPACT_REC, C.byref(recs), C.byref(cnt)), "kwk_fired_device", eng.h)
             eng.sync()
             out = C.c_uint32(0xFFFFFFFF)
             assert hip.hipMemcpy(C.byref(out), cnt, 4, 2) == 0  # hipMemcpyDeviceToHost

@@ -55,6 +55,9 @@ def test_abi_exports_every_header_symbol():
     lib = ctypes.CDLL(abi.LIB_PATH)
     declared = _header_functions()
     assert declared == sorted(abi.EXPORTS)
+    assert [n for n in declared if n.startswith("kwk_fired")] == [
+        "kwk_fired_compact", "kwk_fired_device", "kwk_fired_fetch", "kwk_fired_fetch_wait", "kwk_fired_keep",
+        "kwk_fired_read"]
     for name in declared:
         assert hasattr(lib, name), name
     out = subprocess.run(["nm", "-D", "--defined-only", abi.LIB_PATH], capture_output=True, text=True).stdout

@@ -107,7 +107,7 @@ def test_c5_fused_steps_every_step_sampled_oracle(n):
     steps per launch over the C5 pod shape — 40M pods on the persistent grid, 12.5M (the N = 8
     shard) one tile per workgroup — stepped by kwk_step_n calls of 10 steps (launches of 4 + 4 + 2
     steps, each launch's 2-byte hand-backs in one launch), and EVERY step's list read by step
-    through the hand-back ring (kwk_fired_keep + kwk_fired_fetch_step) and decoded on the host: the
+    through the hand-back ring (kwk_fired_keep + kwk_fired_fetch) and decoded on the host: the
     fired records of every ~9973rd slot must equal `OracleSim` stepped one step at a time, at each
     of the 20 steps; after each call the sampled objects' states equal the oracle's."""
     from bench import shard_pod_variants

@@ -148,13 +148,13 @@ def test_handback_pair_equals_one_launch_at_4m_pods():
 
 @pytest.mark.parametrize("state", ["auto", "u16", "dw"])
 def test_packed_handback_equals_records_at_4m_pods(state):
-    """The packed hand-back (kwk_fired_compact_packed / kwk_fired_packed: 4-byte records, stage in
-    bits 31-27, slot in 26-0) over the same step's segments as the 8-byte list, through both
+    """The packed hand-back (kwk_fired_compact / kwk_fired_read with KWK_COMPACT_PACKED: 4-byte records,
+    stage in bits 31-27, slot in 26-0) over the same step's segments as the 8-byte list, through both
     compaction paths (one launch at <= 8192 segments, the scan + expansion pair above): the same
-    (slot, stage) sequence; kwk_fired after a packed compaction re-expands the full records
+    (slot, stage) sequence; kwk_fired_read(KWK_COMPACT_REC) after a packed compaction re-expands the full records
     (flags included); kwk_step_n with KWK_COMPACT_PACKED leaves the same packed list as the
     per-step calls.  1-byte ids (sweep8), 2-byte words, fused 8-byte records (C2 mix).  The 2-byte
-    hand-back (kwk_fired_packed16) of the 1-byte sweep decodes to the same (slot, stage, flags); the
+    hand-back (KWK_COMPACT_PACKED16) of the 1-byte sweep decodes to the same (slot, stage, flags); the
     other formats refuse it."""
     from kwok_amd.host import abi
     if state == "dw":
@@ -491,10 +491,10 @@ def test_fused_step_n_pair_equals_per_step_calls(compact_small):
 
 
 def test_fetch_async_equals_sync_readback():
-    """kwk_fired_fetch_async (the overlapped host hand-back): each step's list copied on the copy
+    """kwk_fired_fetch(KWK_STEP_LAST) (the overlapped host hand-back): each step's list copied on the copy
     stream while the next step is enqueued and compacted (the compaction waits for the copy on the
-    device), buffers alternating, equals the synchronous kwk_fired_packed16 / kwk_fired_packed /
-    kwk_fired of a twin engine stepped alike — the bitmap hand-back (maps + stage codes), 2-byte
+    device), buffers alternating, equals the synchronous kwk_fired_read (KWK_COMPACT_PACKED16 / _PACKED /
+    _REC) of a twin engine stepped alike — the bitmap hand-back (maps + stage codes), 2-byte
     records with their per-segment counts, 4-byte packed and 8-byte records."""
     from kwok_amd.host import abi
     from kwok_amd.host.engine import PinnedBuffer
@@ -550,13 +550,13 @@ def test_fetch_async_equals_sync_readback():
 def test_fused_call_every_step_list_equals_per_step_calls(n_nodes, mode):
     """Every step's hand-back of a fused kwk_step_n call: 10 steps in one call
     sweep as launches of 4 + 4 + 2 steps, each launch's hand-backs in one launch, and every step's
-    list lands in a ring slot of its own (kwk_fired_keep).  kwk_fired_fetch_step(k) for each of the
+    list lands in a ring slot of its own (kwk_fired_keep).  kwk_fired_fetch(k) for each of the
     10 steps — all fetched before one wait, the copies overlapping the later steps — must equal the
     list of the same step from per-step kwk_step + compaction calls of an unfused twin: the 2-byte
     records with their per-segment counts (25M pods: persistent grid, scan + expansion pair; 2M:
     one-tile grid, one-launch prefix) and the bitmap hand-back (25M).  The lists' transitions add up
     to the fired count (n_host == fired), a step the ring no longer holds is refused, and the
-    call's last list is still the engine's (kwk_fired_packed16)."""
+    call's last list is still the engine's (kwk_fired_read(KWK_COMPACT_PACKED16))."""
     from kwok_amd.host import abi
     from kwok_amd.host.engine import PinnedBuffer
     now0, dt, seed = 1_700_000_000 * 10**9, 10**9, 0x6B776F6B
