@@ -529,6 +529,13 @@ kwk_status kwk_metrics_eval(kwk_engine* pods, int64_t now_ns, uint32_t node_firs
  * writer on the GPU, an all-reduce) and for timing the evaluation without the copy */
 kwk_status kwk_metrics_eval_device(kwk_engine* pods, int64_t now_ns, uint32_t node_first, uint32_t n_nodes,
                                    const double** out, uint64_t* n_out);
+/* what such a consumer needs to walk those values (enqueue only): the engine's device node_ptr
+ * (n_nodes + 1 of kwk_usage_config) and cptr (per pod slot: its first container, pods + 1), and
+ * *alive_bits = a bit per pod slot of the range (bit i of word i / 32: slot node_ptr[node_first] + i
+ * is alive — a dead slot's NaN is not a live series' NaN), written on the engine's stream; valid
+ * until the next call */
+kwk_status kwk_metrics_series_device(kwk_engine* pods, uint32_t node_first, uint32_t n_nodes, const uint32_t** node_ptr,
+                                     const uint32_t** cptr, const uint32_t** alive_bits);
 
 /* Histogram Metric CRs (kind: histogram; pkg/kwok/metrics/metrics.go:133-160,356-462,
  * histogram.go:81-164): per series every bucket's value program runs (a lowered CEL value, as

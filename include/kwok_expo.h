@@ -1,0 +1,90 @@
+/* Device metric exposition: the Prometheus text (format 0.0.4) of a scrape written by the GPU —
+ * the consumer kwk_metrics_eval_device was left for.
+ *
+ * Replaces, per node scrape, the reference's registry gather + text encode
+ * (pkg/kwok/metrics/metrics.go:480-502,525-573, pkg/kwok/server/metrics.go:129-150:
+ * UpdateHandler.Update fills the gauges / counters, promhttp encodes every family sorted by name
+ * and every series sorted by label values).  The host builds the exposition program once per
+ * Metric CR (kwk_metric_set_exposition, kwok_metrics.h), renders every object's label block once
+ * (kwk_metric_labels_render) and uploads blocks and sort keys (kwk_expo_set_labels /
+ * kwk_expo_commit).  Each scrape, kwk_expo_scrape evaluates the values on the device
+ * (kwk_metrics_eval_device) and writes, for every node of the range, the text
+ * MetricsProgram.exposition(MetricsProgram.scrape(..)) gives for that node alone, byte for byte:
+ * every family's HELP / TYPE lines (also when the node has no series of it), the series of live
+ * pod slots in label order, the values as strconv.AppendFloat(v, 'g', -1, 64).
+ *
+ * Three launches per scrape on the engine's stream, no host round trip between them:
+ *   lengths   a workgroup per node: formats every live value once (32 bytes of device memory per
+ *             series of the range), the bytes of the node's text
+ *   scan      exclusive scan of the node totals into 64-bit offsets, the grand total
+ *   write     a workgroup per node again: every line at its scanned offset
+ * Output room is reserved by the caller (kwk_expo_reserve); a scrape whose text does not fit
+ * writes nothing and kwk_expo_result returns KWK_ECAP (the write kernel compares the scanned total
+ * with the reservation on the device, and every store is bounded by the node's scanned range).
+ */
+#ifndef KWOK_EXPO_H
+#define KWOK_EXPO_H
+
+#include <stdint.h>
+
+#include "kwok_engine.h"
+#include "kwok_metrics.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct kwk_expo kwk_expo;
+
+const char* kwk_expo_last_error(const kwk_expo* ex);
+/* a writer for `pods`' scrapes (after kwk_usage_config / kwk_usage_mixed / kwk_usage_pods and
+ * kwk_metrics_load of the same Metric CR) over its n_nodes nodes, on the engine's stream; the
+ * program is copied.  Rows of a label group are nodes, pod slots or containers
+ * (kwk_usage_read_containers order) by the group's dimension. */
+kwk_status kwk_expo_create(kwk_engine* pods, uint32_t n_nodes, const kwk_expo_program* prog, kwk_expo** out);
+kwk_status kwk_expo_destroy(kwk_expo* ex);
+/* rows [first, first + n) of `group`: row i's label block is blocks[block_offsets[i] ..
+ * block_offsets[i + 1]) and its sort key keys[key_offsets[i] .. key_offsets[i + 1])
+ * (kwk_metric_labels_render's outputs; offsets hold n + 1 entries).  Host-side until
+ * kwk_expo_commit.  After a pod is replaced: set its rows again and commit.  The row counts are the
+ * engine's layout as of kwk_expo_create or the last kwk_expo_commit: after a kwk_usage_config /
+ * kwk_usage_mixed that changes the pod or container count, commit once (it re-reads the layout and
+ * keeps the rows set so far), then set the new rows and commit again.  Rows of dead slots need not
+ * be set; a scrape that meets a live series of a labelled group whose row was never set writes
+ * nothing and kwk_expo_result returns KWK_ESTATE with their count. */
+kwk_status kwk_expo_set_labels(kwk_expo* ex, uint32_t group, uint32_t first, uint32_t n, const uint32_t* block_offsets,
+                               const char* blocks, const uint32_t* key_offsets, const char* keys);
+/* stable-sorts every node's rows of each group by key (bytewise; ties keep row order: the order of
+ * exposition()'s sorted(series, key=label values)) and uploads blocks and permutations.  Re-reads
+ * the engine's node_ptr / container layout. */
+kwk_status kwk_expo_commit(kwk_expo* ex);
+/* output room: text bytes one scrape may produce */
+kwk_status kwk_expo_reserve(kwk_expo* ex, uint64_t max_bytes);
+/* enqueue one scrape of nodes [node_first, node_first + n_nodes) at now_ns, after the caller's
+ * kwk_usage(now_ns): kwk_metrics_eval_device, kwk_metrics_series_device, then the three kernels */
+kwk_status kwk_expo_scrape(kwk_expo* ex, int64_t now_ns, uint32_t node_first, uint32_t n_nodes);
+/* synchronise; the last scrape's text size.  KWK_ECAP when it exceeds the reservation: nothing was
+ * written — reserve more and scrape again.  KWK_ESTATE: live series without a label row (above) */
+kwk_status kwk_expo_result(kwk_expo* ex, uint64_t* n_bytes);
+/* device outputs of the last scrape: n_nodes + 1 byte offsets and the bytes; node j of the range's
+ * text is bytes[offsets[j] .. offsets[j + 1]) */
+kwk_status kwk_expo_device(kwk_expo* ex, const uint64_t** offsets, const char** bytes);
+/* copy them to host memory (n_nodes + 1 offsets; the size from kwk_expo_result) */
+kwk_status kwk_expo_copy(kwk_expo* ex, uint64_t* offsets, char* bytes);
+/* HIP events around the last scrape's kernels: milliseconds of [0] the whole scrape (value
+ * evaluation included), [1] lengths, [2] scan, [3] write */
+kwk_status kwk_expo_elapsed(kwk_expo* ex, float ms[4]);
+/* Tuning and diagnosis hook, not part of the serving path (tests and tools/expo_bench.py cover both
+ * kernels with it; the default's threshold is measured at one shape only and may change): workgroup
+ * size per node, 64 (a wave per node), 256, or 0 = the default, chosen from the mean pods per node */
+kwk_status kwk_expo_set_width(kwk_expo* ex, uint32_t width);
+/* the device formatter over n doubles (tests, diagnosis): out = n x 24 bytes, lens = n lengths */
+kwk_status kwk_expo_format_values(kwk_expo* ex, const double* host_values, uint32_t n, char* out, uint8_t* lens);
+/* the host build of the same formatter (no GPU): strconv.AppendFloat(v, 'g', -1, 64) -> length */
+uint32_t kwk_expo_format_f64(double v, char out[24]);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif

@@ -23,7 +23,14 @@
  * 0 for every bucket of a histogram), exactly as the Python host's MetricsProgram does
  * (kwok_amd/host/metrics.py, cel.py lower), which is this compiler's CPU cross-check: byte-equal
  * programs on the shipped Metric CR, the histogram CRs and the reference-vector CR
- * (tests/test_metric_compiler.py).  Labels stay host CEL (string-valued: Prometheus exposition).
+ * (tests/test_metric_compiler.py).
+ *
+ * Exposition (the Prometheus text of a scrape, written on the device by kwok_expo.h): the set also
+ * builds the exposition program — families in name order with their HELP / TYPE bytes and label
+ * group — and renders an object's label block natively (kwk_metric_labels_render), for the label
+ * expressions that are a string literal or a field selection from node / pod / container.  A CR
+ * with any other label, a histogram or a host-evaluated metric has no exposition program
+ * (KWK_ENOLOWER names it): its text stays with the host (kwok_amd/host/metrics.py exposition).
  *
  * Threading: a metric set is read-only after kwk_compile_metrics; sets are independent.
  */
@@ -71,6 +78,46 @@ kwk_status kwk_metric_set_describe(const kwk_metric_set* m, const char** json);
  * the Metric CRD does not define); *n_ops = the program length (also when cap is too small:
  * KWK_ECAP).  KWK_ENOLOWER: no device form; KWK_EINVAL: the expression does not compile. */
 kwk_status kwk_cel_lower(const char* expr, uint32_t dimension, kwk_metric_op* out, uint32_t cap, uint32_t* n_ops);
+
+/* ------------------------------------------------------------------ exposition program */
+typedef struct {
+  uint32_t name_off, name_len;     /* the family's name in lits */
+  uint32_t header_off, header_len; /* "# HELP <name> <escaped help>\n# TYPE <name> <kind>\n" in lits */
+  uint32_t metric;                 /* index among the gauges / counters: kwk_metrics_eval's order */
+  uint32_t dimension;              /* KWK_METRIC_DIM_* */
+  uint32_t group;                  /* its label group */
+  uint32_t reserved;
+} kwk_expo_family;
+typedef struct {
+  uint32_t dimension;  /* rows are nodes, pod slots or containers (kwk_usage_read_containers order) */
+  uint32_t n_labels;   /* 0: the series line has no label block */
+} kwk_expo_group;
+typedef struct {
+  uint32_t n_families, n_groups, n_metrics, n_lit_bytes;
+  const kwk_expo_family* families;    /* in name order (client_golang's Gather) */
+  const kwk_expo_group* groups;       /* distinct (dimension, ordered labels) */
+  const uint32_t* metric_dimension;   /* n_metrics: every gauge / counter of the CR, in CR order */
+  const char* lits;
+} kwk_expo_program;
+
+/* the set's exposition program (arrays owned by the set).  All or nothing — KWK_ENOLOWER, the
+ * message naming the metric (and label), when a family is a histogram, is host-evaluated, or has a
+ * label expression outside the supported subset (a string literal, or node / pod / container
+ * followed by field selections): a node's text with families missing is not servable. */
+kwk_status kwk_metric_set_exposition(const kwk_metric_set* m, kwk_expo_program* out);
+
+/* One object's labels of `group`: block = `{k="v",k2="v2"}` with the values escaped as the text
+ * format does (\\, \n, \") — empty for a group without labels — and key = its sort key: the
+ * unescaped values in label order, each ended by a 0 byte (a 0 / 1 byte inside a value is written
+ * 1 1 / 1 2), so that bytewise order of keys is the order of the value lists.  node_json /
+ * pod_json: the objects the expressions select from (NULL when the group's labels do not read
+ * it); container = pod.spec.containers[container_index] for a container group.  *block_len /
+ * *key_len are always the sizes needed; KWK_ECAP when a cap is smaller (nothing usable written).
+ * KWK_EINVAL, naming the object and label, where the selection fails: a missing object or key, or
+ * a leaf that is not a string (the typed zero values CEL would substitute are not guessed). */
+kwk_status kwk_metric_labels_render(const kwk_metric_set* m, uint32_t group, const char* node_json, const char* pod_json,
+                                    uint32_t container_index, char* block, uint32_t block_cap, uint32_t* block_len,
+                                    char* key, uint32_t key_cap, uint32_t* key_len);
 
 #ifdef __cplusplus
 }

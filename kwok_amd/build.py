@@ -36,6 +36,11 @@ EMIT_SRC = [os.path.join(PKG, "csrc", "emit.hip")]
 EMIT_HDR = [os.path.join(ROOT, "include", "kwok_emit.h"), os.path.join(ROOT, "include", "kwok_engine.h"),
             os.path.join(PKG, "csrc", "timefmt.hpp")]
 EMIT_OUT = os.path.join(PKG, "lib", "libkwok_emit.so")
+EXPO_SRC = [os.path.join(PKG, "csrc", "expo.hip")]
+EXPO_HDR = [os.path.join(ROOT, "include", "kwok_expo.h"), os.path.join(ROOT, "include", "kwok_metrics.h"),
+            os.path.join(ROOT, "include", "kwok_engine.h"), os.path.join(PKG, "csrc", "f64fmt.hpp"),
+            os.path.join(PKG, "csrc", "f64fmt_tables.hpp")]
+EXPO_OUT = os.path.join(PKG, "lib", "libkwok_expo.so")
 ARCH = "gfx950"  # MI355X only
 
 
@@ -105,6 +110,20 @@ def build_emit(force: bool = False, verbose: bool = False) -> str:
     return EMIT_OUT
 
 
+def build_expo(force: bool = False, verbose: bool = False) -> str:
+    """The device exposition writer (HIP kernels over the engine's metric values, linked to the engine)."""
+    if not force and not _stale(EXPO_OUT, EXPO_SRC + EXPO_HDR + [OUT]):
+        return EXPO_OUT
+    cmd = ["hipcc", f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wno-unused-result",
+           "-Wno-unused-value", "-I", os.path.join(ROOT, "include"), "-o", EXPO_OUT + ".tmp"] + \
+        EXPO_SRC + ["-L", os.path.dirname(OUT), "-lkwok_engine", "-Wl,-rpath,$ORIGIN"]
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    subprocess.run(cmd, check=True)
+    os.replace(EXPO_OUT + ".tmp", EXPO_OUT)
+    return EXPO_OUT
+
+
 def build(force: bool = False, verbose: bool = False) -> str:
     build_encoder(force, verbose)
     build_compiler(force, verbose)
@@ -113,6 +132,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     _build_engine(force, verbose)
     build_comm(force, verbose)
     build_emit(force, verbose)
+    build_expo(force, verbose)
     return OUT
 
 

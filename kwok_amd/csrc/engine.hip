@@ -4692,6 +4692,8 @@ struct kwk_engine {
   double zero_time_unix_s = 0.0;
   double* d_mout = nullptr;
   size_t mout_cap = 0;
+  uint32_t* d_alive_bits = nullptr;  // kwk_metrics_series_device: a bit per pod slot of the last range
+  size_t alive_words = 0;
   // histogram Metric programs (kwk_histograms_load)
   kwk_metric_op* d_hops = nullptr;
   kwk_metric_bucket* d_hbuckets = nullptr;
@@ -5202,7 +5204,7 @@ kwk_status kwk_engine_destroy(kwk_engine* e) {
                   e->d_node_ptr, e->d_ukey, e->d_cpu, e->d_mem, e->d_node_out, e->d_node_cum, e->d_node_last,
                   e->d_usage_part, e->d_cluster, e->d_uchunk, e->d_podv, e->d_agg, e->d_agg_counts, e->d_agg_masks, e->d_count_part, e->d_stage_buf, e->d_pod_out, e->d_pod_cum, e->d_pod_last,
                   e->d_lease, e->d_lease_op, e->d_lease_ops, e->d_fsm, e->d_fsm_due, e->d_mixed, e->d_ckeys, e->d_ccum,
-                  e->d_mbase, e->d_cptr, e->d_mops, e->d_pod_created, e->d_node_created, e->d_node_started, e->d_mout,
+                  e->d_mbase, e->d_cptr, e->d_mops, e->d_pod_created, e->d_node_created, e->d_node_started, e->d_mout, e->d_alive_bits,
                   e->d_lease_nops, e->d_lease_stats, e->d_ukey8, e->d_kv, e->d_hops, e->d_hbuckets, e->d_hkeys,
                   e->d_hbounds, e->d_hout, e->d_id2w, e->d_w2id, e->d_fsm8, e->d_fsm8_due};
   for (void* p : ptrs) if (p) hipFree(p);
@@ -6924,6 +6926,48 @@ kwk_status kwk_metrics_eval_device(kwk_engine* e, int64_t now_ns, uint32_t node_
   *out = nullptr;
   if (kwk_status st = enqueue_metrics(e, now_ns, node_first, n_nodes, true, n_out)) return st;
   *out = e->d_mout;
+  return KWK_OK;
+}
+
+// bit i of `bits` = pod slot p0 + i is alive; one ballot (two words) per wave, n rounded up to whole waves
+__global__ __launch_bounds__(kBlock) void alive_bits_kernel(const void* __restrict__ st, StateFmt fmt, uint32_t p0, uint32_t n,
+                                                            uint32_t* __restrict__ bits) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  const bool alive = i < n && (load_state(st, (uint64_t)p0 + i, fmt).y & KWK_F_ALIVE) != 0;
+  const uint64_t b = __ballot(alive);
+  if ((threadIdx.x & 63u) == 0 && i < n) {
+    bits[2 * (size_t)(i >> 6)] = (uint32_t)b;
+    bits[2 * (size_t)(i >> 6) + 1] = (uint32_t)(b >> 32);
+  }
+}
+
+kwk_status kwk_metrics_series_device(kwk_engine* e, uint32_t node_first, uint32_t n_nodes, const uint32_t** node_ptr,
+                                     const uint32_t** cptr, const uint32_t** alive_bits) {
+  ErrScope es_(e);
+  if (!e || !node_ptr || !cptr || !alive_bits) return fail(KWK_EINVAL, "null argument");
+  if (!e->d_node_ptr) return fail(KWK_ESTATE, "kwk_usage_config must be called first");
+  if (e->has_mixed_keys && !e->d_mixed) return fail(KWK_ESTATE, "kwk_usage_mixed must be called first");
+  if ((uint64_t)node_first + n_nodes > e->n_nodes) return fail(KWK_EINVAL, "nodes beyond the usage configuration");
+  if (kwk_status st = set_dev(e)) return st;
+  if (kwk_status st = ensure_cptr(e)) return st;
+  const uint32_t p0 = e->h_node_ptr[node_first], p1 = e->h_node_ptr[node_first + n_nodes];
+  const size_t words = 2 * (((size_t)(p1 - p0) + 63) / 64) + 2;
+  if (words > e->alive_words) {
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (e->d_alive_bits) HIP_TRY(hipFree(e->d_alive_bits));
+    e->d_alive_bits = nullptr;
+    e->alive_words = 0;
+    HIP_TRY(hipMalloc(&e->d_alive_bits, 4 * words));
+    e->alive_words = words;
+  }
+  if (p1 > p0) {
+    hipLaunchKernelGGL(alive_bits_kernel, dim3((p1 - p0 + kBlock - 1) / kBlock), dim3(kBlock), 0, e->stream, e->d_st, e->fmt,
+                       p0, p1 - p0, e->d_alive_bits);
+    HIP_TRY(hipGetLastError());
+  }
+  *node_ptr = e->d_node_ptr;
+  *cptr = e->d_cptr;
+  *alive_bits = e->d_alive_bits;
   return KWK_OK;
 }
 

@@ -1,0 +1,816 @@
+// Device metric exposition (include/kwok_expo.h): the Prometheus text of a scrape, per node,
+// written on the engine's stream from the device-evaluated values.
+//
+// Reference: UpdateHandler.Update + the promhttp text encoder (pkg/kwok/metrics/metrics.go:
+// 480-502,525-573, pkg/kwok/server/metrics.go:129-150; expfmt text_create.go) — here the label
+// blocks are rendered once per object on the host (kwk_metric_labels_render), sorted once per node
+// (kwk_expo_commit), and only the values change per scrape.
+//
+// Three launches per scrape (no inter-workgroup waiting, no host round trip):
+//   expo_node_kernel<W, false>  a workgroup of W lanes per node, family-major, series in the committed
+//                               order: line = name + block + ' ' + value + '\n' (dead pod slots: none).
+//                               Formats every live value once (f64fmt.hpp) into a 32-byte stash slot
+//                               (24 bytes + length) and sums the node's bytes with its HELP / TYPE lines
+//   expo_scan_kernel            one workgroup: exclusive scan of the node totals into 64-bit offsets,
+//                               the grand total
+//   expo_node_kernel<W, true>   the same walk; the lanes take a family's lines W at a time and a block scan
+//                               of their lengths gives each its offset in the node.  A wave's 64 lines are
+//                               one contiguous span: each lane assembles its line in LDS (8-byte words,
+//                               read from the sources as aligned 8-byte words), at the span's own
+//                               misalignment, and the wave stores the span as 16-byte vectors (bytes at
+//                               the two ends).  A span longer than the LDS window is written by its
+//                               lanes directly.  The kernel returns at once when the scanned total exceeds
+//                               the reservation, and every store is bounded by the node's scanned range.
+// W = 64 (one wave per node) up to kWidePods pods per node, 256 above.
+// Both choices were measured against their alternatives — lanes storing their lines directly, and
+// formatting the value again in the write pass instead of the stash — at the C4 size (DESIGN.md
+// "Device metric exposition", `ab_c4` in profiles/r7/expo_bench.json): this pair is the fastest of
+// the four.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <numeric>
+#include <string>
+#include <vector>
+
+#include "../../include/kwok_expo.h"
+#include "f64fmt.hpp"
+
+namespace {
+
+thread_local std::string g_err;
+thread_local std::string* tl_err = nullptr;
+struct ErrScope {
+  std::string* prev;
+  explicit ErrScope(std::string* target) : prev(tl_err) { tl_err = target; }
+  ~ErrScope() { tl_err = prev; }
+};
+kwk_status fail(kwk_status code, const std::string& msg) {
+  g_err = msg;
+  if (tl_err) *tl_err = msg;
+  return code;
+}
+#define HIP_TRY(x)                                                                                \
+  do {                                                                                            \
+    hipError_t e_ = (x);                                                                          \
+    if (e_ != hipSuccess) return fail(KWK_EHIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
+  } while (0)
+
+constexpr uint32_t kScanBlock = 1024;
+constexpr uint32_t kFmtBlock = 256;
+constexpr uint32_t kWidePods = 256;  // pods per node (mean) above which a node gets 256 lanes (64 is faster at 100)
+
+struct DevFamily {
+  uint32_t name_off, name_len, header_off, header_len;
+  uint32_t dim, group;
+  uint32_t before[3];  // gauges / counters of each dimension before this family's in CR order (its value offset)
+  uint32_t reserved;
+};
+
+struct DevGroup {
+  const uint32_t* blk_off;  // rows + 1 (NULL: no labels)
+  const char* blk;
+  const uint32_t* perm;     // per node's row range: the rows in key order (NULL: node rows)
+};
+
+struct ExpoArgs {
+  const DevFamily* fam;
+  const DevGroup* grp;
+  const char* lits;
+  const uint32_t* node_ptr;
+  const uint32_t* cptr;
+  const uint32_t* pod_of;   // per container: its pod slot
+  const uint32_t* alive;    // bit per pod slot of the range
+  const double* vals;
+  uint32_t n_fam, n0, n_nodes, p0, p1, c0, c1;
+  unsigned long long* node_bytes;  // n_nodes
+  unsigned long long* offsets;     // n_nodes + 1
+  unsigned long long* total;       // [0] the text's size, [1] live series of a labelled group whose row was never set
+  char* out;
+  unsigned long long cap;
+  uint4* stash;  // 32 bytes per value: its formatted bytes and their count (lengths pass -> write pass)
+};
+
+constexpr uint32_t kLdsWave = 12288;  // LDS window of one wave's 64 lines (C4 lines: ~105 bytes)
+
+// a value's formatted bytes (at most 24) in three registers
+struct RegSink {
+  uint64_t w0 = 0, w1 = 0, w2 = 0;
+  uint32_t n = 0;
+  __device__ __forceinline__ void put(char c) {
+    const uint64_t x = (uint64_t)(uint8_t)c << (8 * (n & 7u));
+    if (n < 8) w0 |= x;
+    else if (n < 16) w1 |= x;
+    else w2 |= x;
+    ++n;
+  }
+};
+
+// bytes of one line, 8 at a time where a whole aligned word is the line's own
+template <class C8, class U64>
+struct LineSinkT {
+  C8* out;
+  unsigned long long at;   // address (offset in out) of byte 0 of the current word
+  unsigned long long end;  // the node's scanned end: nothing is stored at or beyond it
+  uint64_t acc;
+  uint32_t n, lo;          // bytes of the word filled so far; the first that is this line's
+  __device__ __forceinline__ void open(C8* o, unsigned long long pos, unsigned long long e) {
+    out = o;
+    end = e;
+    lo = (uint32_t)(pos & 7u);
+    at = pos - lo;
+    n = lo;
+    acc = 0;
+  }
+  __device__ __forceinline__ void flush() {
+    if (lo == 0 && n == 8) {
+      if (at + 8 <= end) *reinterpret_cast<U64*>(out + at) = acc;
+    } else {
+      for (uint32_t b = lo; b < n; ++b)
+        if (at + b < end) out[at + b] = (char)(acc >> (8 * b));
+    }
+    at += 8;
+    acc = 0;
+    n = 0;
+    lo = 0;
+  }
+  __device__ __forceinline__ void put(char c) {
+    acc |= (uint64_t)(uint8_t)c << (8 * n);
+    if (++n == 8) flush();
+  }
+  // k <= 8 bytes, the low ones of x
+  __device__ __forceinline__ void push(uint64_t x, uint32_t k) {
+    if (k < 8) x &= (1ull << (8 * k)) - 1ull;
+    const uint32_t nn = n + k;
+    acc |= x << (8 * n);
+    if (nn >= 8) {
+      const uint64_t rest = n ? x >> (8 * (8 - n)) : 0ull;
+      n = 8;
+      flush();
+      acc = rest;
+      n = nn - 8;
+    } else {
+      n = nn;
+    }
+  }
+  // len bytes at src, read as the aligned 8-byte words that hold them (the arrays are padded by 8)
+  __device__ __forceinline__ void run(const char* __restrict__ src, uint32_t len) {
+    if (!len) return;
+    const uint32_t sa = (uint32_t)((size_t)src & 7u);
+    const uint64_t* w = reinterpret_cast<const uint64_t*>(src - sa);
+    uint64_t cur = *w >> (8 * sa);
+    uint32_t avail = 8 - sa;
+    for (;;) {
+      const uint32_t k = avail < len ? avail : len;
+      push(cur, k);
+      len -= k;
+      if (!len) break;
+      cur = *++w;
+      avail = 8;
+    }
+  }
+  __device__ __forceinline__ void close() {
+    if (n > lo) flush();
+  }
+};
+using LineSink = LineSinkT<char, uint64_t>;
+typedef __attribute__((address_space(3))) char lds_c8;
+typedef __attribute__((address_space(3))) uint64_t lds_u64;
+using LdsSink = LineSinkT<lds_c8, lds_u64>;
+
+__device__ __forceinline__ uint32_t wave_incl(uint32_t v, uint32_t lane) {
+#pragma unroll
+  for (uint32_t d = 1; d < 64; d <<= 1) {
+    const uint32_t t = __shfl_up(v, d, 64);
+    if (lane >= d) v += t;
+  }
+  return v;
+}
+
+// exclusive offset of this lane's `len` among the workgroup's, and their total (every lane calls)
+template <uint32_t W>
+__device__ __forceinline__ uint32_t block_excl(uint32_t len, uint32_t* s_wave, uint32_t& total) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t incl = wave_incl(len, lane);
+  if (W == 64) {
+    total = __shfl(incl, 63, 64);
+    return incl - len;
+  }
+  constexpr uint32_t kWaves = W / 64;
+  uint32_t* s = s_wave;  // read before the caller's next barrier: the write loop has two between calls
+  if (lane == 63) s[threadIdx.x >> 6] = incl;
+  __syncthreads();
+  uint32_t base = 0, t = 0;
+#pragma unroll
+  for (uint32_t w = 0; w < kWaves; ++w) {
+    const uint32_t x = s[w];
+    if (w < (threadIdx.x >> 6)) base += x;
+    t += x;
+  }
+  total = t;
+  return base + incl - len;
+}
+
+template <uint32_t W, bool kWrite>
+__global__ __launch_bounds__(W) void expo_node_kernel(ExpoArgs a) {
+  __shared__ __attribute__((aligned(16))) char s_stage[kWrite ? (W / 64) * kLdsWave : 16];
+  __shared__ uint32_t s_wave[W / 64];
+  __shared__ unsigned long long s_sum[W / 64];
+  const uint32_t j = blockIdx.x, tid = threadIdx.x;
+  if (j >= a.n_nodes) return;
+  unsigned long long pos = 0, end = 0, sum = 0;
+  if (kWrite) {
+    // the text does not fit the reservation, or a live series has no labels: nothing is written
+    if (a.total[0] > a.cap || a.total[1] != 0) return;
+    pos = a.offsets[j];
+    end = a.offsets[j + 1];
+  }
+  const uint32_t node = a.n0 + j;
+  const uint32_t pb = a.node_ptr[node], pe = a.node_ptr[node + 1];
+  const uint32_t cb = a.cptr[pb], ce = a.cptr[pe];
+  for (uint32_t f = 0; f < a.n_fam; ++f) {
+    const DevFamily F = a.fam[f];
+    const DevGroup G = a.grp[F.group];
+    if (kWrite) {
+      for (uint32_t i = tid; i < F.header_len; i += W)
+        if (pos + i < end) a.out[pos + i] = a.lits[F.header_off + i];
+      pos += F.header_len;
+    } else if (tid == 0) {
+      sum += F.header_len;
+    }
+    const uint32_t first = F.dim == KWK_METRIC_DIM_NODE ? node : F.dim == KWK_METRIC_DIM_POD ? pb : cb;
+    const uint32_t count = F.dim == KWK_METRIC_DIM_NODE ? 1u : F.dim == KWK_METRIC_DIM_POD ? pe - pb : ce - cb;
+    const uint32_t base = F.dim == KWK_METRIC_DIM_NODE ? a.n0 : F.dim == KWK_METRIC_DIM_POD ? a.p0 : a.c0;
+    const double* vals = a.vals + ((unsigned long long)F.before[0] * a.n_nodes + (unsigned long long)F.before[1] * (a.p1 - a.p0) +
+                                   (unsigned long long)F.before[2] * (a.c1 - a.c0));
+    for (uint32_t s0 = 0; s0 < count; s0 += W) {
+      const uint32_t s = s0 + tid;
+      uint32_t len = 0, row = 0, bo = 0, bl = 0;
+      double v = 0.0;
+      RegSink rs;
+      if (s < count) {
+        row = G.perm ? G.perm[first + s] : first + s;
+        bool alive = true;
+        if (F.dim != KWK_METRIC_DIM_NODE) {
+          const uint32_t pod = (F.dim == KWK_METRIC_DIM_POD ? row : a.pod_of[row]) - a.p0;
+          alive = (a.alive[pod >> 5] >> (pod & 31u)) & 1u;
+        }
+        if (alive) {
+          v = vals[row - base];
+          if (G.blk_off) {
+            bo = G.blk_off[row];
+            bl = G.blk_off[row + 1] - bo;
+            if (!kWrite && bl == 0) atomicAdd(&a.total[1], 1ull);  // a rendered block is never empty ("{..}")
+          }
+          // the value's text: formatted once, by the lengths pass
+          uint4* st = a.stash + 2 * (size_t)((vals - a.vals) + (row - base));
+          if (!kWrite) {
+            kwkf64::format(v, rs);
+            st[0] = make_uint4((uint32_t)rs.w0, (uint32_t)(rs.w0 >> 32), (uint32_t)rs.w1, (uint32_t)(rs.w1 >> 32));
+            st[1] = make_uint4((uint32_t)rs.w2, (uint32_t)(rs.w2 >> 32), rs.n, 0u);
+          } else {
+            const uint4 x = st[0], y = st[1];
+            rs.w0 = x.x | (uint64_t)x.y << 32;
+            rs.w1 = x.z | (uint64_t)x.w << 32;
+            rs.w2 = y.x | (uint64_t)y.y << 32;
+            rs.n = y.z < (uint32_t)kwkf64::kMaxBytes ? y.z : (uint32_t)kwkf64::kMaxBytes;
+          }
+          len = F.name_len + bl + 2u + rs.n;
+        }
+      }
+      if (!kWrite) {
+        sum += len;
+      } else {
+        uint32_t total;
+        const uint32_t at = block_excl<W>(len, s_wave, total);
+        // this wave's lines are one contiguous span: staged in LDS at the span's own misalignment and
+        // stored as 16-byte vectors (a span beyond the window goes the direct way)
+        const uint32_t lane = tid & 63u;
+        const uint32_t wfirst = __shfl(at, 0, 64), wtotal = __shfl(at + len, 63, 64) - wfirst;
+        const unsigned long long gbase = pos + wfirst;
+        const uint32_t mis = (uint32_t)(gbase & 15u);
+        const bool staged = mis + wtotal <= kLdsWave;
+        char* stage = s_stage + (tid >> 6) * kLdsWave;
+        auto line = [&](auto& o) {
+          o.run(a.lits + F.name_off, F.name_len);
+          o.run(G.blk + bo, bl);
+          o.put(' ');
+          o.push(rs.w0, rs.n < 8 ? rs.n : 8u);
+          if (rs.n > 8) o.push(rs.w1, rs.n < 16 ? rs.n - 8 : 8u);
+          if (rs.n > 16) o.push(rs.w2, rs.n - 16);
+          o.put('\n');
+          o.close();
+        };
+        if (len) {
+          if (staged) {
+            LdsSink o;
+            o.open((lds_c8*)stage, mis + (at - wfirst), mis + wtotal);
+            line(o);
+          } else {
+            LineSink o;
+            o.open(a.out, pos + at, end);
+            line(o);
+          }
+        }
+        __syncthreads();
+        if (staged) {
+          const unsigned long long g0 = gbase - mis;  // 16-byte aligned
+          const uint32_t hi = mis + wtotal;
+          for (uint32_t q = 16 * lane; q < hi; q += 16 * 64) {
+            if (q >= mis && q + 16 <= hi) {
+              if (g0 + q + 16 <= end) *reinterpret_cast<uint4*>(a.out + g0 + q) = *reinterpret_cast<const uint4*>(stage + q);
+            } else {
+              for (uint32_t b = q < mis ? mis : q; b < q + 16 && b < hi; ++b)
+                if (g0 + b < end) a.out[g0 + b] = stage[b];
+            }
+          }
+        }
+        __syncthreads();
+        pos += total;
+      }
+    }
+  }
+  if (!kWrite) {
+#pragma unroll
+    for (uint32_t d = 32; d; d >>= 1) sum += __shfl_down(sum, d, 64);
+    if (W == 64) {
+      if (tid == 0) a.node_bytes[j] = sum;
+    } else {
+      if ((tid & 63u) == 0) s_sum[tid >> 6] = sum;
+      __syncthreads();
+      if (tid == 0) {
+        unsigned long long t = 0;
+        for (uint32_t w = 0; w < W / 64; ++w) t += s_sum[w];
+        a.node_bytes[j] = t;
+      }
+    }
+  }
+}
+
+// offsets[j] = sum of node_bytes[0 .. j), offsets[n] = *total = the text's size
+__global__ __launch_bounds__(kScanBlock) void expo_scan_kernel(const unsigned long long* __restrict__ node_bytes, uint32_t n,
+                                                               unsigned long long* __restrict__ offsets,
+                                                               unsigned long long* __restrict__ total) {
+  __shared__ unsigned long long s_wave[kScanBlock / 64];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  unsigned long long carry = 0;
+  for (uint32_t b = 0; b < n; b += kScanBlock) {
+    const uint32_t i = b + tid;
+    const unsigned long long v = i < n ? node_bytes[i] : 0ull;
+    unsigned long long incl = v;
+#pragma unroll
+    for (uint32_t d = 1; d < 64; d <<= 1) {
+      const unsigned long long t = __shfl_up(incl, d, 64);
+      if (lane >= d) incl += t;
+    }
+    if (lane == 63) s_wave[wave] = incl;
+    __syncthreads();
+    unsigned long long base = 0, chunk = 0;
+    for (uint32_t w = 0; w < kScanBlock / 64; ++w) {
+      const unsigned long long x = s_wave[w];
+      if (w < wave) base += x;
+      chunk += x;
+    }
+    if (i < n) offsets[i] = carry + base + incl - v;
+    carry += chunk;
+    __syncthreads();
+  }
+  if (tid == 0) {
+    offsets[n] = carry;
+    *total = carry;
+  }
+}
+
+__global__ __launch_bounds__(kFmtBlock) void expo_format_kernel(const double* __restrict__ v, uint32_t n, char* __restrict__ out,
+                                                                uint8_t* __restrict__ lens) {
+  const uint32_t i = blockIdx.x * kFmtBlock + threadIdx.x;
+  if (i >= n) return;
+  lens[i] = (uint8_t)kwkf64::format_f64(v[i], out + (size_t)i * kwkf64::kMaxBytes);
+}
+
+struct Group {
+  uint32_t dim = 0, n_labels = 0;
+  std::vector<std::string> blocks, keys;  // per row
+  uint32_t* d_blk_off = nullptr;
+  char* d_blk = nullptr;
+  uint32_t* d_perm = nullptr;
+};
+
+}  // namespace
+
+struct kwk_expo {
+  std::string err;
+  kwk_engine* eng = nullptr;  // must outlive the writer
+  hipStream_t stream = nullptr;  // the engine's stream as of the current call (it may be re-created)
+  int device = 0;
+  uint32_t n_nodes = 0, n_pods = 0, n_cont = 0, width = 0;
+  uint4* d_stash = nullptr;
+  uint64_t stash_cap = 0;
+  std::vector<DevFamily> fam;
+  std::vector<Group> groups;
+  std::vector<uint32_t> h_node_ptr, h_cptr;
+  DevFamily* d_fam = nullptr;
+  DevGroup* d_grp = nullptr;
+  char* d_lits = nullptr;
+  uint32_t* d_pod_of = nullptr;
+  unsigned long long* d_node_bytes = nullptr;
+  unsigned long long* d_offsets = nullptr;
+  unsigned long long* d_total = nullptr;
+  uint32_t cap_nodes = 0;
+  char* d_out = nullptr;
+  uint64_t cap_bytes = 0;
+  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  bool committed = false, scraped = false;
+  uint32_t last_nodes = 0;
+
+  ~kwk_expo() {
+    hipSetDevice(device);
+    void* s = nullptr;
+    if (eng && kwk_stream(eng, &s) == KWK_OK && s) hipStreamSynchronize(static_cast<hipStream_t>(s));
+    for (Group& g : groups)
+      for (void* p : {(void*)g.d_blk_off, (void*)g.d_blk, (void*)g.d_perm})
+        if (p) hipFree(p);
+    for (void* p : {(void*)d_fam, (void*)d_grp, (void*)d_lits, (void*)d_pod_of, (void*)d_node_bytes, (void*)d_offsets,
+                    (void*)d_total, (void*)d_out, (void*)d_stash})
+      if (p) hipFree(p);
+    for (hipEvent_t e : ev)
+      if (e) hipEventDestroy(e);
+  }
+};
+
+namespace {
+
+kwk_status bind(kwk_expo* ex) {
+  void* s = nullptr;
+  if (kwk_stream(ex->eng, &s) != KWK_OK || !s) return fail(KWK_ESTATE, std::string("kwk_stream: ") + kwk_last_error(ex->eng));
+  ex->stream = static_cast<hipStream_t>(s);
+  HIP_TRY(hipSetDevice(ex->device));
+  return KWK_OK;
+}
+
+// copies ordered on the engine's (non-blocking) stream
+kwk_status copy_in(kwk_expo* ex, void* dst, const void* src, size_t bytes) {
+  if (!bytes) return KWK_OK;
+  HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ex->stream));
+  HIP_TRY(hipStreamSynchronize(ex->stream));
+  return KWK_OK;
+}
+
+kwk_status copy_out(kwk_expo* ex, void* dst, const void* src, size_t bytes) {
+  if (!bytes) return KWK_OK;
+  HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ex->stream));
+  HIP_TRY(hipStreamSynchronize(ex->stream));
+  return KWK_OK;
+}
+
+// replaces *dst by a device copy of n items (the stream is idle: callers synchronise first)
+template <typename T>
+kwk_status replace(kwk_expo* ex, T** dst, const T* src, size_t n) {
+  if (*dst) HIP_TRY(hipFree(*dst));
+  *dst = nullptr;
+  void* d = nullptr;
+  HIP_TRY(hipMalloc(&d, std::max<size_t>(1, n) * sizeof(T)));
+  *dst = static_cast<T*>(d);
+  return copy_in(ex, d, src, n * sizeof(T));
+}
+
+uint32_t group_rows(const kwk_expo* ex, uint32_t dim) {
+  return dim == KWK_METRIC_DIM_NODE ? ex->n_nodes : dim == KWK_METRIC_DIM_POD ? ex->n_pods : ex->n_cont;
+}
+
+// the engine's node_ptr / cptr as of now (host copies), the row counts of every group
+kwk_status refresh_layout(kwk_expo* ex) {
+  const uint32_t *np = nullptr, *cp = nullptr, *al = nullptr;
+  if (kwk_metrics_series_device(ex->eng, 0, ex->n_nodes, &np, &cp, &al) != KWK_OK)
+    return fail(KWK_ESTATE, std::string("kwk_metrics_series_device: ") + kwk_last_error(ex->eng));
+  ex->h_node_ptr.resize((size_t)ex->n_nodes + 1);
+  if (kwk_status st = copy_out(ex, ex->h_node_ptr.data(), np, 4 * ex->h_node_ptr.size())) return st;
+  ex->n_pods = ex->h_node_ptr[ex->n_nodes];
+  ex->h_cptr.resize((size_t)ex->n_pods + 1);
+  if (kwk_status st = copy_out(ex, ex->h_cptr.data(), cp, 4 * ex->h_cptr.size())) return st;
+  ex->n_cont = ex->h_cptr[ex->n_pods];
+  for (Group& g : ex->groups) {
+    g.blocks.resize(group_rows(ex, g.dim));
+    g.keys.resize(group_rows(ex, g.dim));
+  }
+  return KWK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* kwk_expo_last_error(const kwk_expo* ex) { return ex ? ex->err.c_str() : g_err.c_str(); }
+
+uint32_t kwk_expo_format_f64(double v, char out[24]) { return kwkf64::format_f64(v, out); }
+
+kwk_status kwk_expo_create(kwk_engine* pods, uint32_t n_nodes, const kwk_expo_program* prog, kwk_expo** out) {
+  ErrScope es_(nullptr);
+  if (!pods || !prog || !out) return fail(KWK_EINVAL, "null argument");
+  if ((prog->n_families && (!prog->families || !prog->lits)) || (prog->n_groups && !prog->groups) ||
+      (prog->n_metrics && !prog->metric_dimension))
+    return fail(KWK_EINVAL, "exposition program: null array");
+  std::vector<DevFamily> fam;
+  for (uint32_t f = 0; f < prog->n_families; ++f) {
+    const kwk_expo_family& F = prog->families[f];
+    if ((uint64_t)F.name_off + F.name_len > prog->n_lit_bytes || (uint64_t)F.header_off + F.header_len > prog->n_lit_bytes)
+      return fail(KWK_EINVAL, "exposition program: family " + std::to_string(f) + " bytes beyond lits");
+    if (F.group >= prog->n_groups || F.metric >= prog->n_metrics || F.dimension > KWK_METRIC_DIM_CONTAINER ||
+        prog->groups[F.group].dimension != F.dimension || prog->metric_dimension[F.metric] != F.dimension)
+      return fail(KWK_EINVAL, "exposition program: family " + std::to_string(f) + " group / metric / dimension");
+    DevFamily d{};
+    d.name_off = F.name_off; d.name_len = F.name_len; d.header_off = F.header_off; d.header_len = F.header_len;
+    d.dim = F.dimension; d.group = F.group;
+    for (uint32_t m = 0; m < F.metric; ++m) {
+      if (prog->metric_dimension[m] > KWK_METRIC_DIM_CONTAINER) return fail(KWK_EINVAL, "exposition program: metric dimension");
+      ++d.before[prog->metric_dimension[m]];
+    }
+    fam.push_back(d);
+  }
+  void* s = nullptr;
+  if (kwk_stream(pods, &s) != KWK_OK) return fail(KWK_EINVAL, std::string("kwk_stream: ") + kwk_last_error(pods));
+  auto* ex = new kwk_expo();
+  ex->eng = pods;
+  ex->stream = static_cast<hipStream_t>(s);
+  ex->n_nodes = n_nodes;
+  ex->fam = std::move(fam);
+  ex->groups.resize(prog->n_groups);
+  for (uint32_t g = 0; g < prog->n_groups; ++g) {
+    ex->groups[g].dim = prog->groups[g].dimension;
+    ex->groups[g].n_labels = prog->groups[g].n_labels;
+  }
+  auto init = [&]() -> kwk_status {
+    HIP_TRY(hipStreamGetDevice(ex->stream, &ex->device));
+    if (kwk_status st = bind(ex)) return st;
+    if (kwk_status st = refresh_layout(ex)) return st;
+    if (kwk_status st = replace(ex, &ex->d_fam, ex->fam.data(), ex->fam.size())) return st;
+    const std::string lits = std::string(prog->lits, prog->n_lit_bytes) + std::string(8, '\0');  // read as 8-byte words
+    if (kwk_status st = replace(ex, &ex->d_lits, lits.data(), lits.size())) return st;
+    HIP_TRY(hipMalloc(&ex->d_total, 16));
+    HIP_TRY(hipMemsetAsync(ex->d_total, 0, 16, ex->stream));
+    for (hipEvent_t& e : ex->ev) HIP_TRY(hipEventCreate(&e));
+    return KWK_OK;
+  };
+  if (kwk_status st = init()) {
+    delete ex;
+    return st;
+  }
+  *out = ex;
+  return KWK_OK;
+}
+
+kwk_status kwk_expo_destroy(kwk_expo* ex) {
+  delete ex;
+  return KWK_OK;
+}
+
+kwk_status kwk_expo_set_labels(kwk_expo* ex, uint32_t group, uint32_t first, uint32_t n, const uint32_t* block_offsets,
+                               const char* blocks, const uint32_t* key_offsets, const char* keys) {
+  ErrScope es_(ex ? &ex->err : nullptr);
+  if (!ex || (n && (!block_offsets || !key_offsets))) return fail(KWK_EINVAL, "null argument");
+  if (group >= ex->groups.size()) return fail(KWK_EINVAL, "label group out of range");
+  Group& g = ex->groups[group];
+  if ((uint64_t)first + n > g.blocks.size()) return fail(KWK_EINVAL, "rows beyond the group's objects");
+  for (uint32_t i = 0; i < n; ++i) {
+    if (block_offsets[i + 1] < block_offsets[i] || key_offsets[i + 1] < key_offsets[i])
+      return fail(KWK_EINVAL, "offsets must be non-decreasing");
+    if ((block_offsets[i + 1] > block_offsets[i] && !blocks) || (key_offsets[i + 1] > key_offsets[i] && !keys))
+      return fail(KWK_EINVAL, "null argument");
+  }
+  for (uint32_t i = 0; i < n; ++i) {
+    g.blocks[first + i].assign(blocks + block_offsets[i], blocks + block_offsets[i + 1]);
+    g.keys[first + i].assign(keys + key_offsets[i], keys + key_offsets[i + 1]);
+  }
+  ex->committed = false;
+  return KWK_OK;
+}
+
+kwk_status kwk_expo_commit(kwk_expo* ex) {
+  ErrScope es_(ex ? &ex->err : nullptr);
+  if (!ex) return fail(KWK_EINVAL, "null writer");
+  if (kwk_status st = bind(ex)) return st;
+  if (kwk_status st = refresh_layout(ex)) return st;
+  HIP_TRY(hipStreamSynchronize(ex->stream));
+  std::vector<uint32_t> pod_of(ex->n_cont);
+  for (uint32_t p = 0; p < ex->n_pods; ++p)
+    for (uint32_t c = ex->h_cptr[p]; c < ex->h_cptr[p + 1]; ++c) pod_of[c] = p;
+  if (kwk_status st = replace(ex, &ex->d_pod_of, pod_of.data(), pod_of.size())) return st;
+  std::vector<DevGroup> dg(ex->groups.size());
+  for (size_t gi = 0; gi < ex->groups.size(); ++gi) {
+    Group& g = ex->groups[gi];
+    const size_t rows = g.blocks.size();
+    if (g.n_labels) {
+      std::vector<uint32_t> off(rows + 1);
+      uint64_t total = 0;
+      for (size_t r = 0; r < rows; ++r) {
+        off[r] = (uint32_t)total;
+        total += g.blocks[r].size();
+        if (total > 0xFFFFFFFFull) return fail(KWK_ECAP, "more than 4 GiB of label blocks in a group");
+      }
+      off[rows] = (uint32_t)total;
+      std::string blob;
+      blob.reserve(total + 8);
+      for (const std::string& b : g.blocks) blob += b;
+      blob.append(8, '\0');  // read as 8-byte words
+      if (kwk_status st = replace(ex, &g.d_blk_off, off.data(), off.size())) return st;
+      if (kwk_status st = replace(ex, &g.d_blk, blob.data(), blob.size())) return st;
+    }
+    if (g.dim != KWK_METRIC_DIM_NODE) {
+      std::vector<uint32_t> perm(rows);
+      std::iota(perm.begin(), perm.end(), 0u);
+      const std::vector<uint32_t>& first = ex->h_node_ptr;
+      for (uint32_t j = 0; j < ex->n_nodes; ++j) {
+        const uint32_t lo = g.dim == KWK_METRIC_DIM_POD ? first[j] : ex->h_cptr[first[j]];
+        const uint32_t hi = g.dim == KWK_METRIC_DIM_POD ? first[j + 1] : ex->h_cptr[first[j + 1]];
+        std::stable_sort(perm.begin() + lo, perm.begin() + hi,
+                         [&](uint32_t x, uint32_t y) { return g.keys[x] < g.keys[y]; });  // std::string: unsigned bytes
+      }
+      if (kwk_status st = replace(ex, &g.d_perm, perm.data(), perm.size())) return st;
+    }
+    dg[gi] = DevGroup{g.d_blk_off, g.d_blk, g.d_perm};
+  }
+  if (kwk_status st = replace(ex, &ex->d_grp, dg.data(), dg.size())) return st;
+  ex->committed = true;
+  return KWK_OK;
+}
+
+kwk_status kwk_expo_reserve(kwk_expo* ex, uint64_t max_bytes) {
+  ErrScope es_(ex ? &ex->err : nullptr);
+  if (!ex) return fail(KWK_EINVAL, "null writer");
+  if (kwk_status st = bind(ex)) return st;
+  HIP_TRY(hipStreamSynchronize(ex->stream));
+  if (ex->d_out) HIP_TRY(hipFree(ex->d_out));
+  ex->d_out = nullptr;
+  ex->cap_bytes = 0;
+  HIP_TRY(hipMalloc(&ex->d_out, std::max<size_t>(8, (size_t)max_bytes)));
+  ex->cap_bytes = max_bytes;
+  return KWK_OK;
+}
+
+kwk_status kwk_expo_set_width(kwk_expo* ex, uint32_t width) {
+  ErrScope es_(ex ? &ex->err : nullptr);
+  if (!ex) return fail(KWK_EINVAL, "null writer");
+  if (width != 0 && width != 64 && width != 256) return fail(KWK_EINVAL, "width must be 0, 64 or 256");
+  ex->width = width;
+  return KWK_OK;
+}
+
+kwk_status kwk_expo_scrape(kwk_expo* ex, int64_t now_ns, uint32_t node_first, uint32_t n_nodes) {
+  ErrScope es_(ex ? &ex->err : nullptr);
+  if (!ex) return fail(KWK_EINVAL, "null writer");
+  if (!ex->committed) return fail(KWK_ESTATE, "kwk_expo_commit must come first");
+  if ((uint64_t)node_first + n_nodes > ex->n_nodes) return fail(KWK_EINVAL, "nodes beyond the writer's");
+  if (kwk_status st = bind(ex)) return st;
+  if (!ex->d_out)
+    if (kwk_status st = kwk_expo_reserve(ex, 0)) return st;
+  if (n_nodes + 1 > ex->cap_nodes) {
+    HIP_TRY(hipStreamSynchronize(ex->stream));
+    if (ex->d_node_bytes) HIP_TRY(hipFree(ex->d_node_bytes));
+    if (ex->d_offsets) HIP_TRY(hipFree(ex->d_offsets));
+    ex->d_node_bytes = ex->d_offsets = nullptr;
+    ex->cap_nodes = 0;
+    HIP_TRY(hipMalloc(&ex->d_node_bytes, 8 * ((size_t)n_nodes + 1)));
+    HIP_TRY(hipMalloc(&ex->d_offsets, 8 * ((size_t)n_nodes + 1)));
+    ex->cap_nodes = n_nodes + 1;
+  }
+  HIP_TRY(hipEventRecord(ex->ev[0], ex->stream));
+  ExpoArgs a{};
+  uint64_t n_vals = 0;
+  if (kwk_metrics_eval_device(ex->eng, now_ns, node_first, n_nodes, &a.vals, &n_vals) != KWK_OK)
+    return fail(KWK_ESTATE, std::string("kwk_metrics_eval_device: ") + kwk_last_error(ex->eng));
+  if (kwk_metrics_series_device(ex->eng, node_first, n_nodes, &a.node_ptr, &a.cptr, &a.alive) != KWK_OK)
+    return fail(KWK_ESTATE, std::string("kwk_metrics_series_device: ") + kwk_last_error(ex->eng));
+  a.fam = ex->d_fam;
+  a.grp = ex->d_grp;
+  a.lits = ex->d_lits;
+  a.pod_of = ex->d_pod_of;
+  a.n_fam = (uint32_t)ex->fam.size();
+  a.n0 = node_first;
+  a.n_nodes = n_nodes;
+  a.p0 = ex->h_node_ptr[node_first];
+  a.p1 = ex->h_node_ptr[node_first + n_nodes];
+  a.c0 = ex->h_cptr[a.p0];
+  a.c1 = ex->h_cptr[a.p1];
+  a.node_bytes = ex->d_node_bytes;
+  a.offsets = ex->d_offsets;
+  a.total = ex->d_total;
+  a.out = ex->d_out;
+  a.cap = ex->cap_bytes;
+  // the values this walk reads are the values the engine wrote: the same series count
+  uint64_t want = 0;
+  for (const DevFamily& F : ex->fam)
+    want += F.dim == KWK_METRIC_DIM_NODE ? n_nodes : F.dim == KWK_METRIC_DIM_POD ? a.p1 - a.p0 : a.c1 - a.c0;
+  if (want != n_vals)
+    return fail(KWK_ESTATE, "the engine's loaded metrics (" + std::to_string(n_vals) + " series) are not the exposition "
+                            "program's (" + std::to_string(want) + "): kwk_metrics_load the same Metric CR; commit after "
+                            "kwk_usage_config");
+  const uint32_t width = ex->width ? ex->width : (n_nodes && (a.p1 - a.p0) / n_nodes > kWidePods) ? 256u : 64u;
+  if (n_vals > ex->stash_cap) {
+    HIP_TRY(hipStreamSynchronize(ex->stream));
+    if (ex->d_stash) HIP_TRY(hipFree(ex->d_stash));
+    ex->d_stash = nullptr;
+    ex->stash_cap = 0;
+    HIP_TRY(hipMalloc(&ex->d_stash, 32 * (size_t)n_vals));
+    ex->stash_cap = n_vals;
+  }
+  a.stash = ex->d_stash;
+#define KWK_EXPO_LAUNCH(WR)                                                                                      \
+  do {                                                                                                          \
+    if (width == 64) hipLaunchKernelGGL((expo_node_kernel<64, WR>), dim3(n_nodes), dim3(64), 0, ex->stream, a); \
+    else hipLaunchKernelGGL((expo_node_kernel<256, WR>), dim3(n_nodes), dim3(256), 0, ex->stream, a);           \
+  } while (0)
+  HIP_TRY(hipMemsetAsync(ex->d_total + 1, 0, 8, ex->stream));
+  HIP_TRY(hipEventRecord(ex->ev[1], ex->stream));
+  if (n_nodes) {
+    KWK_EXPO_LAUNCH(false);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipEventRecord(ex->ev[2], ex->stream));
+  hipLaunchKernelGGL(expo_scan_kernel, dim3(1), dim3(kScanBlock), 0, ex->stream, ex->d_node_bytes, n_nodes, ex->d_offsets,
+                     ex->d_total);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(ex->ev[3], ex->stream));
+  if (n_nodes) {
+    KWK_EXPO_LAUNCH(true);
+    HIP_TRY(hipGetLastError());
+  }
+#undef KWK_EXPO_LAUNCH
+  HIP_TRY(hipEventRecord(ex->ev[4], ex->stream));
+  ex->scraped = true;
+  ex->last_nodes = n_nodes;
+  return KWK_OK;
+}
+
+kwk_status kwk_expo_result(kwk_expo* ex, uint64_t* n_bytes) {
+  ErrScope es_(ex ? &ex->err : nullptr);
+  if (!ex || !n_bytes) return fail(KWK_EINVAL, "null argument");
+  if (!ex->scraped) return fail(KWK_ESTATE, "kwk_expo_scrape must come first");
+  if (kwk_status st = bind(ex)) return st;
+  unsigned long long t[2] = {0, 0};
+  if (kwk_status st = copy_out(ex, t, ex->d_total, sizeof t)) return st;
+  *n_bytes = t[0];
+  if (t[1])
+    return fail(KWK_ESTATE, std::to_string(t[1]) + " live series of a labelled group have no label row: nothing was written; "
+                            "kwk_expo_set_labels their rows and kwk_expo_commit");
+  if (t[0] > ex->cap_bytes)
+    return fail(KWK_ECAP, "the text exceeds the reservation: kwk_expo_reserve(" + std::to_string(t[0]) + ") and scrape again");
+  return KWK_OK;
+}
+
+kwk_status kwk_expo_device(kwk_expo* ex, const uint64_t** offsets, const char** bytes) {
+  ErrScope es_(ex ? &ex->err : nullptr);
+  if (!ex) return fail(KWK_EINVAL, "null writer");
+  if (offsets) *offsets = reinterpret_cast<const uint64_t*>(ex->d_offsets);
+  if (bytes) *bytes = ex->d_out;
+  return KWK_OK;
+}
+
+kwk_status kwk_expo_copy(kwk_expo* ex, uint64_t* offsets, char* bytes) {
+  ErrScope es_(ex ? &ex->err : nullptr);
+  uint64_t nb = 0;
+  if (kwk_status st = kwk_expo_result(ex, &nb)) return st;
+  if (!offsets || (nb && !bytes)) return fail(KWK_EINVAL, "null argument");
+  if (kwk_status st = copy_out(ex, offsets, ex->d_offsets, 8 * ((size_t)ex->last_nodes + 1))) return st;
+  return copy_out(ex, bytes, ex->d_out, (size_t)nb);
+}
+
+kwk_status kwk_expo_elapsed(kwk_expo* ex, float ms[4]) {
+  ErrScope es_(ex ? &ex->err : nullptr);
+  if (!ex || !ms) return fail(KWK_EINVAL, "null argument");
+  if (!ex->scraped) return fail(KWK_ESTATE, "kwk_expo_scrape must come first");
+  if (kwk_status st = bind(ex)) return st;
+  HIP_TRY(hipEventSynchronize(ex->ev[4]));
+  HIP_TRY(hipEventElapsedTime(&ms[0], ex->ev[0], ex->ev[4]));
+  for (int i = 1; i < 4; ++i) HIP_TRY(hipEventElapsedTime(&ms[i], ex->ev[i], ex->ev[i + 1]));
+  return KWK_OK;
+}
+
+kwk_status kwk_expo_format_values(kwk_expo* ex, const double* host_values, uint32_t n, char* out, uint8_t* lens) {
+  ErrScope es_(ex ? &ex->err : nullptr);
+  if (!ex || (n && (!host_values || !out || !lens))) return fail(KWK_EINVAL, "null argument");
+  if (!n) return KWK_OK;
+  if (kwk_status st = bind(ex)) return st;
+  double* d_v = nullptr;
+  char* d_o = nullptr;
+  uint8_t* d_l = nullptr;
+  auto run = [&]() -> kwk_status {
+    HIP_TRY(hipMalloc(&d_v, 8 * (size_t)n));
+    HIP_TRY(hipMalloc(&d_o, (size_t)kwkf64::kMaxBytes * n));
+    HIP_TRY(hipMalloc(&d_l, n));
+    if (kwk_status st = copy_in(ex, d_v, host_values, 8 * (size_t)n)) return st;
+    HIP_TRY(hipMemsetAsync(d_o, 0, (size_t)kwkf64::kMaxBytes * n, ex->stream));
+    hipLaunchKernelGGL(expo_format_kernel, dim3((n + kFmtBlock - 1) / kFmtBlock), dim3(kFmtBlock), 0, ex->stream, d_v, n, d_o,
+                       d_l);
+    HIP_TRY(hipGetLastError());
+    if (kwk_status st = copy_out(ex, out, d_o, (size_t)kwkf64::kMaxBytes * n)) return st;
+    return copy_out(ex, lens, d_l, n);
+  };
+  const kwk_status st = run();
+  hipStreamSynchronize(ex->stream);
+  for (void* p : {(void*)d_v, (void*)d_o, (void*)d_l})
+    if (p) hipFree(p);
+  return st;
+}
+
+}  // extern "C"

@@ -1,10 +1,12 @@
 // Native Metric CR compiler (include/kwok_metrics.h): a Metric CR's gauges, counters and
-// histograms -> the device programs of kwk_metrics_load / kwk_histograms_load.  Restates
+// histograms -> the device programs of kwk_metrics_load / kwk_histograms_load, the exposition
+// program of the device text writer (kwok_expo.h) and the native label renderer.  Restates
 // kwok_amd/host/metrics.py (load_metric_yaml, MetricsProgram) over celc.hpp's lowering.
 //
 // Reference: pkg/kwok/metrics/metrics.go:168-462 (updateGauge / updateCounter / updateHistogram:
 // one compiled CEL program per value and per bucket, node / pod / container series),
 // :133-160 (a histogram's visible bounds), pkg/apis/v1alpha1/metric_types.go (the CRD).
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <memory>
@@ -18,7 +20,32 @@
 
 using kwkjson::JV;
 
+// one label of a metric: a string literal, or a selection chain from node / pod / container
+struct LabelExpr {
+  std::string name, src;
+  bool lit = false;
+  std::string value;              // lit
+  int root = 0;                   // 0 node, 1 pod, 2 container
+  std::vector<std::string> path;  // fields selected from the root
+};
+
+struct MetricCfg {
+  std::string name, help, kind;
+  uint32_t dim = 0, index = 0;
+  bool device = true;
+  std::vector<std::pair<std::string, std::string>> labels;  // (name, CEL source)
+};
+
 struct kwk_metric_set {
+  std::vector<MetricCfg> cfgs;
+  // the exposition program (kwk_metric_set_exposition), or why there is none
+  kwk_status expo_status = KWK_OK;
+  std::string expo_err;
+  std::vector<kwk_expo_family> families;
+  std::vector<kwk_expo_group> groups;
+  std::vector<std::vector<LabelExpr>> group_labels;
+  std::vector<uint32_t> metric_dims;
+  std::string lits;
   std::vector<kwk_metric_desc> metrics;
   std::vector<kwk_metric_op> ops;
   std::vector<kwk_histogram_desc> hists;
@@ -102,6 +129,107 @@ std::vector<kwkcel::Op> lower_value(const std::string& src, uint32_t dim, const 
 }
 
 const char* kDims[] = {"node", "pod", "container"};
+
+// ------------------------------------------------------------------ exposition (kwok_metrics.h)
+struct NoExposition : std::runtime_error { using std::runtime_error::runtime_error; };
+
+// a label's CEL source -> LabelExpr; NoExposition outside the supported subset
+LabelExpr label_expr(const std::string& metric, const std::string& name, const std::string& src) {
+  LabelExpr L;
+  L.name = name;
+  L.src = src;
+  const std::string who = "metric '" + metric + "' label '" + name + "'";
+  kwkcel::NP n;
+  try {
+    n = kwkcel::parse(src);
+  } catch (const std::exception& e) {
+    throw NoExposition(who + ": CEL syntax error in '" + src + "': " + e.what());
+  }
+  if (n->k == kwkcel::Node::LIT && n->lit.t == kwkcel::Value::STR) {
+    L.lit = true;
+    L.value = n->lit.s;
+    return L;
+  }
+  std::vector<std::string> rev;
+  while (n->k == kwkcel::Node::SELECT) {
+    rev.push_back(n->name);
+    n = n->kids[0];
+  }
+  if (n->k != kwkcel::Node::IDENT || rev.empty() || (n->name != "node" && n->name != "pod" && n->name != "container"))
+    throw NoExposition(who + ": '" + src + "' is neither a string literal nor a field selection from node / pod / container");
+  L.root = n->name == "node" ? 0 : n->name == "pod" ? 1 : 2;
+  L.path.assign(rev.rbegin(), rev.rend());
+  return L;
+}
+
+std::string escape_help(const std::string& v) {  // _escape_help
+  std::string o;
+  for (char c : v) {
+    if (c == '\\') o += "\\\\";
+    else if (c == '\n') o += "\\n";
+    else o += c;
+  }
+  return o;
+}
+
+void build_exposition(kwk_metric_set& M) {
+  try {
+    std::vector<const MetricCfg*> order;
+    for (const MetricCfg& c : M.cfgs) {
+      if (c.kind == "histogram") throw NoExposition("metric '" + c.name + "' is a histogram: no device exposition");
+      if (!c.device) throw NoExposition("metric '" + c.name + "' is host-evaluated: no device exposition");
+      order.push_back(&c);
+      M.metric_dims.push_back(c.dim);
+    }
+    std::stable_sort(order.begin(), order.end(), [](const MetricCfg* a, const MetricCfg* b) { return a->name < b->name; });
+    std::vector<std::string> group_ids;
+    for (const MetricCfg* c : order) {
+      std::vector<LabelExpr> ls;
+      std::string id = std::to_string(c->dim);
+      for (const auto& l : c->labels) {
+        ls.push_back(label_expr(c->name, l.first, l.second));
+        id += '\0' + l.first + '\0' + l.second;
+      }
+      size_t g = 0;
+      while (g < group_ids.size() && group_ids[g] != id) ++g;
+      if (g == group_ids.size()) {
+        group_ids.push_back(id);
+        M.groups.push_back(kwk_expo_group{c->dim, (uint32_t)ls.size()});
+        M.group_labels.push_back(std::move(ls));
+      }
+      kwk_expo_family f{};
+      f.name_off = (uint32_t)M.lits.size();
+      f.name_len = (uint32_t)c->name.size();
+      M.lits += c->name;
+      std::string help = c->help;
+      while (!help.empty() && help.back() == '\n') help.pop_back();  // m.help.rstrip("\n")
+      const std::string header = "# HELP " + c->name + " " + escape_help(help) + "\n# TYPE " + c->name + " " + c->kind + "\n";
+      f.header_off = (uint32_t)M.lits.size();
+      f.header_len = (uint32_t)header.size();
+      M.lits += header;
+      f.metric = c->index;
+      f.dimension = c->dim;
+      f.group = (uint32_t)g;
+      M.families.push_back(f);
+    }
+  } catch (const NoExposition& e) {
+    M.expo_status = KWK_ENOLOWER;
+    M.expo_err = e.what();
+    M.families.clear();
+    M.groups.clear();
+    M.group_labels.clear();
+    M.lits.clear();
+  }
+}
+
+struct BadObject : std::runtime_error { using std::runtime_error::runtime_error; };
+
+bool parse_json(const char* text, JV& out) {
+  kwkjson::Parser p{text, text + strlen(text)};
+  if (!p.value(out)) return false;
+  p.ws();
+  return p.p == p.e;
+}
 
 void compile(kwk_metric_set& M, const JV& cr) {
   if (cr.t != JV::OBJ) throw BadCR("a Metric object");
@@ -197,6 +325,16 @@ void compile(kwk_metric_set& M, const JV& cr) {
       put_ops(M.ops, prog);
     }
     if (!device) host.push_back(name);
+    {
+      MetricCfg c;
+      c.name = name; c.help = help; c.kind = kind; c.dim = dim; c.index = index; c.device = device;
+      if (const JV* ls = m.get("labels"); ls && ls->t == JV::ARR)
+        for (size_t j = 0; j < ls->a.size(); ++j) {
+          const std::string lw = where + ".labels[" + std::to_string(j) + "]";
+          c.labels.emplace_back(str_field(ls->a[j], "name", "", lw), str_field(ls->a[j], "value", "", lw));
+        }
+      M.cfgs.push_back(std::move(c));
+    }
     if (i) d += ",";
     d += "{\"name\":";
     kwkhost::esc(d, name);
@@ -214,6 +352,7 @@ void compile(kwk_metric_set& M, const JV& cr) {
   }
   d += "]}";
   M.describe = std::move(d);
+  build_exposition(M);
 }
 
 }  // namespace
@@ -276,6 +415,94 @@ kwk_status kwk_metric_set_describe(const kwk_metric_set* m, const char** json) {
   if (!m || !json) return fail(KWK_EINVAL, "null argument");
   *json = m->describe.c_str();
   return KWK_OK;
+}
+
+kwk_status kwk_metric_set_exposition(const kwk_metric_set* m, kwk_expo_program* out) {
+  if (!m || !out) return fail(KWK_EINVAL, "null argument");
+  if (m->expo_status != KWK_OK) return fail(m->expo_status, m->expo_err);
+  out->n_families = (uint32_t)m->families.size();
+  out->n_groups = (uint32_t)m->groups.size();
+  out->n_metrics = (uint32_t)m->metric_dims.size();
+  out->n_lit_bytes = (uint32_t)m->lits.size();
+  out->families = m->families.data();
+  out->groups = m->groups.data();
+  out->metric_dimension = m->metric_dims.data();
+  out->lits = m->lits.data();
+  return KWK_OK;
+}
+
+kwk_status kwk_metric_labels_render(const kwk_metric_set* m, uint32_t group, const char* node_json, const char* pod_json,
+                                    uint32_t container_index, char* block, uint32_t block_cap, uint32_t* block_len,
+                                    char* key, uint32_t key_cap, uint32_t* key_len) {
+  if (!m || !block_len || !key_len || (block_cap && !block) || (key_cap && !key)) return fail(KWK_EINVAL, "null argument");
+  if (m->expo_status != KWK_OK) return fail(m->expo_status, m->expo_err);
+  if (group >= m->groups.size()) return fail(KWK_EINVAL, "label group out of range");
+  try {
+    const std::vector<LabelExpr>& ls = m->group_labels[group];
+    JV node, pod;
+    const JV* roots[3] = {nullptr, nullptr, nullptr};
+    bool need[3] = {false, false, false};
+    for (const LabelExpr& l : ls)
+      if (!l.lit) need[l.root] = true;
+    if (need[0]) {
+      if (!node_json) throw BadObject("the labels read node: node_json is required");
+      if (!parse_json(node_json, node)) throw BadObject("node: malformed JSON");
+      roots[0] = &node;
+    }
+    if (need[1] || need[2]) {
+      if (!pod_json) throw BadObject("the labels read pod / container: pod_json is required");
+      if (!parse_json(pod_json, pod)) throw BadObject("pod: malformed JSON");
+      roots[1] = &pod;
+    }
+    if (need[2]) {
+      const JV* spec = field(pod, "spec");
+      const JV* cs = spec ? field(*spec, "containers") : nullptr;
+      if (!cs || cs->t != JV::ARR || container_index >= cs->a.size())
+        throw BadObject("pod.spec.containers[" + std::to_string(container_index) + "]: no such container");
+      roots[2] = &cs->a[container_index];
+    }
+    std::string b, k;
+    static const char* kRoots[] = {"node", "pod", "container"};
+    for (size_t i = 0; i < ls.size(); ++i) {
+      const LabelExpr& l = ls[i];
+      const std::string* val = &l.value;
+      if (!l.lit) {
+        const JV* v = roots[l.root];
+        std::string at = kRoots[l.root];
+        for (const std::string& f : l.path) {
+          const JV* nx = field(*v, f.c_str());
+          if (!nx) throw BadObject("label '" + l.name + "': " + at + " has no key '" + f + "'");
+          at += "." + f;
+          v = nx;
+        }
+        if (v->t != JV::STR) throw BadObject("label '" + l.name + "': " + at + " is not a string");
+        val = &v->s;
+      }
+      b += i ? "," : "{";
+      b += l.name + "=\"";
+      for (char c : *val) {
+        if (c == '\\') b += "\\\\";
+        else if (c == '\n') b += "\\n";
+        else if (c == '"') b += "\\\"";
+        else b += c;
+      }
+      b += '"';
+      for (char c : *val) {
+        if (c == 0 || c == 1) { k += '\x01'; k += (char)(c + 1); }
+        else k += c;
+      }
+      k += '\0';
+    }
+    if (!ls.empty()) b += "}";
+    *block_len = (uint32_t)b.size();
+    *key_len = (uint32_t)k.size();
+    if (b.size() > block_cap || k.size() > key_cap) return fail(KWK_ECAP, "label buffers too small");
+    if (!b.empty()) memcpy(block, b.data(), b.size());
+    if (!k.empty()) memcpy(key, k.data(), k.size());
+    return KWK_OK;
+  } catch (const std::exception& e) {
+    return fail(KWK_EINVAL, e.what());
+  }
 }
 
 kwk_status kwk_cel_lower(const char* expr, uint32_t dimension, kwk_metric_op* out, uint32_t cap, uint32_t* n_ops) {

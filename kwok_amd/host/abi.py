@@ -187,7 +187,7 @@ EXPORTS = [
     "kwk_metrics_load", "kwk_metrics_inputs", "kwk_metrics_eval", "kwk_aggregate", "kwk_aggregate_read",
     "kwk_last_sweep", "kwk_tick_bind", "kwk_tick", "kwk_tick_n", "kwk_histograms_load", "kwk_histograms_eval",
     "kwk_fired_fetch", "kwk_fired_fetch_wait", "kwk_fired_keep",
-    "kwk_metrics_eval_device", "kwk_histograms_eval_device",
+    "kwk_metrics_eval_device", "kwk_histograms_eval_device", "kwk_metrics_series_device",
 ]
 ABI_VERSION = 3  # KWK_ABI_VERSION of include/kwok_engine.h: the library must match the structs above
 TICK_COMPACT = 1 << 0  # KWK_TICK_COMPACT
@@ -237,6 +237,8 @@ def lib():
     L.kwk_metrics_eval.argtypes = [C.c_void_p, C.c_int64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, _p(C.c_uint64)]
     L.kwk_metrics_eval_device.argtypes = [C.c_void_p, C.c_int64, C.c_uint32, C.c_uint32, _p(C.c_void_p),
                                           _p(C.c_uint64)]
+    L.kwk_metrics_series_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, _p(C.c_void_p), _p(C.c_void_p),
+                                            _p(C.c_void_p)]
     L.kwk_histograms_eval_device.argtypes = [C.c_void_p, C.c_int64, C.c_uint32, C.c_uint32, _p(C.c_void_p),
                                              _p(C.c_uint64)]
     L.kwk_histograms_load.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]

@@ -15,6 +15,10 @@ reported in ``MetricsProgram.host_metrics``, never a silent substitute for the d
 Histograms (metrics.go:133-160,356-462; histogram.go:81-164): every bucket's value is lowered
 the same way and kwk_histograms_eval returns, per series, the bucket counts histogram.Write
 would expose (cumulative counts of the visible bounds, +Inf, sample count and sum).
+
+For a CR of gauges / counters whose labels are literals or selected fields the text is also written
+on the device (host/expo.py, include/kwok_expo.h), byte-equal to ``exposition(scrape(..))`` here,
+which stays the cross-check and the path of every other CR.
 """
 from __future__ import annotations
 
@@ -71,9 +75,13 @@ def go_float(v: float) -> str:
     if v == 0:
         return "-0" if math.copysign(1.0, v) < 0 else "0"
     neg = v < 0
-    e = f"{abs(v):.17e}".partition("e")[2]  # the decimal exponent; the shortest digits from repr
-    digits = repr(abs(v)).split("e")[0].replace(".", "").lstrip("0").rstrip("0") or "0"
-    exp = int(e)
+    # the shortest digits and their decimal exponent, both from repr (the exponent of the exact
+    # value can differ: 1e23 is 9.99...e22 exactly and prints 1e+23)
+    m, _, e = repr(abs(v)).partition("e")
+    ip, _, fp = m.partition(".")
+    lead = len(ip + fp) - len((ip + fp).lstrip("0"))
+    digits = (ip + fp).strip("0") or "0"
+    exp = int(e or 0) + len(ip) - 1 - lead
     if exp < -4 or exp >= 6:
         out = digits[0] + ("." + digits[1:] if len(digits) > 1 else "") + f"e{'-' if exp < 0 else '+'}{abs(exp):02d}"
     elif exp >= 0:

@@ -20,6 +20,23 @@ KWK_ENOLOWER = -5
 _bound = False
 
 
+class ExpoFamily(C.Structure):
+    _fields_ = [("name_off", C.c_uint32), ("name_len", C.c_uint32), ("header_off", C.c_uint32),
+                ("header_len", C.c_uint32), ("metric", C.c_uint32), ("dimension", C.c_uint32), ("group", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class ExpoGroup(C.Structure):
+    _fields_ = [("dimension", C.c_uint32), ("n_labels", C.c_uint32)]
+
+
+class ExpoProgramStruct(C.Structure):
+    """kwk_expo_program (include/kwok_metrics.h)."""
+    _fields_ = [("n_families", C.c_uint32), ("n_groups", C.c_uint32), ("n_metrics", C.c_uint32),
+                ("n_lit_bytes", C.c_uint32), ("families", C.POINTER(ExpoFamily)), ("groups", C.POINTER(ExpoGroup)),
+                ("metric_dimension", C.POINTER(C.c_uint32)), ("lits", C.c_void_p)]
+
+
 def lib():
     global _bound
     L = _compiler_lib()
@@ -35,14 +52,28 @@ def lib():
                                                 C.POINTER(C.c_uint32), C.POINTER(C.c_void_p)]
         L.kwk_metric_set_describe.argtypes = [C.c_void_p, C.POINTER(C.c_char_p)]
         L.kwk_cel_lower.argtypes = [C.c_char_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+        L.kwk_metric_set_exposition.argtypes = [C.c_void_p, C.POINTER(ExpoProgramStruct)]
+        L.kwk_metric_labels_render.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_char_p, C.c_uint32, C.c_void_p,
+                                               C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p, C.c_uint32,
+                                               C.POINTER(C.c_uint32)]
         for n in ("kwk_compile_metrics", "kwk_metric_set_destroy", "kwk_metric_set_programs",
-                  "kwk_metric_set_histograms", "kwk_metric_set_describe", "kwk_cel_lower"):
+                  "kwk_metric_set_histograms", "kwk_metric_set_describe", "kwk_cel_lower",
+                  "kwk_metric_set_exposition", "kwk_metric_labels_render"):
             getattr(L, n).restype = C.c_int32
         _bound = True
     return L
 
 
 class MetricCompileError(ValueError):
+    pass
+
+
+class NoExposition(MetricCompileError):
+    """The Metric CR has no device exposition program (a histogram, a host-evaluated metric or a
+    label outside the supported subset)."""
+
+
+class LabelRenderError(ValueError):
     pass
 
 
@@ -123,6 +154,39 @@ class NativeMetricSet:
         return (C.string_at(d, n * C.sizeof(abi.HistogramDesc)) if n else b"",
                 C.string_at(b, nb * C.sizeof(abi.MetricBucket)) if nb else b"",
                 C.string_at(o, no * C.sizeof(abi.MetricOp)) if no else b"")
+
+    def exposition_program(self) -> ExpoProgramStruct:
+        """kwk_metric_set_exposition: the program of the device text writer (arrays owned by the
+        set); NoExposition (KWK_ENOLOWER) names the metric that keeps the text on the host."""
+        prog = ExpoProgramStruct()
+        L = lib()
+        st = L.kwk_metric_set_exposition(self.h, C.byref(prog))
+        if st != 0:
+            msg = L.kwk_metric_set_last_error(None).decode(errors="replace")
+            raise (NoExposition if st == KWK_ENOLOWER else MetricCompileError)(msg)
+        return prog
+
+    def labels_render(self, group: int, node, pod, container_index: int = 0) -> Tuple[bytes, bytes]:
+        """kwk_metric_labels_render: (label block, sort key) of one object of `group`; node / pod
+        are JSON objects (dict), JSON text (bytes) or None.  LabelRenderError (KWK_EINVAL) names
+        the object and label whose selection fails."""
+        def text(o):
+            return None if o is None else o if isinstance(o, bytes) else json.dumps(o).encode()
+        nj, pj = text(node), text(pod)
+        L = lib()
+        bl, kl = C.c_uint32(), C.c_uint32()
+        cap = 256
+        while True:
+            b, k = C.create_string_buffer(cap), C.create_string_buffer(cap)
+            st = L.kwk_metric_labels_render(self.h, group, nj, pj, container_index, b, cap, C.byref(bl), k, cap,
+                                            C.byref(kl))
+            if st == abi.KWK_ECAP:
+                cap = max(bl.value, kl.value)
+                continue
+            if st != 0:
+                msg = L.kwk_metric_set_last_error(None).decode(errors="replace")
+                raise (NoExposition if st == KWK_ENOLOWER else LabelRenderError)(msg)
+            return b.raw[:bl.value], k.raw[:kl.value]
 
     def load(self, pods_engine):
         """kwk_metrics_load (+ kwk_histograms_load when the CR has histograms) from the set's arrays."""
