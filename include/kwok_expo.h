@@ -11,11 +11,16 @@
  * (kwk_metrics_eval_device) and writes, for every node of the range, the text
  * MetricsProgram.exposition(MetricsProgram.scrape(..)) gives for that node alone, byte for byte:
  * every family's HELP / TYPE lines (also when the node has no series of it), the series of live
- * pod slots in label order, the values as strconv.AppendFloat(v, 'g', -1, 64).
+ * pod slots in label order, the values as strconv.AppendFloat(v, 'g', -1, 64).  A histogram family
+ * (a set compiled with KWK_METRICS_EXPO_HISTOGRAMS, a writer made by kwk_expo_create_hist) writes
+ * what expfmt writes for histogram.Write's dto: per series the _bucket lines of the visible bounds
+ * and +Inf, then _sum and _count, from the record kwk_histograms_eval_device leaves on the device
+ * (counts as float64(uint64); a dead pod slot, by the alive bits, has no lines).
  *
  * Three launches per scrape on the engine's stream, no host round trip between them:
  *   lengths   a workgroup per node: formats every live value once (32 bytes of device memory per
- *             series of the range), the bytes of the node's text
+ *             series of the range, and per record word of a histogram series), the bytes of the
+ *             node's text
  *   scan      exclusive scan of the node totals into 64-bit offsets, the grand total
  *   write     a workgroup per node again: every line at its scanned offset
  * Output room is reserved by the caller (kwk_expo_reserve); a scrape whose text does not fit
@@ -42,6 +47,13 @@ const char* kwk_expo_last_error(const kwk_expo* ex);
  * program is copied.  Rows of a label group are nodes, pod slots or containers
  * (kwk_usage_read_containers order) by the group's dimension. */
 kwk_status kwk_expo_create(kwk_engine* pods, uint32_t n_nodes, const kwk_expo_program* prog, kwk_expo** out);
+/* the same for a program with histogram families (kind code 1; also after kwk_histograms_load of
+ * the same CR), with their tables (kwk_metric_set_exposition_histograms; copied).  kwk_expo_create
+ * given such a program returns KWK_EINVAL naming the family.  Every other call is the same for
+ * both; a scrape also runs kwk_histograms_eval_device and returns KWK_ESTATE when the engine's
+ * record words are not the program's (every histogram: its series x (n_visible + 3)). */
+kwk_status kwk_expo_create_hist(kwk_engine* pods, uint32_t n_nodes, const kwk_expo_program* prog,
+                                const kwk_expo_hist_program* hist_prog, kwk_expo** out);
 kwk_status kwk_expo_destroy(kwk_expo* ex);
 /* rows [first, first + n) of `group`: row i's label block is blocks[block_offsets[i] ..
  * block_offsets[i + 1]) and its sort key keys[key_offsets[i] .. key_offsets[i + 1])
@@ -51,7 +63,8 @@ kwk_status kwk_expo_destroy(kwk_expo* ex);
  * kwk_usage_mixed that changes the pod or container count, commit once (it re-reads the layout and
  * keeps the rows set so far), then set the new rows and commit again.  Rows of dead slots need not
  * be set; a scrape that meets a live series of a labelled group whose row was never set writes
- * nothing and kwk_expo_result returns KWK_ESTATE with their count. */
+ * nothing and kwk_expo_result returns KWK_ESTATE with their count (a histogram series counts once,
+ * not once per line). */
 kwk_status kwk_expo_set_labels(kwk_expo* ex, uint32_t group, uint32_t first, uint32_t n, const uint32_t* block_offsets,
                                const char* blocks, const uint32_t* key_offsets, const char* keys);
 /* stable-sorts every node's rows of each group by key (bytewise; ties keep row order: the order of
@@ -61,7 +74,8 @@ kwk_status kwk_expo_commit(kwk_expo* ex);
 /* output room: text bytes one scrape may produce */
 kwk_status kwk_expo_reserve(kwk_expo* ex, uint64_t max_bytes);
 /* enqueue one scrape of nodes [node_first, node_first + n_nodes) at now_ns, after the caller's
- * kwk_usage(now_ns): kwk_metrics_eval_device, kwk_metrics_series_device, then the three kernels */
+ * kwk_usage(now_ns): kwk_metrics_eval_device, kwk_metrics_series_device (kwk_histograms_eval_device
+ * when the program has histogram families), then the three kernels */
 kwk_status kwk_expo_scrape(kwk_expo* ex, int64_t now_ns, uint32_t node_first, uint32_t n_nodes);
 /* synchronise; the last scrape's text size.  KWK_ECAP when it exceeds the reservation: nothing was
  * written — reserve more and scrape again.  KWK_ESTATE: live series without a label row (above) */

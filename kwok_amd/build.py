@@ -27,7 +27,7 @@ COMPILER_SRC = [os.path.join(PKG, "csrc", "compiler.cpp"), os.path.join(PKG, "cs
 COMPILER_HDR = [os.path.join(ROOT, "include", "kwok_compiler.h"), os.path.join(ROOT, "include", "kwok_metrics.h"),
                 os.path.join(ROOT, "include", "kwok_engine.h"), DOM_HDR] + \
     [os.path.join(PKG, "csrc", h) for h in ("host_common.hpp", "gotpl.hpp", "patchtpl.hpp", "nextstate.hpp", "labelsel.hpp",
-                                            "celc.hpp")]
+                                            "celc.hpp", "f64fmt.hpp", "f64fmt_tables.hpp")]
 COMPILER_OUT = os.path.join(PKG, "lib", "libkwok_compiler.so")
 COMM_SRC = [os.path.join(PKG, "csrc", "comm.cpp")]
 COMM_HDR = [os.path.join(ROOT, "include", "kwok_comm.h"), os.path.join(ROOT, "include", "kwok_engine.h")]

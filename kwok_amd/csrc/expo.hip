@@ -6,26 +6,37 @@
 // blocks are rendered once per object on the host (kwk_metric_labels_render), sorted once per node
 // (kwk_expo_commit), and only the values change per scrape.
 //
-// Three launches per scrape (no inter-workgroup waiting, no host round trip):
-//   expo_node_kernel<W, false>  a workgroup of W lanes per node, family-major, series in the committed
-//                               order: line = name + block + ' ' + value + '\n' (dead pod slots: none).
-//                               Formats every live value once (f64fmt.hpp) into a 32-byte stash slot
-//                               (24 bytes + length) and sums the node's bytes with its HELP / TYPE lines
-//   expo_scan_kernel            one workgroup: exclusive scan of the node totals into 64-bit offsets,
-//                               the grand total
-//   expo_node_kernel<W, true>   the same walk; the lanes take a family's lines W at a time and a block scan
-//                               of their lengths gives each its offset in the node.  A wave's 64 lines are
-//                               one contiguous span: each lane assembles its line in LDS (8-byte words,
-//                               read from the sources as aligned 8-byte words), at the span's own
-//                               misalignment, and the wave stores the span as 16-byte vectors (bytes at
-//                               the two ends).  A span longer than the LDS window is written by its
-//                               lanes directly.  The kernel returns at once when the scanned total exceeds
-//                               the reservation, and every store is bounded by the node's scanned range.
+// Three launches per scrape (no inter-workgroup waiting, no host round trip); the third template
+// parameter is whether the program has histogram families (below):
+//   expo_node_kernel<W, false, H> a workgroup of W lanes per node, family-major, series in the committed
+//                                 order: line = name + block + ' ' + value + '\n' (dead pod slots: none).
+//                                 Formats every live value once (f64fmt.hpp) into a 32-byte stash slot
+//                                 (24 bytes + length) and sums the node's bytes with its HELP / TYPE lines
+//   expo_scan_kernel              one workgroup: exclusive scan of the node totals into 64-bit offsets,
+//                                 the grand total
+//   expo_node_kernel<W, true, H>  the same walk; the lanes take a family's lines W at a time and a block scan
+//                                 of their lengths gives each its offset in the node.  A wave's 64 lines are
+//                                 one contiguous span: each lane assembles its line in LDS (8-byte words,
+//                                 read from the sources as aligned 8-byte words), at the span's own
+//                                 misalignment, and the wave stores the span as 16-byte vectors (bytes at
+//                                 the two ends).  A span longer than the LDS window is written by its
+//                                 lanes directly.  The kernel returns at once when the scanned total exceeds
+//                                 the reservation, and every store is bounded by the node's scanned range.
 // W = 64 (one wave per node) up to kWidePods pods per node, 256 above.
 // Both choices were measured against their alternatives — lanes storing their lines directly, and
 // formatting the value again in the write pass instead of the stash — at the C4 size (DESIGN.md
 // "Device metric exposition", `ab_c4` in profiles/r7/expo_bench.json): this pair is the fastest of
 // the four.
+//
+// Histogram families (kwk_expo_create_hist; kwk_expo_hist_program in kwok_metrics.h): a series is
+// n_visible + 3 lines, so a family of a node is count x (n_visible + 3) lines and the lanes walk that
+// line index space W at a time: lane L -> series L / lines (its row through the group's permutation),
+// line L % lines, whose prefix and tail come from the per-line table and whose value is one word of the
+// engine's histogram record (kwk_histograms_eval_device), float64(uint64) for a count, the float64
+// bits for the sum.  Each printed word is formatted once, by the lengths pass, into the stash region
+// after the scalars'.  The block scan, the LDS staging and the bounded stores are the scalar
+// families'.  Only expo_node_kernel<W, ., true> knows any of this: a program without histogram
+// families launches <W, ., false>, whose code has no histogram state.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -64,8 +75,13 @@ constexpr uint32_t kWidePods = 256;  // pods per node (mean) above which a node 
 struct DevFamily {
   uint32_t name_off, name_len, header_off, header_len;
   uint32_t dim, group;
-  uint32_t before[3];  // gauges / counters of each dimension before this family's in CR order (its value offset)
-  uint32_t reserved;
+  uint32_t before[3];  // gauges / counters of each dimension before this family's in CR order (its value offset);
+                       // a histogram family: record words per series of the histograms before its own
+  uint32_t hist;       // 0: a gauge / counter; else 1 + its index in ExpoArgs.hist
+};
+
+struct DevHist {
+  uint32_t nvis, line0;  // n_visible; its n_visible + 3 entries of ExpoArgs.hlines
 };
 
 struct DevGroup {
@@ -90,6 +106,11 @@ struct ExpoArgs {
   char* out;
   unsigned long long cap;
   uint4* stash;  // 32 bytes per value: its formatted bytes and their count (lengths pass -> write pass)
+  // histogram families (expo_node_kernel<., ., true> only)
+  const DevHist* hist;
+  const kwk_expo_hist_line* hlines;
+  const unsigned long long* hvals;  // the engine's histogram records
+  unsigned long long n_vals;        // the scalars' values: the histogram words' stash slots follow theirs
 };
 
 constexpr uint32_t kLdsWave = 12288;  // LDS window of one wave's 64 lines (C4 lines: ~105 bytes)
@@ -212,7 +233,7 @@ __device__ __forceinline__ uint32_t block_excl(uint32_t len, uint32_t* s_wave, u
   return base + incl - len;
 }
 
-template <uint32_t W, bool kWrite>
+template <uint32_t W, bool kWrite, bool kHist>
 __global__ __launch_bounds__(W) void expo_node_kernel(ExpoArgs a) {
   __shared__ __attribute__((aligned(16))) char s_stage[kWrite ? (W / 64) * kLdsWave : 16];
   __shared__ uint32_t s_wave[W / 64];
@@ -242,14 +263,32 @@ __global__ __launch_bounds__(W) void expo_node_kernel(ExpoArgs a) {
     const uint32_t first = F.dim == KWK_METRIC_DIM_NODE ? node : F.dim == KWK_METRIC_DIM_POD ? pb : cb;
     const uint32_t count = F.dim == KWK_METRIC_DIM_NODE ? 1u : F.dim == KWK_METRIC_DIM_POD ? pe - pb : ce - cb;
     const uint32_t base = F.dim == KWK_METRIC_DIM_NODE ? a.n0 : F.dim == KWK_METRIC_DIM_POD ? a.p0 : a.c0;
-    const double* vals = a.vals + ((unsigned long long)F.before[0] * a.n_nodes + (unsigned long long)F.before[1] * (a.p1 - a.p0) +
-                                   (unsigned long long)F.before[2] * (a.c1 - a.c0));
-    for (uint32_t s0 = 0; s0 < count; s0 += W) {
-      const uint32_t s = s0 + tid;
+    const unsigned long long voff = (unsigned long long)F.before[0] * a.n_nodes + (unsigned long long)F.before[1] * (a.p1 - a.p0) +
+                                    (unsigned long long)F.before[2] * (a.c1 - a.c0);
+    const double* vals = a.vals + voff;
+    // a histogram family: `lines` lines per series, the lanes walk count x lines
+    const bool hist = kHist && F.hist != 0;
+    uint32_t lines = 1, nvis = 0, line0 = 0;
+    if (hist) {
+      const DevHist H = a.hist[F.hist - 1];
+      nvis = H.nvis;
+      line0 = H.line0;
+      lines = nvis + 3;
+    }
+    const uint32_t n_lines = count * lines;  // fits: kwk_expo_commit bounds a node's rows
+    for (uint32_t s0 = 0; s0 < n_lines; s0 += W) {
+      uint32_t s = s0 + tid, k = 0;
+      const bool mine = s < n_lines;
+      if (hist) {
+        const uint32_t q = s / lines;
+        k = s - q * lines;
+        s = q;
+      }
       uint32_t len = 0, row = 0, bo = 0, bl = 0;
+      uint32_t po = F.name_off, pl = F.name_len, to = 0, tl = 0;  // the line's prefix and tail in lits
       double v = 0.0;
       RegSink rs;
-      if (s < count) {
+      if (mine) {
         row = G.perm ? G.perm[first + s] : first + s;
         bool alive = true;
         if (F.dim != KWK_METRIC_DIM_NODE) {
@@ -257,14 +296,33 @@ __global__ __launch_bounds__(W) void expo_node_kernel(ExpoArgs a) {
           alive = (a.alive[pod >> 5] >> (pod & 31u)) & 1u;
         }
         if (alive) {
-          v = vals[row - base];
           if (G.blk_off) {
             bo = G.blk_off[row];
             bl = G.blk_off[row + 1] - bo;
-            if (!kWrite && bl == 0) atomicAdd(&a.total[1], 1ull);  // a rendered block is never empty ("{..}")
+            // a rendered block is never empty ("{..}"); a histogram series counts once, not per line
+            if (!kWrite && bl == 0 && k == 0) atomicAdd(&a.total[1], 1ull);
+          }
+          size_t slot = (size_t)voff + (row - base);
+          if (hist) {
+            const kwk_expo_hist_line ln = a.hlines[line0 + k];
+            po = ln.prefix_off;
+            pl = ln.prefix_len;
+            to = ln.tail_off;
+            tl = ln.tail_len;
+            if (bl) --bl;  // the block without its closing brace: the tail closes it
+            // text order buckets, +Inf, _sum, _count; record order counts, +Inf, count, sum
+            const uint32_t w = k <= nvis ? k : k == nvis + 1 ? nvis + 2 : nvis + 1;
+            const size_t rec = (size_t)voff + (size_t)(row - base) * lines;
+            slot = (size_t)a.n_vals + rec + k;
+            if (!kWrite) {
+              const unsigned long long x = a.hvals[rec + w];
+              v = w == nvis + 2 ? __longlong_as_double((long long)x) : (double)x;  // float64(uint64): nearest even
+            }
+          } else {
+            v = vals[row - base];
           }
           // the value's text: formatted once, by the lengths pass
-          uint4* st = a.stash + 2 * (size_t)((vals - a.vals) + (row - base));
+          uint4* st = a.stash + 2 * slot;
           if (!kWrite) {
             kwkf64::format(v, rs);
             st[0] = make_uint4((uint32_t)rs.w0, (uint32_t)(rs.w0 >> 32), (uint32_t)rs.w1, (uint32_t)(rs.w1 >> 32));
@@ -276,7 +334,7 @@ __global__ __launch_bounds__(W) void expo_node_kernel(ExpoArgs a) {
             rs.w2 = y.x | (uint64_t)y.y << 32;
             rs.n = y.z < (uint32_t)kwkf64::kMaxBytes ? y.z : (uint32_t)kwkf64::kMaxBytes;
           }
-          len = F.name_len + bl + 2u + rs.n;
+          len = pl + bl + tl + 2u + rs.n;
         }
       }
       if (!kWrite) {
@@ -293,8 +351,9 @@ __global__ __launch_bounds__(W) void expo_node_kernel(ExpoArgs a) {
         const bool staged = mis + wtotal <= kLdsWave;
         char* stage = s_stage + (tid >> 6) * kLdsWave;
         auto line = [&](auto& o) {
-          o.run(a.lits + F.name_off, F.name_len);
+          o.run(a.lits + po, pl);
           o.run(G.blk + bo, bl);
+          if (kHist) o.run(a.lits + to, tl);
           o.put(' ');
           o.push(rs.w0, rs.n < 8 ? rs.n : 8u);
           if (rs.n > 8) o.push(rs.w1, rs.n < 16 ? rs.n - 8 : 8u);
@@ -408,9 +467,13 @@ struct kwk_expo {
   uint4* d_stash = nullptr;
   uint64_t stash_cap = 0;
   std::vector<DevFamily> fam;
+  std::vector<DevHist> hist;  // of the histogram families' histograms (empty: a scalar-only program)
+  uint32_t max_lines = 1;     // most lines of a series
   std::vector<Group> groups;
   std::vector<uint32_t> h_node_ptr, h_cptr;
   DevFamily* d_fam = nullptr;
+  DevHist* d_hist = nullptr;
+  kwk_expo_hist_line* d_hlines = nullptr;
   DevGroup* d_grp = nullptr;
   char* d_lits = nullptr;
   uint32_t* d_pod_of = nullptr;
@@ -432,7 +495,7 @@ struct kwk_expo {
       for (void* p : {(void*)g.d_blk_off, (void*)g.d_blk, (void*)g.d_perm})
         if (p) hipFree(p);
     for (void* p : {(void*)d_fam, (void*)d_grp, (void*)d_lits, (void*)d_pod_of, (void*)d_node_bytes, (void*)d_offsets,
-                    (void*)d_total, (void*)d_out, (void*)d_stash})
+                    (void*)d_total, (void*)d_out, (void*)d_stash, (void*)d_hist, (void*)d_hlines})
       if (p) hipFree(p);
     for (hipEvent_t e : ev)
       if (e) hipEventDestroy(e);
@@ -505,23 +568,63 @@ const char* kwk_expo_last_error(const kwk_expo* ex) { return ex ? ex->err.c_str(
 
 uint32_t kwk_expo_format_f64(double v, char out[24]) { return kwkf64::format_f64(v, out); }
 
-kwk_status kwk_expo_create(kwk_engine* pods, uint32_t n_nodes, const kwk_expo_program* prog, kwk_expo** out) {
+}  // extern "C"
+
+namespace {
+
+// kwk_expo_create (hp = NULL: a histogram family is refused) and kwk_expo_create_hist
+kwk_status create(kwk_engine* pods, uint32_t n_nodes, const kwk_expo_program* prog, const kwk_expo_hist_program* hp,
+                  kwk_expo** out) {
   ErrScope es_(nullptr);
   if (!pods || !prog || !out) return fail(KWK_EINVAL, "null argument");
   if ((prog->n_families && (!prog->families || !prog->lits)) || (prog->n_groups && !prog->groups) ||
       (prog->n_metrics && !prog->metric_dimension))
     return fail(KWK_EINVAL, "exposition program: null array");
+  if (hp && ((hp->n_hists && !hp->hists) || (hp->n_lines && !hp->lines)))
+    return fail(KWK_EINVAL, "histogram exposition program: null array");
   std::vector<DevFamily> fam;
+  std::vector<DevHist> hist;
+  uint32_t max_lines = 1;
   for (uint32_t f = 0; f < prog->n_families; ++f) {
     const kwk_expo_family& F = prog->families[f];
     if ((uint64_t)F.name_off + F.name_len > prog->n_lit_bytes || (uint64_t)F.header_off + F.header_len > prog->n_lit_bytes)
       return fail(KWK_EINVAL, "exposition program: family " + std::to_string(f) + " bytes beyond lits");
-    if (F.group >= prog->n_groups || F.metric >= prog->n_metrics || F.dimension > KWK_METRIC_DIM_CONTAINER ||
-        prog->groups[F.group].dimension != F.dimension || prog->metric_dimension[F.metric] != F.dimension)
-      return fail(KWK_EINVAL, "exposition program: family " + std::to_string(f) + " group / metric / dimension");
+    const std::string name(prog->lits + F.name_off, F.name_len);
+    if (F.reserved > KWK_EXPO_KIND_HISTOGRAM)
+      return fail(KWK_EINVAL, "exposition program: family " + std::to_string(f) + " ('" + name + "') has an unknown kind code");
     DevFamily d{};
     d.name_off = F.name_off; d.name_len = F.name_len; d.header_off = F.header_off; d.header_len = F.header_len;
     d.dim = F.dimension; d.group = F.group;
+    if (F.reserved == KWK_EXPO_KIND_HISTOGRAM) {
+      if (!hp)
+        return fail(KWK_EINVAL, "exposition program: family " + std::to_string(f) + " ('" + name + "') is a histogram: "
+                                "kwk_expo_create_hist takes its tables (kwk_metric_set_exposition_histograms)");
+      if (F.group >= prog->n_groups || F.metric >= hp->n_hists || F.dimension > KWK_METRIC_DIM_CONTAINER ||
+          prog->groups[F.group].dimension != F.dimension || hp->hists[F.metric].dimension != F.dimension)
+        return fail(KWK_EINVAL, "exposition program: family " + std::to_string(f) + " group / histogram / dimension");
+      for (uint32_t h = 0; h <= F.metric; ++h) {
+        const kwk_expo_hist& H = hp->hists[h];
+        if (H.dimension > KWK_METRIC_DIM_CONTAINER || H.n_visible > 64 ||
+            (uint64_t)H.first_line + H.n_visible + 3 > hp->n_lines)
+          return fail(KWK_EINVAL, "histogram exposition program: histogram " + std::to_string(h) + " dimension / lines");
+        if (h < F.metric) d.before[H.dimension] += H.n_visible + 3;
+      }
+      const kwk_expo_hist& H = hp->hists[F.metric];
+      for (uint32_t k = 0; k < H.n_visible + 3; ++k) {
+        const kwk_expo_hist_line& l = hp->lines[H.first_line + k];
+        if ((uint64_t)l.prefix_off + l.prefix_len > prog->n_lit_bytes || (uint64_t)l.tail_off + l.tail_len > prog->n_lit_bytes)
+          return fail(KWK_EINVAL, "histogram exposition program: family '" + name + "' line " + std::to_string(k) +
+                                  " bytes beyond lits");
+      }
+      hist.push_back(DevHist{H.n_visible, H.first_line});
+      d.hist = (uint32_t)hist.size();
+      max_lines = std::max(max_lines, H.n_visible + 3);
+      fam.push_back(d);
+      continue;
+    }
+    if (F.group >= prog->n_groups || F.metric >= prog->n_metrics || F.dimension > KWK_METRIC_DIM_CONTAINER ||
+        prog->groups[F.group].dimension != F.dimension || prog->metric_dimension[F.metric] != F.dimension)
+      return fail(KWK_EINVAL, "exposition program: family " + std::to_string(f) + " group / metric / dimension");
     for (uint32_t m = 0; m < F.metric; ++m) {
       if (prog->metric_dimension[m] > KWK_METRIC_DIM_CONTAINER) return fail(KWK_EINVAL, "exposition program: metric dimension");
       ++d.before[prog->metric_dimension[m]];
@@ -535,6 +638,8 @@ kwk_status kwk_expo_create(kwk_engine* pods, uint32_t n_nodes, const kwk_expo_pr
   ex->stream = static_cast<hipStream_t>(s);
   ex->n_nodes = n_nodes;
   ex->fam = std::move(fam);
+  ex->hist = std::move(hist);
+  ex->max_lines = max_lines;
   ex->groups.resize(prog->n_groups);
   for (uint32_t g = 0; g < prog->n_groups; ++g) {
     ex->groups[g].dim = prog->groups[g].dimension;
@@ -547,6 +652,10 @@ kwk_status kwk_expo_create(kwk_engine* pods, uint32_t n_nodes, const kwk_expo_pr
     if (kwk_status st = replace(ex, &ex->d_fam, ex->fam.data(), ex->fam.size())) return st;
     const std::string lits = std::string(prog->lits, prog->n_lit_bytes) + std::string(8, '\0');  // read as 8-byte words
     if (kwk_status st = replace(ex, &ex->d_lits, lits.data(), lits.size())) return st;
+    if (!ex->hist.empty()) {
+      if (kwk_status st = replace(ex, &ex->d_hist, ex->hist.data(), ex->hist.size())) return st;
+      if (kwk_status st = replace(ex, &ex->d_hlines, hp->lines, (size_t)hp->n_lines)) return st;
+    }
     HIP_TRY(hipMalloc(&ex->d_total, 16));
     HIP_TRY(hipMemsetAsync(ex->d_total, 0, 16, ex->stream));
     for (hipEvent_t& e : ex->ev) HIP_TRY(hipEventCreate(&e));
@@ -558,6 +667,23 @@ kwk_status kwk_expo_create(kwk_engine* pods, uint32_t n_nodes, const kwk_expo_pr
   }
   *out = ex;
   return KWK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+kwk_status kwk_expo_create(kwk_engine* pods, uint32_t n_nodes, const kwk_expo_program* prog, kwk_expo** out) {
+  return create(pods, n_nodes, prog, nullptr, out);
+}
+
+kwk_status kwk_expo_create_hist(kwk_engine* pods, uint32_t n_nodes, const kwk_expo_program* prog,
+                                const kwk_expo_hist_program* hist_prog, kwk_expo** out) {
+  if (!hist_prog) {
+    ErrScope es_(nullptr);
+    return fail(KWK_EINVAL, "null argument");
+  }
+  return create(pods, n_nodes, prog, hist_prog, out);
 }
 
 kwk_status kwk_expo_destroy(kwk_expo* ex) {
@@ -592,6 +718,11 @@ kwk_status kwk_expo_commit(kwk_expo* ex) {
   if (kwk_status st = bind(ex)) return st;
   if (kwk_status st = refresh_layout(ex)) return st;
   HIP_TRY(hipStreamSynchronize(ex->stream));
+  // a node's family is walked as rows x lines of a series in 32 bits
+  for (uint32_t j = 0; j < ex->n_nodes; ++j)
+    if ((uint64_t)(ex->h_cptr[ex->h_node_ptr[j + 1]] - ex->h_cptr[ex->h_node_ptr[j]]) * ex->max_lines > 0xFFFFFFFFull ||
+        (uint64_t)(ex->h_node_ptr[j + 1] - ex->h_node_ptr[j]) * ex->max_lines > 0xFFFFFFFFull)
+      return fail(KWK_ECAP, "node " + std::to_string(j) + ": more than 2^32 lines in a family");
   std::vector<uint32_t> pod_of(ex->n_cont);
   for (uint32_t p = 0; p < ex->n_pods; ++p)
     for (uint32_t c = ex->h_cptr[p]; c < ex->h_cptr[p + 1]; ++c) pod_of[c] = p;
@@ -698,27 +829,50 @@ kwk_status kwk_expo_scrape(kwk_expo* ex, int64_t now_ns, uint32_t node_first, ui
   a.out = ex->d_out;
   a.cap = ex->cap_bytes;
   // the values this walk reads are the values the engine wrote: the same series count
-  uint64_t want = 0;
-  for (const DevFamily& F : ex->fam)
-    want += F.dim == KWK_METRIC_DIM_NODE ? n_nodes : F.dim == KWK_METRIC_DIM_POD ? a.p1 - a.p0 : a.c1 - a.c0;
+  const bool has_hist = !ex->hist.empty();
+  uint64_t want = 0, want_words = 0, n_words = 0;
+  for (const DevFamily& F : ex->fam) {
+    const uint64_t series = F.dim == KWK_METRIC_DIM_NODE ? n_nodes : F.dim == KWK_METRIC_DIM_POD ? a.p1 - a.p0 : a.c1 - a.c0;
+    if (F.hist) want_words += series * (ex->hist[F.hist - 1].nvis + 3);
+    else want += series;
+  }
+  if (has_hist) {
+    const uint64_t* hv = nullptr;
+    if (kwk_histograms_eval_device(ex->eng, now_ns, node_first, n_nodes, &hv, &n_words) != KWK_OK)
+      return fail(KWK_ESTATE, std::string("kwk_histograms_eval_device: ") + kwk_last_error(ex->eng));
+    if (want_words != n_words)
+      return fail(KWK_ESTATE, "the engine's loaded histograms (" + std::to_string(n_words) + " record words) are not the "
+                              "exposition program's (" + std::to_string(want_words) + "): kwk_histograms_load the same "
+                              "Metric CR; commit after kwk_usage_config");
+    a.hvals = reinterpret_cast<const unsigned long long*>(hv);
+    a.hist = ex->d_hist;
+    a.hlines = ex->d_hlines;
+    a.n_vals = n_vals;
+  }
   if (want != n_vals)
     return fail(KWK_ESTATE, "the engine's loaded metrics (" + std::to_string(n_vals) + " series) are not the exposition "
                             "program's (" + std::to_string(want) + "): kwk_metrics_load the same Metric CR; commit after "
                             "kwk_usage_config");
   const uint32_t width = ex->width ? ex->width : (n_nodes && (a.p1 - a.p0) / n_nodes > kWidePods) ? 256u : 64u;
-  if (n_vals > ex->stash_cap) {
+  const uint64_t n_slots = n_vals + n_words;  // the histogram words' slots after the scalars'
+  if (n_slots > ex->stash_cap) {
     HIP_TRY(hipStreamSynchronize(ex->stream));
     if (ex->d_stash) HIP_TRY(hipFree(ex->d_stash));
     ex->d_stash = nullptr;
     ex->stash_cap = 0;
-    HIP_TRY(hipMalloc(&ex->d_stash, 32 * (size_t)n_vals));
-    ex->stash_cap = n_vals;
+    HIP_TRY(hipMalloc(&ex->d_stash, 32 * (size_t)n_slots));
+    ex->stash_cap = n_slots;
   }
   a.stash = ex->d_stash;
-#define KWK_EXPO_LAUNCH(WR)                                                                                      \
-  do {                                                                                                          \
-    if (width == 64) hipLaunchKernelGGL((expo_node_kernel<64, WR>), dim3(n_nodes), dim3(64), 0, ex->stream, a); \
-    else hipLaunchKernelGGL((expo_node_kernel<256, WR>), dim3(n_nodes), dim3(256), 0, ex->stream, a);           \
+#define KWK_EXPO_LAUNCH_H(WR, H)                                                                                    \
+  do {                                                                                                             \
+    if (width == 64) hipLaunchKernelGGL((expo_node_kernel<64, WR, H>), dim3(n_nodes), dim3(64), 0, ex->stream, a); \
+    else hipLaunchKernelGGL((expo_node_kernel<256, WR, H>), dim3(n_nodes), dim3(256), 0, ex->stream, a);           \
+  } while (0)
+#define KWK_EXPO_LAUNCH(WR)                 \
+  do {                                      \
+    if (has_hist) KWK_EXPO_LAUNCH_H(WR, true); \
+    else KWK_EXPO_LAUNCH_H(WR, false);      \
   } while (0)
   HIP_TRY(hipMemsetAsync(ex->d_total + 1, 0, 8, ex->stream));
   HIP_TRY(hipEventRecord(ex->ev[1], ex->stream));
@@ -736,6 +890,7 @@ kwk_status kwk_expo_scrape(kwk_expo* ex, int64_t now_ns, uint32_t node_first, ui
     HIP_TRY(hipGetLastError());
   }
 #undef KWK_EXPO_LAUNCH
+#undef KWK_EXPO_LAUNCH_H
   HIP_TRY(hipEventRecord(ex->ev[4], ex->stream));
   ex->scraped = true;
   ex->last_nodes = n_nodes;

@@ -15,6 +15,7 @@
 
 #include "../../include/kwok_metrics.h"
 #include "celc.hpp"
+#include "f64fmt.hpp"
 #include "host_common.hpp"
 #include "json_dom.hpp"
 
@@ -51,6 +52,10 @@ struct kwk_metric_set {
   std::vector<kwk_histogram_desc> hists;
   std::vector<kwk_metric_bucket> buckets;
   std::vector<kwk_metric_op> hist_ops;
+  // the histogram families' tables (kwk_metric_set_exposition_histograms): only with the flag
+  uint32_t flags = 0;
+  std::vector<kwk_expo_hist> expo_hists;
+  std::vector<kwk_expo_hist_line> expo_lines;
   std::string describe;
 };
 
@@ -172,15 +177,60 @@ std::string escape_help(const std::string& v) {  // _escape_help
   return o;
 }
 
+// Go's sort.Float64s order of a histogram's bounds (NaN first): the engine's record order
+bool bound_less(double x, double y) { return x < y || (std::isnan(x) && !std::isnan(y)); }
+
+// the n_visible + 3 line shapes of histogram c (kwok_metrics.h), their bytes appended to lits
+void build_hist_lines(kwk_metric_set& M, const MetricCfg& c, bool labelled) {
+  const kwk_histogram_desc& hd = M.hists[c.index];
+  std::vector<double> bounds;
+  for (uint32_t b = 0; b < hd.n_buckets; ++b)
+    if (!M.buckets[hd.first_bucket + b].hidden) bounds.push_back(M.buckets[hd.first_bucket + b].le);
+  std::stable_sort(bounds.begin(), bounds.end(), bound_less);
+  kwk_expo_hist h{};
+  h.dimension = c.dim;
+  h.n_visible = (uint32_t)bounds.size();
+  h.first_line = (uint32_t)M.expo_lines.size();
+  M.expo_hists[c.index] = h;
+  auto lit = [&](const std::string& t, uint32_t& off, uint32_t& len) {
+    off = (uint32_t)M.lits.size();
+    len = (uint32_t)t.size();
+    M.lits += t;
+  };
+  uint32_t bucket_off, bucket_len;
+  lit(c.name + "_bucket", bucket_off, bucket_len);
+  auto bucket = [&](const std::string& le) {
+    kwk_expo_hist_line l{};
+    l.prefix_off = bucket_off;
+    l.prefix_len = bucket_len;
+    lit(std::string(labelled ? "," : "{") + "le=\"" + le + "\"}", l.tail_off, l.tail_len);
+    M.expo_lines.push_back(l);
+  };
+  for (double b : bounds) {
+    char buf[kwkf64::kMaxBytes];
+    bucket(std::string(buf, kwkf64::format_f64(b, buf)));
+  }
+  bucket("+Inf");
+  for (const char* suffix : {"_sum", "_count"}) {
+    kwk_expo_hist_line l{};
+    lit(c.name + suffix, l.prefix_off, l.prefix_len);
+    lit(labelled ? "}" : "", l.tail_off, l.tail_len);
+    M.expo_lines.push_back(l);
+  }
+}
+
 void build_exposition(kwk_metric_set& M) {
   try {
     std::vector<const MetricCfg*> order;
+    const bool with_hists = (M.flags & KWK_METRICS_EXPO_HISTOGRAMS) != 0;
     for (const MetricCfg& c : M.cfgs) {
-      if (c.kind == "histogram") throw NoExposition("metric '" + c.name + "' is a histogram: no device exposition");
+      if (c.kind == "histogram" && !with_hists)
+        throw NoExposition("metric '" + c.name + "' is a histogram: no device exposition");
       if (!c.device) throw NoExposition("metric '" + c.name + "' is host-evaluated: no device exposition");
       order.push_back(&c);
-      M.metric_dims.push_back(c.dim);
+      if (c.kind != "histogram") M.metric_dims.push_back(c.dim);
     }
+    if (with_hists) M.expo_hists.resize(M.hists.size());
     std::stable_sort(order.begin(), order.end(), [](const MetricCfg* a, const MetricCfg* b) { return a->name < b->name; });
     std::vector<std::string> group_ids;
     for (const MetricCfg* c : order) {
@@ -210,6 +260,10 @@ void build_exposition(kwk_metric_set& M) {
       f.metric = c->index;
       f.dimension = c->dim;
       f.group = (uint32_t)g;
+      if (c->kind == "histogram") {
+        f.reserved = KWK_EXPO_KIND_HISTOGRAM;
+        build_hist_lines(M, *c, M.groups[g].n_labels != 0);
+      }
       M.families.push_back(f);
     }
   } catch (const NoExposition& e) {
@@ -219,6 +273,8 @@ void build_exposition(kwk_metric_set& M) {
     M.groups.clear();
     M.group_labels.clear();
     M.lits.clear();
+    M.expo_hists.clear();
+    M.expo_lines.clear();
   }
 }
 
@@ -367,7 +423,12 @@ const char* kwk_metric_set_last_error(const kwk_metric_set* m) {
 }
 
 kwk_status kwk_compile_metrics(const char* metric_json, kwk_metric_set** out) {
+  return kwk_compile_metrics_flags(metric_json, 0, out);
+}
+
+kwk_status kwk_compile_metrics_flags(const char* metric_json, uint32_t flags, kwk_metric_set** out) {
   if (!metric_json || !out) return fail(KWK_EINVAL, "null argument");
+  if (flags & ~KWK_METRICS_EXPO_HISTOGRAMS) return fail(KWK_EINVAL, "unknown flags");
   try {
     JV cr;
     kwkjson::Parser p{metric_json, metric_json + strlen(metric_json)};
@@ -375,6 +436,7 @@ kwk_status kwk_compile_metrics(const char* metric_json, kwk_metric_set** out) {
     p.ws();
     if (p.p != p.e) return fail(KWK_EINVAL, "metric: trailing bytes after the JSON value");
     std::unique_ptr<kwk_metric_set> M(new kwk_metric_set());
+    M->flags = flags;
     compile(*M, cr);
     *out = M.release();
     return KWK_OK;
@@ -428,6 +490,16 @@ kwk_status kwk_metric_set_exposition(const kwk_metric_set* m, kwk_expo_program* 
   out->groups = m->groups.data();
   out->metric_dimension = m->metric_dims.data();
   out->lits = m->lits.data();
+  return KWK_OK;
+}
+
+kwk_status kwk_metric_set_exposition_histograms(const kwk_metric_set* m, kwk_expo_hist_program* out) {
+  if (!m || !out) return fail(KWK_EINVAL, "null argument");
+  if (m->expo_status != KWK_OK) return fail(m->expo_status, m->expo_err);
+  out->n_hists = (uint32_t)m->expo_hists.size();
+  out->n_lines = (uint32_t)m->expo_lines.size();
+  out->hists = m->expo_hists.data();
+  out->lines = m->expo_lines.data();
   return KWK_OK;
 }
 

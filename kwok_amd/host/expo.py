@@ -6,8 +6,10 @@ as the GPU wrote it.
 Reference: UpdateHandler.Update + promhttp's text encoder (pkg/kwok/metrics/metrics.go:480-502,
 525-573, pkg/kwok/server/metrics.go:129-150).  The text of a node equals
 ``MetricsProgram.exposition(MetricsProgram.scrape(...))`` for that node alone, byte for byte
-(tests/test_gpu_expo.py); that Python path stays the CPU cross-check and the only path of a CR
-the device program refuses (histograms, host-evaluated metrics, computed labels).
+(tests/test_gpu_expo.py, tests/test_gpu_expo_hist.py); that Python path stays the CPU cross-check
+and the only path of a CR the device program refuses (host-evaluated metrics, computed labels, and
+histograms unless the set was compiled with ``expo_histograms=True``: then ``Exposition`` creates
+the writer with the histogram tables, kwk_expo_create_hist).
 """
 from __future__ import annotations
 
@@ -18,7 +20,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import abi
-from .native_metrics import ExpoProgramStruct, NativeMetricSet
+from .native_metrics import KIND_HISTOGRAM, ExpoHistProgramStruct, ExpoProgramStruct, NativeMetricSet
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "lib", "libkwok_expo.so")
 DIM_NODE, DIM_POD, DIM_CONTAINER = 0, 1, 2
@@ -46,6 +48,8 @@ def lib():
     L.kwk_expo_last_error.restype = C.c_char_p
     L.kwk_expo_last_error.argtypes = [vp]
     L.kwk_expo_create.argtypes = [vp, u32, C.POINTER(ExpoProgramStruct), C.POINTER(vp)]
+    L.kwk_expo_create_hist.argtypes = [vp, u32, C.POINTER(ExpoProgramStruct), C.POINTER(ExpoHistProgramStruct),
+                                       C.POINTER(vp)]
     L.kwk_expo_destroy.argtypes = [vp]
     L.kwk_expo_set_labels.argtypes = [vp, u32, u32, u32, vp, vp, vp, vp]
     L.kwk_expo_commit.argtypes = [vp]
@@ -59,7 +63,7 @@ def lib():
     L.kwk_expo_format_values.argtypes = [vp, vp, u32, vp, vp]
     L.kwk_expo_format_f64.argtypes = [C.c_double, vp]
     L.kwk_expo_format_f64.restype = u32
-    for n in ("kwk_expo_create", "kwk_expo_destroy", "kwk_expo_set_labels", "kwk_expo_commit", "kwk_expo_reserve",
+    for n in ("kwk_expo_create", "kwk_expo_create_hist", "kwk_expo_destroy", "kwk_expo_set_labels", "kwk_expo_commit", "kwk_expo_reserve",
               "kwk_expo_scrape", "kwk_expo_result", "kwk_expo_device", "kwk_expo_copy", "kwk_expo_elapsed",
               "kwk_expo_set_width", "kwk_expo_format_values"):
         getattr(L, n).restype = C.c_int32
@@ -98,7 +102,13 @@ class Exposition:
         self.cptr = np.concatenate([[0], np.cumsum(engine.usage_containers)]).astype(np.int64)
         self.h = C.c_void_p()
         L = lib()
-        st = L.kwk_expo_create(engine.h, self.n_nodes, C.byref(self.prog), C.byref(self.h))
+        self.hist_prog = None
+        if any(self.prog.families[f].reserved == KIND_HISTOGRAM for f in range(self.prog.n_families)):
+            self.hist_prog = metric_set.exposition_hist_program()
+            st = L.kwk_expo_create_hist(engine.h, self.n_nodes, C.byref(self.prog), C.byref(self.hist_prog),
+                                        C.byref(self.h))
+        else:
+            st = L.kwk_expo_create(engine.h, self.n_nodes, C.byref(self.prog), C.byref(self.h))
         if st != 0:
             raise ExpoError("kwk_expo_create: " + L.kwk_expo_last_error(None).decode(errors="replace"), st)
         self.reserved = 0

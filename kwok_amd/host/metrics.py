@@ -16,9 +16,11 @@ Histograms (metrics.go:133-160,356-462; histogram.go:81-164): every bucket's val
 the same way and kwk_histograms_eval returns, per series, the bucket counts histogram.Write
 would expose (cumulative counts of the visible bounds, +Inf, sample count and sum).
 
-For a CR of gauges / counters whose labels are literals or selected fields the text is also written
-on the device (host/expo.py, include/kwok_expo.h), byte-equal to ``exposition(scrape(..))`` here,
-which stays the cross-check and the path of every other CR.
+For a CR whose values all have a device form and whose labels are literals or selected fields the
+text is also written on the device (host/expo.py, include/kwok_expo.h), byte-equal to
+``exposition(scrape(..))`` here, which stays the cross-check and the path of every other CR.
+Histogram families are part of that device text when the CR is compiled with
+``from_native(text, expo_histograms=True)``; the default keeps a histogram CR's text here.
 """
 from __future__ import annotations
 
@@ -178,11 +180,13 @@ class MetricsProgram:
                 self.programs.append((m.dimension, [(cel.OP_CONST, math.nan)]))
 
     @classmethod
-    def from_native(cls, text: str) -> "MetricsProgram":
-        """The Metric CR of a YAML text compiled by the native compiler (kwk_compile_metrics)."""
+    def from_native(cls, text: str, expo_histograms: bool = False) -> "MetricsProgram":
+        """The Metric CR of a YAML text compiled by the native compiler (kwk_compile_metrics);
+        expo_histograms: with KWK_METRICS_EXPO_HISTOGRAMS, so that the device exposition program
+        includes the histogram families (host/expo.py)."""
         from .native_metrics import NativeMetricSet
         _, configs = load_metric_yaml(text)
-        return cls(configs, native=NativeMetricSet(load_metric_doc(text)))
+        return cls(configs, native=NativeMetricSet(load_metric_doc(text), expo_histograms=expo_histograms))
 
     def load(self, pods_engine):
         if self.native is not None:

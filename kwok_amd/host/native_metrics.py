@@ -16,6 +16,8 @@ from . import abi, cel
 from .native_compiler import lib as _compiler_lib
 
 KWK_ENOLOWER = -5
+KWK_METRICS_EXPO_HISTOGRAMS = 1   # kwk_compile_metrics_flags
+KIND_SCALAR, KIND_HISTOGRAM = 0, 1  # kwk_expo_family.reserved: the kind code
 
 _bound = False
 
@@ -37,6 +39,22 @@ class ExpoProgramStruct(C.Structure):
                 ("metric_dimension", C.POINTER(C.c_uint32)), ("lits", C.c_void_p)]
 
 
+class ExpoHistLine(C.Structure):
+    _fields_ = [("prefix_off", C.c_uint32), ("prefix_len", C.c_uint32), ("tail_off", C.c_uint32),
+                ("tail_len", C.c_uint32)]
+
+
+class ExpoHist(C.Structure):
+    _fields_ = [("dimension", C.c_uint32), ("n_visible", C.c_uint32), ("first_line", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class ExpoHistProgramStruct(C.Structure):
+    """kwk_expo_hist_program (include/kwok_metrics.h): the histogram families' per-line tables."""
+    _fields_ = [("n_hists", C.c_uint32), ("n_lines", C.c_uint32), ("hists", C.POINTER(ExpoHist)),
+                ("lines", C.POINTER(ExpoHistLine))]
+
+
 def lib():
     global _bound
     L = _compiler_lib()
@@ -44,6 +62,8 @@ def lib():
         L.kwk_metric_set_last_error.restype = C.c_char_p
         L.kwk_metric_set_last_error.argtypes = [C.c_void_p]
         L.kwk_compile_metrics.argtypes = [C.c_char_p, C.POINTER(C.c_void_p)]
+        L.kwk_compile_metrics_flags.argtypes = [C.c_char_p, C.c_uint32, C.POINTER(C.c_void_p)]
+        L.kwk_metric_set_exposition_histograms.argtypes = [C.c_void_p, C.POINTER(ExpoHistProgramStruct)]
         L.kwk_metric_set_destroy.argtypes = [C.c_void_p]
         L.kwk_metric_set_programs.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_void_p),
                                               C.POINTER(C.c_uint32), C.POINTER(C.c_void_p)]
@@ -58,7 +78,8 @@ def lib():
                                                C.POINTER(C.c_uint32)]
         for n in ("kwk_compile_metrics", "kwk_metric_set_destroy", "kwk_metric_set_programs",
                   "kwk_metric_set_histograms", "kwk_metric_set_describe", "kwk_cel_lower",
-                  "kwk_metric_set_exposition", "kwk_metric_labels_render"):
+                  "kwk_metric_set_exposition", "kwk_metric_labels_render", "kwk_compile_metrics_flags",
+                  "kwk_metric_set_exposition_histograms"):
             getattr(L, n).restype = C.c_int32
         _bound = True
     return L
@@ -69,8 +90,8 @@ class MetricCompileError(ValueError):
 
 
 class NoExposition(MetricCompileError):
-    """The Metric CR has no device exposition program (a histogram, a host-evaluated metric or a
-    label outside the supported subset)."""
+    """The Metric CR has no device exposition program (a host-evaluated metric, a label outside the
+    supported subset, or a histogram in a set compiled without ``expo_histograms``)."""
 
 
 class LabelRenderError(ValueError):
@@ -104,12 +125,19 @@ def cel_lower(expr: str, dimension: str) -> List[Tuple[int, float]]:
 
 
 class NativeMetricSet:
-    """One Metric CR compiled by kwk_compile_metrics."""
+    """One Metric CR compiled by kwk_compile_metrics; expo_histograms: by kwk_compile_metrics_flags
+    with KWK_METRICS_EXPO_HISTOGRAMS, so that histogram families are part of the exposition program
+    (``exposition_hist_program``) instead of refusing it."""
 
-    def __init__(self, metric_doc: dict):
+    def __init__(self, metric_doc: dict, expo_histograms: bool = False):
         self.h = C.c_void_p()
+        self.expo_histograms = bool(expo_histograms)
         L = lib()
-        st = L.kwk_compile_metrics(json.dumps(metric_doc).encode(), C.byref(self.h))
+        if expo_histograms:
+            st = L.kwk_compile_metrics_flags(json.dumps(metric_doc).encode(), KWK_METRICS_EXPO_HISTOGRAMS,
+                                             C.byref(self.h))
+        else:
+            st = L.kwk_compile_metrics(json.dumps(metric_doc).encode(), C.byref(self.h))
         if st != 0:
             raise MetricCompileError(L.kwk_metric_set_last_error(None).decode(errors="replace"))
         s = C.c_char_p()
@@ -161,6 +189,17 @@ class NativeMetricSet:
         prog = ExpoProgramStruct()
         L = lib()
         st = L.kwk_metric_set_exposition(self.h, C.byref(prog))
+        if st != 0:
+            msg = L.kwk_metric_set_last_error(None).decode(errors="replace")
+            raise (NoExposition if st == KWK_ENOLOWER else MetricCompileError)(msg)
+        return prog
+
+    def exposition_hist_program(self) -> ExpoHistProgramStruct:
+        """kwk_metric_set_exposition_histograms: per histogram its dimension, n_visible and the
+        prefix / tail byte ranges (in the exposition program's lits) of its n_visible + 3 lines."""
+        prog = ExpoHistProgramStruct()
+        L = lib()
+        st = L.kwk_metric_set_exposition_histograms(self.h, C.byref(prog))
         if st != 0:
             msg = L.kwk_metric_set_last_error(None).decode(errors="replace")
             raise (NoExposition if st == KWK_ENOLOWER else MetricCompileError)(msg)

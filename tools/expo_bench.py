@@ -4,6 +4,7 @@ and at a larger size in node-range chunks that fit the reservation.
 
     python tools/expo_bench.py [--nodes 10000 --pods 1000000] [--chunk 0] [--scrapes 10 --warmup 3]
                                [--sample 16] [--out profiles/r7/expo_bench.json] [--tag c4]
+    python tools/expo_bench.py --hist [--out profiles/r8/expo_hist_bench.json] [--tag c4_hist]
 
 Per all-node scrape, by HIP events on the engine's stream (medians over --scrapes, after --warmup):
 microseconds of the lengths / scan / write kernels, the bytes written, GB/s of the write kernel and
@@ -11,6 +12,12 @@ of the three kernels together; the same with the other workgroup width.  Then th
 only path — MetricsProgram.scrape + exposition in Python — timed on --sample nodes and
 extrapolated (stated as such) to every node; those nodes' device text is compared byte for byte.
 The result is merged into the JSON file under --tag.
+
+--hist: the histogram leg.  The CR is the shipped families plus one pod-dimension and one
+container-dimension histogram of 5 visible buckets over pod.Usage("memory") /
+pod.Usage("cpu", container.name), compiled with expo_histograms (kwk_expo_create_hist); the
+scalar-only CR is measured first in the same process and recorded beside it ("scalar_same_run"),
+with the histogram write pass's bytes/s relative to the scalar pass's.
 """
 import argparse
 import copy
@@ -25,7 +32,31 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def build_rig(n_nodes, n_pods, seed):
+LABELS = {"pod": [{"name": "namespace", "value": "pod.metadata.namespace"}, {"name": "pod", "value": "pod.metadata.name"}],
+          "container": [{"name": "container", "value": "container.name"},
+                        {"name": "namespace", "value": "pod.metadata.namespace"},
+                        {"name": "pod", "value": "pod.metadata.name"}]}
+
+
+def hist_cr_text():
+    """The shipped Metric CR plus a pod and a container histogram (5 visible buckets each; the
+    labels of the shipped pod / container families, so they share their label groups)."""
+    import yaml
+    from kwok_amd.configs import METRIC_CR
+    from kwok_amd.host.metrics import load_metric_doc
+    doc = load_metric_doc(open(METRIC_CR).read())
+    mib, milli = 'pod.Usage("memory") / 1048576.0', 'pod.Usage("cpu", container.name) * 1000.0'
+    doc["spec"]["metrics"] += [
+        {"name": "pod_memory_working_set_mib", "kind": "histogram", "dimension": "pod", "help": "pod memory (MiB)",
+         "labels": LABELS["pod"],
+         "buckets": [{"le": le, "value": mib} for le in (16, 64, 256, 1024, 4096)]},
+        {"name": "container_cpu_millicores", "kind": "histogram", "dimension": "container", "help": "container cpu (m)",
+         "labels": LABELS["container"],
+         "buckets": [{"le": le, "value": milli} for le in (10, 100, 500, 1000, 4000)]}]
+    return yaml.safe_dump(doc)
+
+
+def build_rig(n_nodes, n_pods, seed, cr_text=None):
     from kwok_amd.configs import METRIC_CR, NOW0, USAGE_YAML, c4_pod_workload
     from kwok_amd.host import cel
     from kwok_amd.host.compiler import KindProgram
@@ -46,7 +77,8 @@ def build_rig(n_nodes, n_pods, seed):
     vkeys, cv, mv, mx, ck = usage_columns(up, pvars)
     pods.usage_config(node_ptr, vkeys[pidx], cv, mv, mx, ck)
     pods.usage_pods(True)
-    mp = MetricsProgram.from_native(open(METRIC_CR).read())
+    mp = MetricsProgram.from_native(cr_text, expo_histograms=True) if cr_text else \
+        MetricsProgram.from_native(open(METRIC_CR).read())
     mp.load(pods)
     slots = np.arange(n_pods, dtype=np.int64)
     created = NOW0 - ((slots * 7919) % 86400) * 10**9 - 3600 * 10**9
@@ -137,14 +169,39 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--sample", type=int, default=16, help="nodes of the Python scrape + exposition comparison")
     ap.add_argument("--seed", type=int, default=0x6B776F6B)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r7", "expo_bench.json"))
-    ap.add_argument("--tag", default="c4")
+    ap.add_argument("--out", default=None, help="default profiles/r7/expo_bench.json (--hist: profiles/r8/expo_hist_bench.json)")
+    ap.add_argument("--tag", default=None, help="default c4 (--hist: c4_hist)")
     ap.add_argument("--native-labels", action="store_true",
                     help="render every label row with kwk_metric_labels_render (Exposition.set_pods): slow from Python")
+    ap.add_argument("--hist", action="store_true",
+                    help="the histogram leg (and the scalar-only CR in the same process): see the module docstring")
     args = ap.parse_args()
+    args.out = args.out or os.path.join(ROOT, "profiles", *(("r8", "expo_hist_bench.json") if args.hist else ("r7", "expo_bench.json")))
+    args.tag = args.tag or ("c4_hist" if args.hist else "c4")
+    if args.hist:
+        scalar = leg(args, None)
+        res = leg(args, hist_cr_text())
+        res["scalar_same_run"] = scalar
+        for w in [k for k in res if k.startswith("width_")]:
+            res[w]["write_GBps_over_scalar"] = round(res[w]["write_GBps"] / scalar[w]["write_GBps"], 3)
+    else:
+        res = leg(args, None)
+    out = {}
+    if os.path.exists(args.out):
+        out = json.load(open(args.out))
+    out[args.tag] = res
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print(json.dumps({args.tag: res}))
+
+
+def leg(args, cr_text):
+    """One CR (None: the shipped one) measured end to end -> its result section."""
     from kwok_amd.host.expo import Exposition
     t_setup = time.perf_counter()
-    pods, mp, pvars, pidx, node_ptr, t = build_rig(args.nodes, args.pods, args.seed)
+    pods, mp, pvars, pidx, node_ptr, t = build_rig(args.nodes, args.pods, args.seed, cr_text)
     ex = Exposition(pods, mp.native)
     if args.native_labels:
         upload_labels_native(ex, pvars, pidx, args.pods)
@@ -168,7 +225,9 @@ def main():
             need = max(need, ex.needed)
     ex.reserve(need + need // 16)
     t += dt
-    res = {"workload": f"{args.nodes} nodes / {args.pods} pods (C4 shape), metrics-resource.yaml, "
+    cr_name = "metrics-resource.yaml + a pod and a container histogram (5 visible buckets)" if cr_text else \
+        "metrics-resource.yaml"
+    res = {"workload": f"{args.nodes} nodes / {args.pods} pods (C4 shape), {cr_name}, "
                        f"{len(chunks)} scrape call(s) of {chunk} nodes", "reserved_bytes": need + need // 16,
            "setup_s": round(setup_s, 1), "commit_s": round(commit_s, 2)}
     ppn = args.pods // max(1, args.nodes)
@@ -200,17 +259,9 @@ def main():
         "note": "an extrapolation: the sampled nodes' mean time x the node count (one Python process)",
         "device_text_equal_nodes": equal}
     assert equal == len(sample), "device text differs from the Python exposition"
-    out = {}
-    if os.path.exists(args.out):
-        out = json.load(open(args.out))
-    out[args.tag] = res
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(out, f, indent=1, sort_keys=True)
-        f.write("\n")
-    print(json.dumps({args.tag: res}))
     ex.close()
     pods.close()
+    return res
 
 
 if __name__ == "__main__":
