@@ -558,8 +558,11 @@ struct kwk_program {
     }
     for (const Stage& st : stages) {
       uint32_t eq_mask = 0, eq_val = 0;
+      bool contradiction = false;
       std::vector<std::pair<uint32_t, uint32_t>> anys;
       auto eq = [&](uint32_t mask, bool want) {
+        // a bit an earlier requirement wants the other way: the requirements exclude each other
+        if (mask & eq_mask & (want ? ~eq_val : eq_val)) contradiction = true;
         eq_mask |= mask;
         if (want) eq_val |= mask;
       };
@@ -610,6 +613,11 @@ struct kwk_program {
       }
       if (anys.size() > KWK_MAX_ANY)
         throw CompileError("stage " + st.name + ": more than " + std::to_string(KWK_MAX_ANY) + " multi-value In requirements");
+      // contradicting eq-tests: the any-clause no object satisfies (compiler.py _compile)
+      if (contradiction) {
+        if (anys.size() == KWK_MAX_ANY) anys.pop_back();
+        anys.emplace_back(0, 1);
+      }
       kwk_stage_desc d;
       memset(&d, 0, sizeof d);
       d.eq_mask = eq_mask;

@@ -248,10 +248,14 @@ class KindProgram:
             self.fin_other_bit = self._bit()
         for st in self.stages:
             eq_mask = eq_val = 0
+            contradiction = False
             anys: List[Tuple[int, int]] = []
 
             def eq(mask, want):
-                nonlocal eq_mask, eq_val
+                nonlocal eq_mask, eq_val, contradiction
+                # a bit an earlier requirement wants the other way: the requirements exclude each other
+                if mask & eq_mask & (~eq_val if want else eq_val):
+                    contradiction = True
                 eq_mask |= mask
                 if want:
                     eq_val |= mask
@@ -300,9 +304,15 @@ class KindProgram:
                             anys.append((m, 1))
                     else:
                         eq(m, False)
-            # a stage whose eq-tests contradict (same bit wanted 1 and 0) can never match
             if len(anys) > abi.MAX_ANY:
                 raise CompileError(f"stage {st.name}: more than {abi.MAX_ANY} multi-value In requirements")
+            # a stage whose eq-tests contradict (same bit wanted 1 and 0) can never match: the
+            # any-clause no object satisfies (as `In` on .metadata.finalizers), in the last any
+            # slot when none is free (the clause it replaces no longer matters)
+            if contradiction:
+                if len(anys) == abi.MAX_ANY:
+                    anys.pop()
+                anys.append((0, 1))
             d = abi.StageDesc()
             d.eq_mask, d.eq_val = eq_mask, eq_val
             d.n_any = len(anys)
@@ -494,7 +504,7 @@ class KindProgram:
             new = [s for s in unchanged if s not in self.applied_bits]
             if not new:
                 break
-            for s in new:
+            for s in sorted(new):  # ascending stage index, as the native compiler's std::set
                 self.applied_bits[s] = self._bit()
                 d = self.stage_desc[s]
                 d.flags |= abi.NEXT_PATCH_STATIC
