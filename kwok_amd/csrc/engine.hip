@@ -1533,6 +1533,57 @@ __device__ __forceinline__ void id8_passn(const uint32_t (&we)[kN], const uint32
   }
 }
 
+// kN passes carried through all kSteps steps of a fused launch in registers (a tile without a queued
+// stage and with at most 2048 / kSteps items: no due test, and an id off the list never joins it).
+// The id byte is read once; step s >= 1 looks up the id step s - 1 left if it still has kIdNeed,
+// else kIdInvalid (the identity: no fire, no statistics — an inactive lane's 0xFF stays 0xFF by the
+// same rule); the last live id is written once.  Step 0's records are staged at the list's consumed
+// front, step s's in region s of the work list (2048 / kSteps records each, past the list), each
+// step with its own count.  live: the items of steps >= 1 (the ids' own writes the line stores
+// replace, as phase 1 of each step counts them)
+template <int kSteps, uint32_t kN>
+__device__ __forceinline__ void id8_carryn(const uint32_t (&we)[kN], const uint32_t* __restrict__ s_fsm,
+                                           uint16_t* __restrict__ wl, const __amdgpu_buffer_rsrc_t seg_rs,
+                                           uint32_t (&segs)[kSteps], uint32_t& n_bytes, uint32_t& n_matched,
+                                           uint32_t (&stc)[4], uint32_t& live, unsigned int* s_stat, uint32_t n_stages,
+                                           uint32_t lane) {
+  constexpr uint32_t kRegion = 2048u / (uint32_t)kSteps;
+  uint32_t key[kN], fin[kN], e[kN];
+#pragma unroll
+  for (uint32_t j = 0; j < kN; ++j) {
+    key[j] = (uint32_t)*(lds_u8*)(size_t)we[j];
+    fin[j] = kIdInvalid;  // the id the item left the list with (kIdInvalid: still on it)
+  }
+#pragma unroll
+  for (int s = 0; s < kSteps; ++s) {
+    if (s > 0) {
+#pragma unroll
+      for (uint32_t j = 0; j < kN; ++j) live += (uint32_t)__popcll(ballot(key[j] != kIdInvalid));
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < kN; ++j) e[j] = s_fsm[key[j]];
+#pragma unroll
+    for (uint32_t j = 0; j < kN; ++j) {
+      n_bytes += (e[j] >> 24) & 31u;
+      n_matched += (e[j] >> 30) & 1u;
+      id8_fire<true>(we[j], e[j], wl + (uint32_t)s * kRegion, seg_rs, segs[s], stc, s_stat, n_stages, lane);
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < kN; ++j) {
+      const uint32_t nid = e[j] & 0xFFu;
+      if (s + 1 < kSteps) {
+        const bool on = (nid & kIdNeed) != 0;  // (an item that left before: nid = kIdInvalid, fin stays)
+        key[j] = on ? nid : kIdInvalid;
+        fin[j] = on ? fin[j] : nid;
+      } else {
+        fin[j] &= nid;  // still on the list: fin = 0xFF; left before: nid = 0xFF
+      }
+    }
+  }
+#pragma unroll
+  for (uint32_t j = 0; j < kN; ++j) *(lds_u8*)(size_t)we[j] = (uint8_t)fin[j];
+}
+
 // the fired ballot of one pass: records staged at the list's consumed front (<= 4 stages) or
 // stored to the segment, per-stage counts
 template <bool kStages4>
@@ -1564,7 +1615,11 @@ __device__ __forceinline__ void id8_fire(const uint32_t addr, const uint32_t e, 
 // VGPRs, 26.8 KB of LDS) so that a 12.5M-id shard's 1526 tiles are one dispatch round, not two
 // kSteps > 1: fused steps (a.now, then a.nowx[s - 1] for step s) for tables without delayed
 // stages — each id is read once, stepped kSteps times in LDS and written once; step 0's records go
-// to a.fired / a.wave_counts, step s's to a.firedx / a.countsx[s - 1] (step_group)
+// to a.fired / a.wave_counts, step s's to a.firedx / a.countsx[s - 1] (step_group).  A
+// wave whose tile holds no queued id and at most 2048 / kSteps items builds its work list once and
+// carries it, two passes at a time, through all kSteps steps in registers (id8_carryn: kIdNeed is a
+// function of the id, so step s + 1's items are step s's whose new id still has it); any other tile
+// rebuilds its list at every step.  Both paths share one block of stores per step
 template <bool kPersist, int kDepth, bool kStages4, int kSteps = 1>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kPersist ? 1 : 6))) void sweep8_kernel(SweepArgs a) {
   constexpr int Q = kQ8;
@@ -1664,8 +1719,17 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kPersist
     // test at `now`, the work list and the table passes; the step's records staged at the work
     // list's front (seg_n).  Returns the items worked: the tile is in LDS iff nonzero.  first: the
     // step that read the ids from HBM (a fused pair's second step adds no read bytes)
-    auto phase12 = [&](const uint4 (&ids)[Q], const int64_t now, const bool first, const bool in_lds, uint32_t& seg_n)
+    // kSteps > 1, step 0 of a tile without a queued id and with at most kCarry items (idle tiles
+    // among them): carry — its pass loop takes each batch through all kSteps steps in registers
+    // (id8_carryn; the step's counts in segs[], its records in region s of the work list) and the
+    // later steps' phase 1 + 2 are skipped.  Any other tile: every step rebuilds its list (a queued
+    // id's due test is made at each step's own `now`)
+    constexpr uint32_t kCarry = kWave / (uint32_t)kSteps;
+    uint32_t segs[kSteps] = {};  // wave-uniform: the steps' record counts
+    bool carry = false;          // wave-uniform
+    auto phase12 = [&](const uint4 (&ids)[Q], const int64_t now, const auto first_t, const bool in_lds, uint32_t& seg_n)
                        __attribute__((always_inline)) -> uint32_t {
+      constexpr bool first = decltype(first_t)::value;
       uint32_t need = 0, pend = 0, ready = 0;
   #pragma unroll
       for (int q = 0; q < Q; ++q) {
@@ -1697,6 +1761,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kPersist
         pos = incl - cnt;
         n_work = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
       }
+      if constexpr (kSteps > 1 && first) carry = !any_due && n_work <= kCarry && ballot(pend != 0) == 0;
       if (n_work) {  // wave-uniform
         // ---- phase 2: the ids to the LDS tile, the work list (absolute LDS addresses of the ids in
         // slot order per lane), then one lookup in the id table per item, 64 items per pass
@@ -1765,6 +1830,20 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kPersist
                 nw[j] = i < n_work ? x : inv_ent;
               }
             }
+            if constexpr (kSteps > 1 && first) {
+              if (carry) {  // wave-uniform
+                // two passes at a time (all four: 96 / 22 SGPRs spilled in the 4-step persistent / one-tile
+                // kernel against 36 / 0, and no faster: 47.3-48.3 vs 47.1-47.3 us per C5 step)
+                static_assert(kB == 4, "two halves");
+                uint32_t live = 0;
+                const uint32_t wa[2] = {we[0], we[1]}, wb[2] = {we[2], we[3]};
+                id8_carryn<kSteps, 2>(wa, s_fsm, wl, seg_rs, segs, n_bytes, n_matched, stc, live, s_stat, n_stages, lane);
+                if (c + 128u < n_work)  // wave-uniform
+                  id8_carryn<kSteps, 2>(wb, s_fsm, wl, seg_rs, segs, n_bytes, n_matched, stc, live, s_stat, n_stages, lane);
+                w_line -= live;  // (wave-uniform: summed with the lanes' n_lline at the end)
+                continue;
+              }
+            }
             id8_passn<kStages4, kB>(we, s_fsm, wl, seg_rs, seg_n, n_bytes, n_matched, stc, s_stat, n_stages, lane);
           }
         }
@@ -1773,9 +1852,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kPersist
       }
       return n_work;
     };
-    // the step's staged records to its segment (kStages4), the header and the count
+    // the step's staged records to its segment (kStages4), the header and the count; roff: the
+    // 16-byte chunk of the work list the step's records start at (a carried step's region)
     auto store_records = [&](const __amdgpu_buffer_rsrc_t seg_rs, const __amdgpu_buffer_rsrc_t cnt_rs,
-                             const uint32_t seg_n) __attribute__((always_inline)) {
+                             const uint32_t seg_n, const uint32_t roff) __attribute__((always_inline)) {
       if constexpr (kStages4) {
         // records: seg_n 2-byte records from the work list, as 16-byte chunks of whole 128-byte
         // lines (the tail of the last line is padding)
@@ -1786,7 +1866,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kPersist
   #pragma unroll
         for (uint32_t r = 0; r < 4; ++r) {
           const uint32_t ci = r * 64u + lane;
-          const uint4 x = wq[ci];
+          const uint4 x = wq[kSteps > 1 ? (roff + ci) & (kWave / 8u - 1u) : ci];
           __builtin_amdgcn_raw_buffer_store_b128(u32x4{x.x, x.y, x.z, x.w}, seg_rs,
                                                  ci < n_chunks ? kRec16Header + ci * 16u : kOOB, 0, 0);
         }
@@ -1813,26 +1893,27 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kPersist
       }
       wave_fired += seg_n;
     };
-    uint32_t seg_n = 0;  // wave-uniform
-    const uint32_t n_work = phase12(cur, a.now, true, false, seg_n);
+    const uint32_t n_work = phase12(cur, a.now, std::true_type{}, false, segs[0]);
     uint32_t any_work = n_work;
-    uint32_t seg_last = seg_n;
 #pragma unroll
     for (int st = 1; st < kSteps; ++st) {
       // step st (a.nowx[st - 1]) on the ids the steps before left: the previous step's records go
-      // to its segment first (they sit in the work list the next list overwrites)
+      // to its segment first (they sit in the work list the next list overwrites; a carried tile's
+      // in that step's region: the same stores on both paths)
       const uint32_t* px = reinterpret_cast<const uint32_t*>(st == 1 ? a.fired : a.firedx[st - 2]);
       store_records(make_rsrc(px + (uint64_t)seg_id * kSeg8, kSeg8 * 4u),
-                    make_rsrc(st == 1 ? a.wave_counts : a.countsx[st - 2], n_tiles * kWavesPerBlock * 4u), seg_last);
-      uint4 mid[Q];
+                    make_rsrc(st == 1 ? a.wave_counts : a.countsx[st - 2], n_tiles * kWavesPerBlock * 4u), segs[st - 1],
+                    carry ? (uint32_t)(st - 1) * (kCarry / 8u) : 0u);
+      if (!carry) {  // wave-uniform
+        uint4 mid[Q];
 #pragma unroll
-      for (int q = 0; q < Q; ++q)
-        mid[q] = any_work ? make_uint4(tw[lds_col8(q * 4 + 0, lane)], tw[lds_col8(q * 4 + 1, lane)],
-                                       tw[lds_col8(q * 4 + 2, lane)], tw[lds_col8(q * 4 + 3, lane)])
-                          : cur[q];
-      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-      seg_last = 0;
-      any_work |= phase12(mid, a.nowx[st - 1], false, any_work != 0, seg_last);
+        for (int q = 0; q < Q; ++q)
+          mid[q] = any_work ? make_uint4(tw[lds_col8(q * 4 + 0, lane)], tw[lds_col8(q * 4 + 1, lane)],
+                                         tw[lds_col8(q * 4 + 2, lane)], tw[lds_col8(q * 4 + 3, lane)])
+                            : cur[q];
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        any_work |= phase12(mid, a.nowx[st - 1], std::false_type{}, any_work != 0, segs[st]);
+      }
     }
     // ---- phase 3 and the hand-back segment: a fixed set of stores per tile (whole 128-byte lines
     // wherever an id changed, the staged records, the header), each lane's offset out of range
@@ -1856,9 +1937,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kPersist
     }
     if constexpr (kSteps > 1)
       store_records(make_rsrc(reinterpret_cast<const uint32_t*>(a.firedx[kSteps - 2]) + (uint64_t)seg_id * kSeg8, kSeg8 * 4u),
-                    make_rsrc(a.countsx[kSteps - 2], n_tiles * kWavesPerBlock * 4u), seg_last);
+                    make_rsrc(a.countsx[kSteps - 2], n_tiles * kWavesPerBlock * 4u), segs[kSteps - 1],
+                    carry ? (uint32_t)(kSteps - 1) * (kCarry / 8u) : 0u);
     else
-      store_records(seg_rs, cnt_rs, seg_last);
+      store_records(seg_rs, cnt_rs, segs[0], 0u);
     if constexpr (kStages4) {
       stc[1] += stc[0] & 0x00FF00FFu;
       stc[2] += (stc[0] >> 8) & 0x00FF00FFu;
