@@ -58,7 +58,8 @@ kwk_status kwk_expo_destroy(kwk_expo* ex);
 /* rows [first, first + n) of `group`: row i's label block is blocks[block_offsets[i] ..
  * block_offsets[i + 1]) and its sort key keys[key_offsets[i] .. key_offsets[i + 1])
  * (kwk_metric_labels_render's outputs; offsets hold n + 1 entries).  Host-side until
- * kwk_expo_commit.  After a pod is replaced: set its rows again and commit.  The row counts are the
+ * kwk_expo_commit or kwk_expo_commit_rows (the rows set since the last commit are remembered as
+ * dirty).  After a pod is replaced: set its rows again and kwk_expo_commit_rows.  The row counts are the
  * engine's layout as of kwk_expo_create or the last kwk_expo_commit: after a kwk_usage_config /
  * kwk_usage_mixed that changes the pod or container count, commit once (it re-reads the layout and
  * keeps the rows set so far), then set the new rows and commit again.  Rows of dead slots need not
@@ -68,9 +69,44 @@ kwk_status kwk_expo_destroy(kwk_expo* ex);
 kwk_status kwk_expo_set_labels(kwk_expo* ex, uint32_t group, uint32_t first, uint32_t n, const uint32_t* block_offsets,
                                const char* blocks, const uint32_t* key_offsets, const char* keys);
 /* stable-sorts every node's rows of each group by key (bytewise; ties keep row order: the order of
- * exposition()'s sorted(series, key=label values)) and uploads blocks and permutations.  Re-reads
- * the engine's node_ptr / container layout. */
+ * exposition()'s sorted(series, key=label values)) and uploads blocks, keys and permutations, packed
+ * (it compacts what kwk_expo_commit_rows appended).  Re-reads the engine's node_ptr / container
+ * layout; synchronises the stream; clears the dirty rows. */
 kwk_status kwk_expo_commit(kwk_expo* ex);
+/* The commit of a live cluster: brings only the rows given to kwk_expo_set_labels since the last
+ * commit (of either kind) up to date, at a cost that follows those rows.  After KWK_OK every later
+ * scrape writes the text it would write after kwk_expo_commit of the same host state; every row's
+ * block and every group's permutation are the ones that call would produce (kwk_expo_read_perm).
+ *
+ * A group's blocks (and, for pod and container groups, its sort keys) live in a device arena with an
+ * {offset, length} pair per row.  kwk_expo_commit lays the rows out packed with slack at the tail; this
+ * call overwrites a row in place where the new bytes fit its slot and appends it at the tail where
+ * they do not; a full tail doubles the arena (copied on the stream; the old buffer is freed by a later
+ * call, after an event).  All dirty blocks and keys go up in one staging copy, a scatter kernel puts
+ * them in place, and expo_sort_kernel re-sorts each node that holds a dirty row of a pod or container
+ * group — nodes of up to KWK_EXPO_SORT_MAX_ROWS rows of the group on the device; a larger node is
+ * sorted on the host (that node only) and its slice of the permutation goes up with the same copy.
+ *
+ * Everything is enqueued on the engine's stream, before the next scrape.  The call does not wait for
+ * that stream: it waits only for its own previous staging copy (an event), and for an 8-byte read of
+ * the engine's pod and container totals on a stream of its own.
+ *   no dirty rows                      KWK_OK, nothing enqueued
+ *   no kwk_expo_commit yet, or an earlier call of this kind failed part-way
+ *                                      KWK_ESTATE
+ *   the engine's pod or container count is not the last kwk_expo_commit's
+ *                                      KWK_ESTATE: kwk_expo_commit (the dirty rows are kept)
+ *   a group's blocks or keys would pass 4 GiB (appended slots are not reclaimed)
+ *                                      KWK_ECAP: kwk_expo_commit compacts the storage
+ * A kwk_usage_config / kwk_usage_mixed that moves pods between nodes or containers between pods but
+ * keeps both counts is not seen here: follow every such call with kwk_expo_commit.
+ * Measured at 10k nodes / 1M pods (DESIGN.md "Incremental label commits"; every row appended, the
+ * dearest case): 0.1 % / 1 % / 10 % of the pods relabelled — the call returns after 0.5 / 3.9 / 32 ms
+ * and the stream has finished it after 1.8 / 8.2 / 40 ms, where kwk_expo_commit takes 0.33 s and
+ * stalls the stream.  Faster at every fraction measured; by its 0.3-0.4 us per relabelled pod it
+ * meets the full commit only near every pod relabelled: prefer kwk_expo_commit then, after a
+ * relayout, and when KWK_ECAP asks for compaction. */
+kwk_status kwk_expo_commit_rows(kwk_expo* ex);
+#define KWK_EXPO_SORT_MAX_ROWS 1024u
 /* output room: text bytes one scrape may produce */
 kwk_status kwk_expo_reserve(kwk_expo* ex, uint64_t max_bytes);
 /* enqueue one scrape of nodes [node_first, node_first + n_nodes) at now_ns, after the caller's
@@ -96,6 +132,16 @@ kwk_status kwk_expo_set_width(kwk_expo* ex, uint32_t width);
 kwk_status kwk_expo_format_values(kwk_expo* ex, const double* host_values, uint32_t n, char* out, uint8_t* lens);
 /* the host build of the same formatter (no GPU): strconv.AppendFloat(v, 'g', -1, 64) -> length */
 uint32_t kwk_expo_format_f64(double v, char out[24]);
+/* a pod or container group's device permutation copied to the host (synchronises; tests, diagnosis):
+ * out = the group's rows; entry i of a node's row range is the row written i-th.  KWK_EINVAL for a
+ * node-dimension group (it has none) */
+kwk_status kwk_expo_read_perm(kwk_expo* ex, uint32_t group, uint32_t* out);
+/* the host build of the device sort's comparator (no GPU): < 0, 0, > 0 as key a sorts before, with or
+ * after key b — unsigned bytes, a proper prefix first (std::string's order) */
+int kwk_expo_key_compare(const char* a, uint32_t na, const char* b, uint32_t nb);
+/* HIP events around the last kwk_expo_commit_rows that enqueued work: milliseconds of [0] the scatter
+ * kernel, [1] the sort kernel (synchronises with them) */
+kwk_status kwk_expo_commit_rows_elapsed(kwk_expo* ex, float ms[2]);
 
 #ifdef __cplusplus
 }

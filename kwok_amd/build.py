@@ -39,7 +39,7 @@ EMIT_OUT = os.path.join(PKG, "lib", "libkwok_emit.so")
 EXPO_SRC = [os.path.join(PKG, "csrc", "expo.hip")]
 EXPO_HDR = [os.path.join(ROOT, "include", "kwok_expo.h"), os.path.join(ROOT, "include", "kwok_metrics.h"),
             os.path.join(ROOT, "include", "kwok_engine.h"), os.path.join(PKG, "csrc", "f64fmt.hpp"),
-            os.path.join(PKG, "csrc", "f64fmt_tables.hpp")]
+            os.path.join(PKG, "csrc", "f64fmt_tables.hpp"), os.path.join(PKG, "csrc", "keycmp.hpp")]
 EXPO_OUT = os.path.join(PKG, "lib", "libkwok_expo.so")
 ARCH = "gfx950"  # MI355X only
 

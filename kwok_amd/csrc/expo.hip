@@ -37,6 +37,16 @@
 // after the scalars'.  The block scan, the LDS staging and the bounded stores are the scalar
 // families'.  Only expo_node_kernel<W, ., true> knows any of this: a program without histogram
 // families launches <W, ., false>, whose code has no histogram state.
+//
+// Label rows (the reference keeps its registry current per object, metrics.go:480-502): a group's
+// blocks, and the sort keys of a pod or container group, live in an arena with an {offset, length}
+// pair per row.  kwk_expo_commit lays every row out packed, sorted on the host; kwk_expo_commit_rows
+// brings only the rows set since the last commit up to date, on the stream, without a host
+// synchronisation:
+//   expo_scatter_kernel  a wave per dirty row: its bytes from the staging copy to its slot (in place
+//                        where they fit, else at the arena's tail), its pair
+//   expo_sort_kernel     a workgroup per (node, group) that holds a dirty row: the node's slice of
+//                        the permutation by a rank sort under the comparator of keycmp.hpp
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -47,6 +57,7 @@
 
 #include "../../include/kwok_expo.h"
 #include "f64fmt.hpp"
+#include "keycmp.hpp"
 
 namespace {
 
@@ -85,9 +96,9 @@ struct DevHist {
 };
 
 struct DevGroup {
-  const uint32_t* blk_off;  // rows + 1 (NULL: no labels)
-  const char* blk;
-  const uint32_t* perm;     // per node's row range: the rows in key order (NULL: node rows)
+  const uint2* blk_ref;  // per row: {offset, length} of its block in the arena (NULL: no labels; length 0: never set)
+  const char* blk;       // the arena (8 readable bytes after every block)
+  const uint32_t* perm;  // per node's row range: the rows in key order (NULL: node rows)
 };
 
 struct ExpoArgs {
@@ -296,9 +307,10 @@ __global__ __launch_bounds__(W) void expo_node_kernel(ExpoArgs a) {
           alive = (a.alive[pod >> 5] >> (pod & 31u)) & 1u;
         }
         if (alive) {
-          if (G.blk_off) {
-            bo = G.blk_off[row];
-            bl = G.blk_off[row + 1] - bo;
+          if (G.blk_ref) {
+            const uint2 ref = G.blk_ref[row];
+            bo = ref.x;
+            bl = ref.y;
             // a rendered block is never empty ("{..}"); a histogram series counts once, not per line
             if (!kWrite && bl == 0 && k == 0) atomicAdd(&a.total[1], 1ull);
           }
@@ -448,13 +460,92 @@ __global__ __launch_bounds__(kFmtBlock) void expo_format_kernel(const double* __
   lens[i] = (uint8_t)kwkf64::format_f64(v[i], out + (size_t)i * kwkf64::kMaxBytes);
 }
 
+// Incremental commits (kwk_expo_commit_rows).  One staging buffer per call holds, in this order, the
+// table of every group's arenas, the scrape's DevGroup table, the scatter rows, the sort segments and
+// the bytes; the kernels read the tables from the device copy of the staging itself.
+struct ArenaDev {
+  char* base;  // a group's block arena, key arena, or its permutation array (as bytes)
+  uint2* ref;  // per row {offset, length} (NULL: the permutation)
+};
+constexpr uint32_t kArenas = 3;  // per group: 0 blocks, 1 keys, 2 permutation
+
+struct ScatterRow {
+  unsigned long long dst, src;  // byte offsets in the arena and in the staging
+  uint32_t len, row, arena, pad;
+};
+
+struct SortSeg {
+  uint32_t lo, hi, group, pad;  // rows [lo, hi) of a node
+};
+
+constexpr uint32_t kScatterBlock = 256;  // a wave per row
+constexpr uint32_t kSortBlock = 256;
+constexpr uint32_t kSortMax = KWK_EXPO_SORT_MAX_ROWS;  // a node's rows sorted on the device (their pairs fit LDS)
+// row i of the staging -> its arena slot and its {offset, length} pair
+__global__ __launch_bounds__(kScatterBlock) void expo_scatter_kernel(const ArenaDev* __restrict__ tab,
+                                                                     const ScatterRow* __restrict__ rows, uint32_t n,
+                                                                     const char* __restrict__ stage) {
+  const uint32_t i = blockIdx.x * (kScatterBlock / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+  if (i >= n) return;
+  const ScatterRow R = rows[i];
+  const ArenaDev A = tab[R.arena];
+  for (uint32_t b = lane; b < R.len; b += 64) A.base[R.dst + b] = stage[R.src + b];
+  if (lane == 0 && A.ref) A.ref[R.row] = make_uint2((uint32_t)R.dst, R.len);
+}
+
+// One workgroup per (node, group) segment: perm[lo .. hi) = the segment's rows in key order, ties by
+// row (std::stable_sort over ascending rows).  A rank sort: row i's place is the count of rows before
+// it in that order.  The pairs sit in LDS (every lane reads pair j at once: a broadcast), the keys are
+// read from the arena, a few KB per node that stay in the vector L1.
+// (Copying the node's keys to LDS first and comparing them there was measured and dropped: 44 KiB of
+// LDS per workgroup, and at 10k nodes the kernel took 7.4 ms against 6.2 ms — DESIGN.md "Incremental
+// label commits".)
+__global__ __launch_bounds__(kSortBlock) void expo_sort_kernel(const ArenaDev* __restrict__ tab,
+                                                               const SortSeg* __restrict__ segs) {
+  __shared__ uint2 s_ref[kSortMax];
+  const SortSeg S = segs[blockIdx.x];
+  const uint32_t n = S.hi - S.lo;
+  if (S.hi < S.lo || n > kSortMax) return;  // (the host sorts a larger segment itself)
+  const ArenaDev K = tab[kArenas * S.group + 1];
+  uint32_t* perm = reinterpret_cast<uint32_t*>(tab[kArenas * S.group + 2].base);
+  for (uint32_t i = threadIdx.x; i < n; i += kSortBlock) s_ref[i] = K.ref[S.lo + i];
+  __syncthreads();
+  for (uint32_t i = threadIdx.x; i < n; i += kSortBlock) {
+    const uint2 ri = s_ref[i];
+    uint32_t rank = 0;
+    for (uint32_t j = 0; j < n; ++j) {
+      const uint2 rj = s_ref[j];
+      const int c = kwkkey::compare(K.base + rj.x, rj.y, K.base + ri.x, ri.y);
+      rank += (c < 0 || (c == 0 && j < i)) ? 1u : 0u;
+    }
+    perm[S.lo + rank] = S.lo + i;
+  }
+}
+
+// a group's blocks or keys on the device: rows at any offset of one buffer, and what the host knows of it
+struct Arena {
+  char* d = nullptr;
+  uint2* d_ref = nullptr;
+  uint64_t size = 0, tail = 0;     // bytes allocated; the first free byte (tail + 8 <= size, both multiples of 8)
+  std::vector<uint32_t> off, cap;  // per row: its slot
+};
+
 struct Group {
   uint32_t dim = 0, n_labels = 0;
   std::vector<std::string> blocks, keys;  // per row
-  uint32_t* d_blk_off = nullptr;
-  char* d_blk = nullptr;
+  std::vector<uint32_t> dirty;            // rows set since the last commit of either kind
+  std::vector<uint8_t> is_dirty;          // per row
+  Arena blk, key;                         // key: groups with a permutation only
   uint32_t* d_perm = nullptr;
 };
+
+struct Pending {  // device buffers replaced by an incremental commit: freed once the stream has passed `ev`
+  hipEvent_t ev;
+  std::vector<void*> ptrs;
+};
+
+constexpr uint64_t kArenaMax = 0xFFFFFFF8ull;  // 32-bit offsets
+inline uint64_t up8(uint64_t x) { return (x + 7ull) & ~7ull; }
 
 }  // namespace
 
@@ -486,13 +577,39 @@ struct kwk_expo {
   hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   bool committed = false, scraped = false;
   uint32_t last_nodes = 0;
+  // incremental commits
+  bool full = false;               // a full commit has laid the arenas out (and no later call left them half written)
+  hipStream_t aux = nullptr;       // the layout totals are read here, beside the engine's stream
+  uint32_t* h_totals = nullptr;    // pinned: the device's node_ptr[n_nodes], cptr[n_pods]
+  char* h_stage = nullptr;         // pinned staging and its device copy
+  char* d_stage = nullptr;
+  uint64_t h_stage_cap = 0, d_stage_cap = 0;
+  hipEvent_t ev_stage = nullptr;   // the last copy out of h_stage
+  bool stage_busy = false;
+  hipEvent_t ev_rows[3] = {nullptr, nullptr, nullptr};  // around the last commit's scatter and sort kernels
+  bool rows_timed = false;
+  std::vector<Pending> pending;
 
   ~kwk_expo() {
     hipSetDevice(device);
     void* s = nullptr;
     if (eng && kwk_stream(eng, &s) == KWK_OK && s) hipStreamSynchronize(static_cast<hipStream_t>(s));
+    if (aux) {
+      hipStreamSynchronize(aux);
+      hipStreamDestroy(aux);
+    }
+    for (Pending& p : pending) {
+      hipEventDestroy(p.ev);
+      for (void* q : p.ptrs) hipFree(q);
+    }
+    if (h_totals) hipHostFree(h_totals);
+    if (h_stage) hipHostFree(h_stage);
+    if (d_stage) hipFree(d_stage);
+    if (ev_stage) hipEventDestroy(ev_stage);
+    for (hipEvent_t e : ev_rows)
+      if (e) hipEventDestroy(e);
     for (Group& g : groups)
-      for (void* p : {(void*)g.d_blk_off, (void*)g.d_blk, (void*)g.d_perm})
+      for (void* p : {(void*)g.blk.d, (void*)g.blk.d_ref, (void*)g.key.d, (void*)g.key.d_ref, (void*)g.d_perm})
         if (p) hipFree(p);
     for (void* p : {(void*)d_fam, (void*)d_grp, (void*)d_lits, (void*)d_pod_of, (void*)d_node_bytes, (void*)d_offsets,
                     (void*)d_total, (void*)d_out, (void*)d_stash, (void*)d_hist, (void*)d_hlines})
@@ -556,8 +673,57 @@ kwk_status refresh_layout(kwk_expo* ex) {
   for (Group& g : ex->groups) {
     g.blocks.resize(group_rows(ex, g.dim));
     g.keys.resize(group_rows(ex, g.dim));
+    g.is_dirty.resize(group_rows(ex, g.dim));
   }
   return KWK_OK;
+}
+
+// frees what earlier incremental commits replaced, where the stream has passed their event
+// (all = true: the stream is idle)
+void drain_pending(kwk_expo* ex, bool all) {
+  size_t kept = 0;
+  for (Pending& p : ex->pending) {
+    if (all || hipEventQuery(p.ev) == hipSuccess) {
+      for (void* q : p.ptrs) hipFree(q);
+      hipEventDestroy(p.ev);
+    } else {
+      if (&ex->pending[kept] != &p) ex->pending[kept] = std::move(p);
+      ++kept;
+    }
+  }
+  ex->pending.resize(kept);
+}
+
+// a full commit's layout of one arena: the set rows packed in row order, slack at the tail
+kwk_status pack_arena(kwk_expo* ex, Arena& a, const std::vector<std::string>& items, const char* what) {
+  const size_t rows = items.size();
+  a.off.assign(rows, 0u);
+  a.cap.assign(rows, 0u);
+  std::vector<uint2> ref(rows);
+  uint64_t total = 0;
+  for (size_t r = 0; r < rows; ++r) {
+    const uint64_t n = items[r].size();
+    if (total + n + 8 > kArenaMax) return fail(KWK_ECAP, std::string("more than 4 GiB of label ") + what + " in a group");
+    a.off[r] = (uint32_t)total;
+    a.cap[r] = (uint32_t)n;
+    ref[r] = make_uint2((uint32_t)total, (uint32_t)n);
+    total += n;
+  }
+  a.tail = up8(total);
+  a.size = std::min<uint64_t>(kArenaMax, a.tail + up8(a.tail / 8) + 4096);
+  std::string blob;
+  blob.reserve(a.tail + 8);
+  for (const std::string& b : items) blob += b;
+  blob.append(a.tail + 8 - total, '\0');  // read as 8-byte words
+  for (void* p : {(void*)a.d, (void*)a.d_ref})
+    if (p) HIP_TRY(hipFree(p));
+  a.d = nullptr;
+  a.d_ref = nullptr;
+  void* d = nullptr;
+  HIP_TRY(hipMalloc(&d, (size_t)a.size));
+  a.d = static_cast<char*>(d);
+  if (kwk_status st = copy_in(ex, a.d, blob.data(), blob.size())) return st;
+  return replace(ex, &a.d_ref, ref.data(), ref.size());
 }
 
 }  // namespace
@@ -659,6 +825,10 @@ kwk_status create(kwk_engine* pods, uint32_t n_nodes, const kwk_expo_program* pr
     HIP_TRY(hipMalloc(&ex->d_total, 16));
     HIP_TRY(hipMemsetAsync(ex->d_total, 0, 16, ex->stream));
     for (hipEvent_t& e : ex->ev) HIP_TRY(hipEventCreate(&e));
+    for (hipEvent_t& e : ex->ev_rows) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(hipEventCreateWithFlags(&ex->ev_stage, hipEventDisableTiming));
+    HIP_TRY(hipStreamCreateWithFlags(&ex->aux, hipStreamNonBlocking));
+    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&ex->h_totals), 8, hipHostMallocDefault));
     return KWK_OK;
   };
   if (kwk_status st = init()) {
@@ -707,6 +877,10 @@ kwk_status kwk_expo_set_labels(kwk_expo* ex, uint32_t group, uint32_t first, uin
   for (uint32_t i = 0; i < n; ++i) {
     g.blocks[first + i].assign(blocks + block_offsets[i], blocks + block_offsets[i + 1]);
     g.keys[first + i].assign(keys + key_offsets[i], keys + key_offsets[i + 1]);
+    if (!g.is_dirty[first + i]) {
+      g.is_dirty[first + i] = 1;
+      g.dirty.push_back(first + i);
+    }
   }
   ex->committed = false;
   return KWK_OK;
@@ -718,6 +892,8 @@ kwk_status kwk_expo_commit(kwk_expo* ex) {
   if (kwk_status st = bind(ex)) return st;
   if (kwk_status st = refresh_layout(ex)) return st;
   HIP_TRY(hipStreamSynchronize(ex->stream));
+  ex->full = ex->committed = false;  // until every arena is laid out again
+  drain_pending(ex, true);
   // a node's family is walked as rows x lines of a series in 32 bits
   for (uint32_t j = 0; j < ex->n_nodes; ++j)
     if ((uint64_t)(ex->h_cptr[ex->h_node_ptr[j + 1]] - ex->h_cptr[ex->h_node_ptr[j]]) * ex->max_lines > 0xFFFFFFFFull ||
@@ -731,23 +907,10 @@ kwk_status kwk_expo_commit(kwk_expo* ex) {
   for (size_t gi = 0; gi < ex->groups.size(); ++gi) {
     Group& g = ex->groups[gi];
     const size_t rows = g.blocks.size();
-    if (g.n_labels) {
-      std::vector<uint32_t> off(rows + 1);
-      uint64_t total = 0;
-      for (size_t r = 0; r < rows; ++r) {
-        off[r] = (uint32_t)total;
-        total += g.blocks[r].size();
-        if (total > 0xFFFFFFFFull) return fail(KWK_ECAP, "more than 4 GiB of label blocks in a group");
-      }
-      off[rows] = (uint32_t)total;
-      std::string blob;
-      blob.reserve(total + 8);
-      for (const std::string& b : g.blocks) blob += b;
-      blob.append(8, '\0');  // read as 8-byte words
-      if (kwk_status st = replace(ex, &g.d_blk_off, off.data(), off.size())) return st;
-      if (kwk_status st = replace(ex, &g.d_blk, blob.data(), blob.size())) return st;
-    }
+    if (g.n_labels)
+      if (kwk_status st = pack_arena(ex, g.blk, g.blocks, "blocks")) return st;
     if (g.dim != KWK_METRIC_DIM_NODE) {
+      if (kwk_status st = pack_arena(ex, g.key, g.keys, "sort keys")) return st;
       std::vector<uint32_t> perm(rows);
       std::iota(perm.begin(), perm.end(), 0u);
       const std::vector<uint32_t>& first = ex->h_node_ptr;
@@ -759,12 +922,237 @@ kwk_status kwk_expo_commit(kwk_expo* ex) {
       }
       if (kwk_status st = replace(ex, &g.d_perm, perm.data(), perm.size())) return st;
     }
-    dg[gi] = DevGroup{g.d_blk_off, g.d_blk, g.d_perm};
+    dg[gi] = DevGroup{g.blk.d_ref, g.blk.d, g.d_perm};
+    g.is_dirty.assign(rows, 0);
+    g.dirty.clear();
   }
   if (kwk_status st = replace(ex, &ex->d_grp, dg.data(), dg.size())) return st;
   ex->committed = true;
+  ex->full = true;
   return KWK_OK;
 }
+
+kwk_status kwk_expo_commit_rows(kwk_expo* ex) {
+  ErrScope es_(ex ? &ex->err : nullptr);
+  if (!ex) return fail(KWK_EINVAL, "null writer");
+  if (!ex->full) return fail(KWK_ESTATE, "kwk_expo_commit must come first: kwk_expo_commit_rows updates a full commit's layout");
+  if (kwk_status st = bind(ex)) return st;
+  // the engine's layout is the one the arenas and permutations were laid out for: its two totals, read on a
+  // stream of this writer's own (the engine's stream is not waited for)
+  const uint32_t *np = nullptr, *cp = nullptr, *al = nullptr;
+  if (kwk_metrics_series_device(ex->eng, ex->n_nodes, 0, &np, &cp, &al) != KWK_OK)
+    return fail(KWK_ESTATE, std::string("the engine's layout changed (kwk_metrics_series_device: ") + kwk_last_error(ex->eng) +
+                            "): kwk_expo_commit re-reads it");
+  HIP_TRY(hipMemcpyAsync(&ex->h_totals[0], np + ex->n_nodes, 4, hipMemcpyDeviceToHost, ex->aux));
+  HIP_TRY(hipStreamSynchronize(ex->aux));
+  if (ex->h_totals[0] == ex->n_pods) {
+    HIP_TRY(hipMemcpyAsync(&ex->h_totals[1], cp + ex->n_pods, 4, hipMemcpyDeviceToHost, ex->aux));
+    HIP_TRY(hipStreamSynchronize(ex->aux));
+  }
+  if (ex->h_totals[0] != ex->n_pods || ex->h_totals[1] != ex->n_cont)
+    return fail(KWK_ESTATE, "the engine's pod or container count (" + std::to_string(ex->h_totals[0]) + " pods) is not the last "
+                            "full commit's (" + std::to_string(ex->n_pods) + " pods, " + std::to_string(ex->n_cont) +
+                            " containers): kwk_expo_commit re-reads the layout");
+  drain_pending(ex, false);
+
+  // the plan: what every arena appends, the (node, group) segments to sort, the staging's size
+  const size_t n_groups = ex->groups.size();
+  struct Grow { Arena* a; uint64_t size; };
+  std::vector<Grow> grow;
+  std::vector<SortSeg> segs, big;  // sorted by expo_sort_kernel; beyond kSortMax rows, sorted here
+  uint64_t n_rows = 0, n_bytes = 0;
+  for (size_t gi = 0; gi < n_groups; ++gi) {
+    Group& g = ex->groups[gi];
+    if (g.dirty.empty()) continue;
+    std::sort(g.dirty.begin(), g.dirty.end());
+    const bool sorted = g.dim != KWK_METRIC_DIM_NODE;
+    uint64_t need_blk = 0, need_key = 0;
+    uint32_t node = 0;
+    bool have_node = false;
+    auto first_row = [&](uint32_t j) { return g.dim == KWK_METRIC_DIM_POD ? ex->h_node_ptr[j] : ex->h_cptr[ex->h_node_ptr[j]]; };
+    for (uint32_t r : g.dirty) {
+      if (g.n_labels) {
+        const uint64_t n = g.blocks[r].size();
+        if (n > g.blk.cap[r]) need_blk += up8(n);
+        n_bytes += up8(n);
+        ++n_rows;
+      }
+      if (!sorted) continue;
+      const uint64_t n = g.keys[r].size();
+      if (n > g.key.cap[r]) need_key += up8(n);
+      n_bytes += up8(n);
+      ++n_rows;
+      uint32_t j = have_node ? node : 0;
+      while (first_row(j + 1) <= r) ++j;  // the rows ascend, so do their nodes
+      if (!have_node || j != node) {
+        const SortSeg s{first_row(j), first_row(j + 1), (uint32_t)gi, 0u};
+        if (s.hi - s.lo > kSortMax) {
+          big.push_back(s);
+          n_bytes += up8(4ull * (s.hi - s.lo));
+          ++n_rows;
+        } else if (s.hi - s.lo > 1) {  // (a segment of one row is its own order)
+          segs.push_back(s);
+        }
+        node = j;
+        have_node = true;
+      }
+    }
+    const uint64_t need[2] = {need_blk, need_key};
+    Arena* arena[2] = {&g.blk, &g.key};
+    for (int k = 0; k < 2; ++k) {
+      Arena& a = *arena[k];
+      if (!need[k] || a.tail + need[k] + 8 <= a.size) continue;
+      if (a.tail + need[k] + 8 > kArenaMax)
+        return fail(KWK_ECAP, "group " + std::to_string(gi) + ": its label " + (k ? "sort keys" : "blocks") +
+                              " would pass 4 GiB (32-bit offsets): kwk_expo_commit compacts the storage");
+      uint64_t size = a.size;
+      while (size < a.tail + need[k] + 8) size = std::min<uint64_t>(kArenaMax, 2 * size);
+      grow.push_back(Grow{&a, size});
+    }
+  }
+  if (!n_rows) {  // (rows of a node group without labels have nothing on the device)
+    for (Group& g : ex->groups) {
+      for (uint32_t r : g.dirty) g.is_dirty[r] = 0;
+      g.dirty.clear();
+    }
+    ex->committed = true;
+    return KWK_OK;
+  }
+  if (n_rows > 0xFFFFFFFFull || segs.size() > 0x7FFFFFFFull)
+    return fail(KWK_ECAP, "more than 2^32 rows in one incremental commit: kwk_expo_commit");
+  const uint64_t tab_at = 0, grp_at = up8(tab_at + sizeof(ArenaDev) * kArenas * n_groups);
+  const uint64_t rows_at = up8(grp_at + sizeof(DevGroup) * n_groups), segs_at = rows_at + sizeof(ScatterRow) * n_rows;
+  const uint64_t bytes_at = up8(segs_at + sizeof(SortSeg) * segs.size()), stage_bytes = bytes_at + n_bytes;
+
+  Pending pend{nullptr, {}};
+  auto run = [&]() -> kwk_status {
+    // the staging buffer is this call's once the last copy out of it is done
+    if (ex->stage_busy) HIP_TRY(hipEventSynchronize(ex->ev_stage));
+    ex->stage_busy = false;
+    if (stage_bytes > ex->h_stage_cap) {
+      if (ex->h_stage) HIP_TRY(hipHostFree(ex->h_stage));
+      ex->h_stage = nullptr;
+      ex->h_stage_cap = 0;
+      HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&ex->h_stage), (size_t)(stage_bytes + stage_bytes / 2), hipHostMallocDefault));
+      ex->h_stage_cap = stage_bytes + stage_bytes / 2;
+    }
+    if (stage_bytes > ex->d_stage_cap) {
+      if (ex->d_stage) pend.ptrs.push_back(ex->d_stage);
+      ex->d_stage = nullptr;
+      ex->d_stage_cap = 0;
+      HIP_TRY(hipMalloc(reinterpret_cast<void**>(&ex->d_stage), (size_t)(stage_bytes + stage_bytes / 2)));
+      ex->d_stage_cap = stage_bytes + stage_bytes / 2;
+    }
+    // an arena whose tail is full doubles: its rows keep their offsets
+    for (const Grow& gr : grow) {
+      void* d = nullptr;
+      HIP_TRY(hipMalloc(&d, (size_t)gr.size));
+      HIP_TRY(hipMemcpyAsync(d, gr.a->d, (size_t)gr.a->tail + 8, hipMemcpyDeviceToDevice, ex->stream));
+      pend.ptrs.push_back(gr.a->d);
+      gr.a->d = static_cast<char*>(d);
+      gr.a->size = gr.size;
+    }
+    char* h = ex->h_stage;
+    ArenaDev* tab = reinterpret_cast<ArenaDev*>(h + tab_at);
+    DevGroup* dgrp = reinterpret_cast<DevGroup*>(h + grp_at);
+    ScatterRow* rows = reinterpret_cast<ScatterRow*>(h + rows_at);
+    uint64_t at = bytes_at, nr = 0;
+    for (size_t gi = 0; gi < n_groups; ++gi) {
+      Group& g = ex->groups[gi];
+      tab[kArenas * gi + 0] = ArenaDev{g.blk.d, g.blk.d_ref};
+      tab[kArenas * gi + 1] = ArenaDev{g.key.d, g.key.d_ref};
+      tab[kArenas * gi + 2] = ArenaDev{reinterpret_cast<char*>(g.d_perm), nullptr};
+      dgrp[gi] = DevGroup{g.blk.d_ref, g.blk.d, g.d_perm};
+      for (uint32_t r : g.dirty) {
+        for (uint32_t k = 0; k < 2; ++k) {
+          if (k == 0 ? g.n_labels == 0 : g.dim == KWK_METRIC_DIM_NODE) continue;
+          Arena& a = k ? g.key : g.blk;
+          const std::string& s = k ? g.keys[r] : g.blocks[r];
+          const uint32_t n = (uint32_t)s.size();
+          if (n > a.cap[r]) {  // the slot is too small: a new one at the tail
+            a.off[r] = (uint32_t)a.tail;
+            a.cap[r] = (uint32_t)up8(n);
+            a.tail += up8(n);
+          }
+          memcpy(h + at, s.data(), n);
+          rows[nr++] = ScatterRow{a.off[r], at, n, r, (uint32_t)(kArenas * gi + k), 0u};
+          at += up8(n);
+        }
+        g.is_dirty[r] = 0;
+      }
+      g.dirty.clear();
+    }
+    for (const SortSeg& s : big) {
+      const Group& g = ex->groups[s.group];
+      uint32_t* p = reinterpret_cast<uint32_t*>(h + at);
+      std::iota(p, p + (s.hi - s.lo), s.lo);
+      std::stable_sort(p, p + (s.hi - s.lo), [&](uint32_t x, uint32_t y) { return g.keys[x] < g.keys[y]; });
+      rows[nr++] = ScatterRow{4ull * s.lo, at, 4u * (s.hi - s.lo), 0u, kArenas * s.group + 2, 0u};
+      at += up8(4ull * (s.hi - s.lo));
+    }
+    if (!segs.empty()) memcpy(h + segs_at, segs.data(), sizeof(SortSeg) * segs.size());
+    HIP_TRY(hipMemcpyAsync(ex->d_stage, h, (size_t)stage_bytes, hipMemcpyHostToDevice, ex->stream));
+    HIP_TRY(hipEventRecord(ex->ev_stage, ex->stream));
+    ex->stage_busy = true;
+    if (!grow.empty())
+      HIP_TRY(hipMemcpyAsync(ex->d_grp, ex->d_stage + grp_at, sizeof(DevGroup) * n_groups, hipMemcpyDeviceToDevice, ex->stream));
+    const ArenaDev* d_tab = reinterpret_cast<const ArenaDev*>(ex->d_stage + tab_at);
+    HIP_TRY(hipEventRecord(ex->ev_rows[0], ex->stream));
+    hipLaunchKernelGGL(expo_scatter_kernel, dim3((uint32_t)((nr + kScatterBlock / 64 - 1) / (kScatterBlock / 64))),
+                       dim3(kScatterBlock), 0, ex->stream, d_tab, reinterpret_cast<const ScatterRow*>(ex->d_stage + rows_at),
+                       (uint32_t)nr, ex->d_stage);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ex->ev_rows[1], ex->stream));
+    if (!segs.empty()) {
+      hipLaunchKernelGGL(expo_sort_kernel, dim3((uint32_t)segs.size()), dim3(kSortBlock), 0, ex->stream, d_tab,
+                         reinterpret_cast<const SortSeg*>(ex->d_stage + segs_at));
+      HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(ex->ev_rows[2], ex->stream));
+    ex->rows_timed = true;
+    if (!pend.ptrs.empty()) {
+      HIP_TRY(hipEventCreateWithFlags(&pend.ev, hipEventDisableTiming));
+      HIP_TRY(hipEventRecord(pend.ev, ex->stream));
+      ex->pending.push_back(pend);
+      pend.ptrs.clear();
+    }
+    return KWK_OK;
+  };
+  const kwk_status st = run();
+  if (st != KWK_OK) {  // the arenas may be half written: only a full commit makes them whole
+    ex->full = ex->committed = false;
+    hipStreamSynchronize(ex->stream);
+    if (pend.ev) hipEventDestroy(pend.ev);
+    for (void* q : pend.ptrs) hipFree(q);
+    return st;
+  }
+  ex->committed = true;
+  return KWK_OK;
+}
+
+kwk_status kwk_expo_commit_rows_elapsed(kwk_expo* ex, float ms[2]) {
+  ErrScope es_(ex ? &ex->err : nullptr);
+  if (!ex || !ms) return fail(KWK_EINVAL, "null argument");
+  if (!ex->rows_timed) return fail(KWK_ESTATE, "a kwk_expo_commit_rows that enqueued work must come first");
+  if (kwk_status st = bind(ex)) return st;
+  HIP_TRY(hipEventSynchronize(ex->ev_rows[2]));
+  for (int i = 0; i < 2; ++i) HIP_TRY(hipEventElapsedTime(&ms[i], ex->ev_rows[i], ex->ev_rows[i + 1]));
+  return KWK_OK;
+}
+
+kwk_status kwk_expo_read_perm(kwk_expo* ex, uint32_t group, uint32_t* out) {
+  ErrScope es_(ex ? &ex->err : nullptr);
+  if (!ex) return fail(KWK_EINVAL, "null writer");
+  if (group >= ex->groups.size()) return fail(KWK_EINVAL, "label group out of range");
+  const Group& g = ex->groups[group];
+  if (g.dim == KWK_METRIC_DIM_NODE) return fail(KWK_EINVAL, "a node-dimension group has no permutation");
+  if (!ex->full) return fail(KWK_ESTATE, "kwk_expo_commit must come first");
+  if (g.blocks.size() && !out) return fail(KWK_EINVAL, "null argument");
+  if (kwk_status st = bind(ex)) return st;
+  return copy_out(ex, out, g.d_perm, 4 * g.blocks.size());
+}
+
+int kwk_expo_key_compare(const char* a, uint32_t na, const char* b, uint32_t nb) { return kwkkey::compare(a, na, b, nb); }
 
 kwk_status kwk_expo_reserve(kwk_expo* ex, uint64_t max_bytes) {
   ErrScope es_(ex ? &ex->err : nullptr);

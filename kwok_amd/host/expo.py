@@ -25,6 +25,7 @@ from .native_metrics import KIND_HISTOGRAM, ExpoHistProgramStruct, ExpoProgramSt
 LIB_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "lib", "libkwok_expo.so")
 DIM_NODE, DIM_POD, DIM_CONTAINER = 0, 1, 2
 MAX_FLOAT_BYTES = 24
+SORT_MAX_ROWS = 1024  # KWK_EXPO_SORT_MAX_ROWS: a node's rows of a group that kwk_expo_commit_rows sorts on the device
 
 _lib = None
 
@@ -63,9 +64,15 @@ def lib():
     L.kwk_expo_format_values.argtypes = [vp, vp, u32, vp, vp]
     L.kwk_expo_format_f64.argtypes = [C.c_double, vp]
     L.kwk_expo_format_f64.restype = u32
+    L.kwk_expo_commit_rows.argtypes = [vp]
+    L.kwk_expo_commit_rows_elapsed.argtypes = [vp, C.POINTER(C.c_float)]
+    L.kwk_expo_read_perm.argtypes = [vp, u32, vp]
+    L.kwk_expo_key_compare.argtypes = [C.c_char_p, u32, C.c_char_p, u32]
+    L.kwk_expo_key_compare.restype = C.c_int
     for n in ("kwk_expo_create", "kwk_expo_create_hist", "kwk_expo_destroy", "kwk_expo_set_labels", "kwk_expo_commit", "kwk_expo_reserve",
               "kwk_expo_scrape", "kwk_expo_result", "kwk_expo_device", "kwk_expo_copy", "kwk_expo_elapsed",
-              "kwk_expo_set_width", "kwk_expo_format_values"):
+              "kwk_expo_set_width", "kwk_expo_format_values", "kwk_expo_commit_rows", "kwk_expo_commit_rows_elapsed",
+              "kwk_expo_read_perm"):
         getattr(L, n).restype = C.c_int32
     _lib = L
     return L
@@ -76,6 +83,11 @@ def format_f64(v: float) -> bytes:
     buf = C.create_string_buffer(MAX_FLOAT_BYTES)
     n = lib().kwk_expo_format_f64(float(v), buf)
     return buf.raw[:n]
+
+
+def key_compare(a: bytes, b: bytes) -> int:
+    """kwk_expo_key_compare: the host build of the device sort's comparator (< 0, 0, > 0)."""
+    return int(lib().kwk_expo_key_compare(a, len(a), b, len(b)))
 
 
 def _pack(items: Sequence[bytes]):
@@ -181,7 +193,27 @@ class Exposition:
             flush()
 
     def commit(self):
+        """kwk_expo_commit: the full commit (re-reads the layout, sorts and uploads every row)."""
         self._check(lib().kwk_expo_commit(self.h), "kwk_expo_commit")
+
+    def commit_rows(self):
+        """kwk_expo_commit_rows: only the rows set since the last commit, enqueued on the engine's
+        stream (the scatter and sort kernels); ExpoError KWK_ESTATE when a full commit is due."""
+        self._check(lib().kwk_expo_commit_rows(self.h), "kwk_expo_commit_rows")
+
+    def commit_rows_elapsed_ms(self):
+        """(scatter, sort) kernel times of the last commit_rows that enqueued work, by HIP events."""
+        ms = (C.c_float * 2)()
+        self._check(lib().kwk_expo_commit_rows_elapsed(self.h, ms), "kwk_expo_commit_rows_elapsed")
+        return tuple(float(x) for x in ms)
+
+    def read_perm(self, group: int) -> np.ndarray:
+        """kwk_expo_read_perm: a pod or container group's device permutation (its rows)."""
+        dim = self.groups[group][0] if 0 <= group < len(self.groups) else DIM_POD
+        rows = int(self.node_ptr[-1]) if dim == DIM_POD else int(self.cptr[-1]) if dim == DIM_CONTAINER else 1
+        out = np.zeros(max(1, rows), dtype=np.uint32)
+        self._check(lib().kwk_expo_read_perm(self.h, group, abi.ptr(out)), "kwk_expo_read_perm")
+        return out[:rows]
 
     def set_width(self, width: int):
         self._check(lib().kwk_expo_set_width(self.h, width), "kwk_expo_set_width")

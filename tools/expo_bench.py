@@ -18,6 +18,13 @@ container-dimension histogram of 5 visible buckets over pod.Usage("memory") /
 pod.Usage("cpu", container.name), compiled with expo_histograms (kwk_expo_create_hist); the
 scalar-only CR is measured first in the same process and recorded beside it ("scalar_same_run"),
 with the histogram write pass's bytes/s relative to the scalar pass's.
+
+--churn: the label-commit leg (default --out profiles/r10/expo_commit_bench.json --tag churn_c4).
+A seeded 0.1 %, 1 % and 10 % of the pods are renamed; per fraction, in one process, the host wall
+time of kwk_expo_set_labels + kwk_expo_commit_rows, the HIP-event times of its scatter and sort
+kernels, and the wall time of kwk_expo_set_labels + a full kwk_expo_commit of the same changes
+(medians of 5 after 1 warm-up).  The permutations and sampled nodes' text after the incremental
+commit are compared with a full commit's.
 """
 import argparse
 import copy
@@ -160,6 +167,115 @@ def timed(ex, pods, t, dt, chunks, scrapes, warmup):
             "kernels_GBps": round(total_bytes / (kern * 1e-3) / 1e9, 1), "scrapes": scrapes, "warmup": warmup}, t
 
 
+def _label_calls(ex, ncont, slots, version):
+    """The kwk_expo_set_labels arguments (ctypes, built outside the timed region) that rename pod
+    `i` of `slots` to pod-<i>-v<version>: one call per pod for the pod group and one for its
+    containers' rows."""
+    import ctypes as C
+    from kwok_amd.host.expo import DIM_CONTAINER, DIM_POD
+    calls = []
+    one = (C.c_uint32 * 2)
+    for g, (dim, _) in enumerate(ex.groups):
+        if dim == DIM_POD:
+            for i in slots:
+                name = b"pod-%d-v%s" % (i, version)
+                blk, key = b'{namespace="default",pod="%s"}' % name, b"default\0%s\0" % name
+                calls.append((ex.h, g, int(i), 1, one(0, len(blk)), blk, one(0, len(key)), key))
+        elif dim == DIM_CONTAINER:
+            for i in slots:
+                name = b"pod-%d-v%s" % (i, version)
+                k = int(ncont[i])
+                blks = [b'{container="container-%d",namespace="default",pod="%s"}' % (j, name) for j in range(k)]
+                keys = [b"container-%d\0default\0%s\0" % (j, name) for j in range(k)]
+                bo, ko = (C.c_uint32 * (k + 1))(), (C.c_uint32 * (k + 1))()
+                for j in range(k):
+                    bo[j + 1] = bo[j] + len(blks[j])
+                    ko[j + 1] = ko[j] + len(keys[j])
+                calls.append((ex.h, g, int(ex.cptr[i]), k, bo, b"".join(blks), ko, b"".join(keys)))
+    return calls
+
+
+def churn(args):
+    """--churn: the cost of bringing relabelled pods' rows up to date, incremental
+    (kwk_expo_commit_rows) against full (kwk_expo_commit), at 0.1 %, 1 % and 10 % of the pods."""
+    from kwok_amd.host.expo import DIM_NODE, Exposition, lib
+    pods, mp, pvars, pidx, node_ptr, t = build_rig(args.nodes, args.pods, args.seed, None)
+    ex = Exposition(pods, mp.native)
+    upload_labels(ex, mp, pvars, pidx, args.pods)
+    ex.commit()
+    L = lib()
+    ncont = np.array([len(v["spec"]["containers"]) for v in pvars])[pidx]
+    rng = np.random.default_rng(args.seed)
+    reps, warm = 5, 1
+    res = {"workload": f"{args.nodes} nodes / {args.pods} pods (C4 shape), metrics-resource.yaml; every relabelled pod's "
+                       "pod row and container rows are set (one kwk_expo_set_labels call per pod and group) and committed",
+           "method": f"medians of {reps} after {warm} warm-up, in one process, the incremental and the full leg alternating; every "
+                     "round renames the same pods to a longer name than the round before, so every row outgrows its slot and "
+                     "is appended (the arenas grow when the tail fills: the dearest case of the incremental path); "
+                     "host_ms = wall time of the calls (kwk_expo_commit_rows only enqueues), kernels by HIP events, "
+                     "done_ms = wall time until the stream has finished the commit",
+           "fractions": {}}
+
+    def set_all(calls):
+        for c in calls:
+            if L.kwk_expo_set_labels(*c) != 0:
+                raise SystemExit("kwk_expo_set_labels: " + L.kwk_expo_last_error(ex.h).decode())
+
+    version = 0
+    for frac in (0.001, 0.01, 0.1):
+        slots = np.sort(rng.choice(args.pods, size=max(1, int(args.pods * frac)), replace=False))
+        rows = {"set_labels_ms": [], "commit_rows_host_ms": [], "scatter_us": [], "sort_us": [], "commit_rows_done_ms": [],
+                "full_set_labels_ms": [], "full_commit_ms": []}
+        for k in range(warm + reps):
+            version += 1
+            calls = _label_calls(ex, ncont, slots, b"%s" % (b"y" * version))
+            t0 = time.perf_counter()
+            set_all(calls)
+            t1 = time.perf_counter()
+            ex.commit_rows()
+            t2 = time.perf_counter()
+            scatter_ms, sort_ms = ex.commit_rows_elapsed_ms()  # waits for the kernels
+            t3 = time.perf_counter()
+            version += 1
+            calls = _label_calls(ex, ncont, slots, b"%s" % (b"y" * version))
+            t4 = time.perf_counter()
+            set_all(calls)
+            t5 = time.perf_counter()
+            ex.commit()
+            t6 = time.perf_counter()
+            if k >= warm:
+                for name, v in (("set_labels_ms", (t1 - t0) * 1e3), ("commit_rows_host_ms", (t2 - t1) * 1e3),
+                                ("scatter_us", scatter_ms * 1e3), ("sort_us", sort_ms * 1e3),
+                                ("commit_rows_done_ms", (t3 - t1) * 1e3), ("full_set_labels_ms", (t5 - t4) * 1e3),
+                                ("full_commit_ms", (t6 - t5) * 1e3)):
+                    rows[name].append(v)
+        med = {k: round(float(np.median(v)), 3) for k, v in rows.items()}
+        med["pods"] = int(len(slots))
+        med["rows"] = int(len(slots) + ncont[slots].sum())
+        med["nodes_touched"] = int(len(np.unique(np.searchsorted(node_ptr, slots, side="right"))))
+        med["incremental_ms"] = round(med["set_labels_ms"] + med["commit_rows_done_ms"], 3)
+        med["full_ms"] = round(med["full_set_labels_ms"] + med["full_commit_ms"], 3)
+        med["full_over_incremental"] = round(med["full_ms"] / med["incremental_ms"], 1)
+        res["fractions"]["%g%%" % (frac * 100)] = med
+    # the two paths agree: the last fraction once more, incremental, against a full commit of the same state
+    version += 1
+    set_all(_label_calls(ex, ncont, slots, b"%s" % (b"y" * version)))
+    ex.commit_rows()
+    sample = [int(j) for j in np.linspace(0, args.nodes - 1, num=min(args.sample, args.nodes)).astype(int)]
+    pods.usage(t)
+    groups = [g for g, (dim, _) in enumerate(ex.groups) if dim != DIM_NODE]
+    perms = [ex.read_perm(g).copy() for g in groups]
+    texts = [ex.scrape(t, j, 1)[0] for j in sample]
+    ex.commit()
+    equal = all(np.array_equal(p, ex.read_perm(g)) for p, g in zip(perms, groups)) and \
+        texts == [ex.scrape(t, j, 1)[0] for j in sample]
+    res["equal_to_full_commit"] = {"permutations": len(groups), "sampled_nodes_text": len(sample), "equal": bool(equal)}
+    assert equal, "the incremental commit differs from the full commit"
+    ex.close()
+    pods.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--nodes", type=int, default=10_000)
@@ -175,10 +291,16 @@ def main():
                     help="render every label row with kwk_metric_labels_render (Exposition.set_pods): slow from Python")
     ap.add_argument("--hist", action="store_true",
                     help="the histogram leg (and the scalar-only CR in the same process): see the module docstring")
+    ap.add_argument("--churn", action="store_true",
+                    help="the label-commit leg: kwk_expo_commit_rows against kwk_expo_commit (see the module docstring)")
     args = ap.parse_args()
-    args.out = args.out or os.path.join(ROOT, "profiles", *(("r8", "expo_hist_bench.json") if args.hist else ("r7", "expo_bench.json")))
-    args.tag = args.tag or ("c4_hist" if args.hist else "c4")
-    if args.hist:
+    args.out = args.out or os.path.join(ROOT, "profiles", *(("r10", "expo_commit_bench.json") if args.churn else
+                                                           ("r8", "expo_hist_bench.json") if args.hist else
+                                                           ("r7", "expo_bench.json")))
+    args.tag = args.tag or ("churn_c4" if args.churn else "c4_hist" if args.hist else "c4")
+    if args.churn:
+        res = churn(args)
+    elif args.hist:
         scalar = leg(args, None)
         res = leg(args, hist_cr_text())
         res["scalar_same_run"] = scalar
