@@ -21,6 +21,16 @@
  * harness re-creates from spec).  A record with an item left to the host keeps its word: the host
  * sets it (kwk_emit_set_words) once it has rendered and applied that object's patches, as it
  * does after any kwk_replace / kwk_upsert.
+ *
+ * Emission from the hand-back ring (DESIGN.md §5 "Emission from the ring"): kwk_emit reads the
+ * engine's last list; kwk_emit_step reads the list of any step the engine's ring still holds
+ * (kwk_ring_view), in the format its compaction left — the 2-byte KWK_COMPACT_PACKED16 lists of
+ * the fused sweep included — so a host calls kwk_step_n(eng, n, ...) once and kwk_emit_step for
+ * step0 .. step0 + n - 1, each into an output set of its own (kwk_emit_reserve_sets), with no
+ * synchronisation in between, and reads the n emissions afterwards (kwk_emit_select).  Still
+ * refused: KWK_COMPACT_BITS lists, and any host intervention between the steps of a fused group
+ * (kwk_emit_set_words / _set_column for host-rendered items belong at group boundaries: the
+ * emissions of a group run in step order on the guard bits the earlier ones left).
  */
 #ifndef KWOK_EMIT_H
 #define KWOK_EMIT_H
@@ -94,12 +104,41 @@ kwk_status kwk_emit_set_words(kwk_emitter* em, uint32_t first, uint32_t n, const
 kwk_status kwk_emit_get_words(kwk_emitter* em, uint32_t first, uint32_t n, uint64_t* words);
 /* rows [first, first + n) of value column c: n * column_stride[c] bytes */
 kwk_status kwk_emit_set_column(kwk_emitter* em, uint32_t c, uint32_t first, uint32_t n, const uint8_t* data);
-/* output room: items and patch bytes one kwk_emit may produce */
+/* output room: items and patch bytes one kwk_emit may produce (in every output set; their number
+ * stays) */
 kwk_status kwk_emit_reserve(kwk_emitter* em, uint32_t max_items, uint64_t max_bytes);
 /* enqueue the emission of the engine's last compacted fired list (source: KWK_EMIT_FROM_*) */
 kwk_status kwk_emit(kwk_emitter* em, int64_t now_ns, uint32_t source);
-/* synchronise; the last emission's totals.  KWK_ECAP when they exceed the reservation: nothing was
- * written (words unchanged) — reserve more and emit the same list again */
+/* enqueue the emission of the ring list of step `step` (kwk_step's step / kwk_step_n's step0 + k;
+ * KWK_STEP_LAST: the engine's list) in whatever format its compaction left: KWK_COMPACT_REC, _PACKED
+ * or _PACKED16.  KWK_ESTATE with the engine's message when the ring no longer holds the step
+ * (kwk_fired_keep), and for a KWK_COMPACT_BITS list (the message names the format).  A list of no
+ * segments (a step that swept nothing) is empty: 0 items, 0 bytes.  Call it while the ring slot is
+ * intact (kwk_ring_view's rule: before the engine's next kwk_step_n call, for a call of at most
+ * kwk_fired_keep() steps). */
+kwk_status kwk_emit_step(kwk_emitter* em, uint64_t step, int64_t now_ns);
+/* Several emissions in flight.  An emitter has 1..8 output sets (items, offsets, bytes, totals and
+ * the elapsed-time events), one by default; every kwk_emit / kwk_emit_step writes the set after the
+ * previous emission's, in turn, so up to n_sets emissions are enqueued back to back and read
+ * afterwards.  kwk_emit_reserve_sets synchronises, gives every set room for max_items / max_bytes (a
+ * set that has to grow loses its outputs; another number of sets frees them all and starts the turn
+ * over).  kwk_emit_select makes kwk_emit_result / _stats / _device / _copy / _elapsed refer to the
+ * emission `back` before the last (0 = the last; < n_sets and < the emissions since the sets were
+ * made); every new emission selects 0 again.
+ *
+ * Overflow with emissions in flight (n_sets > 1).  An emission whose totals exceed its set writes
+ * nothing and leaves the words unchanged, and raises a flag on the device; every emission enqueued
+ * after it, before the host has noticed, finds the flag, writes nothing and leaves the words alone
+ * too (its step's emission would read the guard bits the failed one was meant to leave).
+ * kwk_emit_result of the failed emission and of each later one returns KWK_ECAP (the later ones'
+ * totals read 0), so the words are exactly those after the last emission that completed.  The flag
+ * is cleared by kwk_emit_reserve / _reserve_sets, and by the first emission enqueued after a reader
+ * has returned KWK_ECAP: the caller reserves more and emits again from the first failed step, and
+ * the result is exact.  With one set every emission stands alone, as it always did. */
+kwk_status kwk_emit_reserve_sets(kwk_emitter* em, uint32_t n_sets, uint32_t max_items, uint64_t max_bytes);
+kwk_status kwk_emit_select(kwk_emitter* em, uint32_t back);
+/* synchronise; the (selected) last emission's totals.  KWK_ECAP when they exceed the reservation:
+ * nothing was written (words unchanged) — reserve more and emit the same list again */
 kwk_status kwk_emit_result(kwk_emitter* em, uint32_t* n_items, uint64_t* n_bytes);
 /* kwk_emit_result plus the number of items emitted on the device (status KWK_EMIT_OK) */
 kwk_status kwk_emit_stats(kwk_emitter* em, uint32_t* n_items, uint32_t* n_emitted, uint64_t* n_bytes);

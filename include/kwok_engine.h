@@ -427,6 +427,27 @@ kwk_status kwk_fired_keep(kwk_engine* eng, uint32_t depth);
 kwk_status kwk_fired_fetch(kwk_engine* eng, uint64_t step, void* out, uint64_t cap_bytes, uint32_t* seg_counts,
                            uint32_t seg_cap, kwk_fetch_info* info);
 kwk_status kwk_fired_fetch_wait(kwk_engine* eng);
+/* A kept list where it lies on the device, by step: what kwk_fired_fetch copies, for an in-process
+ * consumer of every step of a kwk_step_n call, fused or not (the device patch emitter's
+ * kwk_emit_step, kwok_emit.h).  The step is looked up as kwk_fired_fetch does (the ring's newest slot
+ * first; KWK_STEP_LAST = the engine's list, KWK_ESTATE when it is not compacted); KWK_ESTATE "no
+ * kept list of step ..." when the ring no longer holds it.  Nothing is synchronised or copied.
+ * The pointers are for work enqueued on the engine's stream (kwk_stream) BEFORE the engine's next
+ * sweep or compaction — or, for a caller that counts, before the compaction that rewrites the slot:
+ * the ring holds the lists of the last kwk_fired_keep() compactions (at least 4), so every step of
+ * one kwk_step_n call of at most that many steps stays valid until the next call.  Nothing makes a
+ * compaction wait for a consumer on another stream.  A list whose n_segs is 0 (a step that swept nothing) is EMPTY
+ * whatever *count holds — every consumer applies that rule, as kwk_fired_fetch does.
+ * (The call is not named kwk_fired_*: that family stays the six format-parameterised entry
+ * points of ABI 3.) */
+typedef struct {
+  const void* list;            /* the dense list, in `format` */
+  const uint32_t* count;       /* device word: its length in records (KWK_COMPACT_BITS: {words, records}) */
+  const uint32_t* seg_counts;  /* KWK_COMPACT_PACKED16: records per segment, n_segs entries; else NULL */
+  uint32_t format, n_segs, region_slots, reserved;
+  uint64_t step;
+} kwk_fired_view; /* 48 bytes */
+kwk_status kwk_ring_view(kwk_engine* eng, uint64_t step, kwk_fired_view* out);
 /* pinned (page-locked) host buffers for kwk_fired_read / kwk_read / usage outputs, reused across steps */
 kwk_status kwk_alloc_host(uint64_t bytes, void** out);
 kwk_status kwk_free_host(void* p);

@@ -13,6 +13,12 @@
 //   emit_write_kernel  per tile again: each record's items / offsets, its guard word, then each wave
 //                      writes its 64 records' bytes (one contiguous span), 64 lanes over every literal
 //                      run and value, through an LDS window that leaves as 16-byte stores
+// A 2-byte ring list (kwk_emit_step of a KWK_COMPACT_PACKED16 slot) takes two more, before the size
+// kernel: emit_seg_base_kernel (the exclusive prefix of the records per segment) and
+// emit_tile_seg_kernel (every tile's first segment), from which the size and write kernels find each
+// record's segment, hence its slot.  Emissions rotate through output sets (kwk_emit_reserve_sets), so
+// the emissions of a fused group are enqueued back to back; a device flag stops the ones behind an
+// emission that exceeded its set.
 // The skeleton pieces and literal runs are staged in LDS when they fit (12 KiB of literals).
 // Roofline: HBM-bound on the patch bytes written (plus 8 bytes read per record and the literal
 // runs, L2-resident); the byte copy is 1-byte stores coalesced per wave.
@@ -89,7 +95,28 @@ struct EmitArgs {
   uint32_t now_len;
   char now[40];
   uint32_t lencache;                 // words' bits 24-31 cache the value lengths (emit_lens_kernel)
+  // several emissions in flight (kwk_emit_reserve_sets): nonzero once an emission exceeded its set —
+  // every kernel of the later ones then leaves at once (totals[4] = 1); sticky_on: this emission sets it
+  uint32_t* sticky;
+  uint32_t sticky_on;
+  // the 2-byte source (kSrc16: a KWK_COMPACT_PACKED16 ring list): the records, the records per segment,
+  // their exclusive prefix seg_base[n_segs + 1] (emit_seg_base_kernel) and each tile's first record's
+  // segment tile_seg (emit_tile_seg_kernel)
+  const uint16_t* p16;
+  const uint32_t* seg_counts;
+  uint32_t* seg_base;
+  uint32_t* tile_seg;
+  uint32_t n_segs, region_slots;
 };
+
+constexpr uint32_t kSrc32 = 0, kSrc16 = 1;  // the list's records: kwk_fired_rec / 4-byte packed | 2-byte
+// the records of the list the tile arrays cover
+template <uint32_t kSrc>
+__device__ __forceinline__ uint32_t list_len(const EmitArgs& a) {
+  const uint32_t n = min(*a.count, a.max_recs);
+  if constexpr (kSrc == kSrc16) return min(n, a.seg_base[a.n_segs]);  // (no record without a segment)
+  return n;
+}
 
 // per skeleton (LDS, built per block for this call's Now length): x = its fixed bytes (literal runs
 // and Now) | value slots << 24 (kSkszPieces: more than 4, count them piece by piece), y = the slots'
@@ -158,6 +185,61 @@ __device__ __forceinline__ Rec fetch(const EmitArgs& a, uint32_t r) {
     x.slot = f.slot;
     x.stage = f.stage;
   }
+  x.valid = x.slot < a.capacity;
+  return x;
+}
+
+// ---- the 2-byte source: which segment a dense record belongs to.  A 2-byte record holds the
+// offset inside its segment; record r of the dense list belongs to the segment s with
+// seg_base[s] <= r < seg_base[s + 1] (the upper bound of r: it steps over empty segments, equal
+// neighbours, and runs of them).  A tile is kTile consecutive records, so its records' segments are
+// the range from its first record's segment (tile_seg[t], written once per list by
+// emit_tile_seg_kernel: no search) to the next tile's first record's (the list's last segment for
+// the last tile): seg_base over that range goes to LDS when it is at most kSegWin entries, and each
+// record's binary search runs over that copy — over global memory otherwise, in both cases over the
+// tile's own range only.
+constexpr uint32_t kSegWin = 264;
+struct SegWin {
+  const uint32_t* base;  // seg_base + s0, or null: the LDS copy
+  uint32_t s0, n;        // entries [0, n]: segments s0 .. s0 + n - 1
+};
+// (LDS of the 2-byte instantiations only: a function's static, allocated where it is called)
+__device__ __forceinline__ uint32_t* seg_win_lds() {
+  __shared__ uint32_t w[kSegWin];
+  return w;
+}
+
+// every thread of the block, once per tile (block-uniform control flow; a barrier inside)
+__device__ __forceinline__ SegWin tile_segs(const EmitArgs& a, uint32_t t, uint32_t n, uint32_t* s_win) {
+  const uint32_t last = a.n_segs - 1u;
+  const uint32_t s0 = min(a.tile_seg[t], last);
+  const uint32_t s1 = max(s0, (t + 1u) * kTile < n ? min(a.tile_seg[t + 1u], last) : last);
+  const uint32_t cnt = s1 - s0 + 1u;
+  if (cnt < kSegWin) {
+    for (uint32_t j = threadIdx.x; j <= cnt; j += blockDim.x) s_win[j] = a.seg_base[s0 + j];
+    __syncthreads();
+    return SegWin{nullptr, s0, cnt};
+  }
+  return SegWin{a.seg_base + s0, s0, cnt};
+}
+
+template <typename P>
+__device__ __forceinline__ uint32_t seg_search(P base, uint32_t n, uint32_t r) {
+  uint32_t lo = 0, hi = n;  // base[lo] <= r < base[hi]
+  while (hi - lo > 1u) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (base[mid] <= r) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+
+__device__ __forceinline__ Rec fetch16(const EmitArgs& a, uint32_t r, const SegWin& w, const uint32_t* s_win) {
+  const uint32_t v = a.p16[r];
+  const uint32_t s = w.s0 + (w.base ? seg_search(w.base, w.n, r) : seg_search(s_win, w.n, r));
+  Rec x;
+  x.slot = s * a.region_slots + KWK_FIRED16_SLOT(v);
+  x.stage = KWK_FIRED16_STAGE(v);
   x.valid = x.slot < a.capacity;
   return x;
 }
@@ -370,22 +452,29 @@ __device__ __forceinline__ T wave_incl(T v, uint32_t lane) {
   return v;
 }
 
-template <bool kLds>
+template <bool kLds, uint32_t kSrc = kSrc32>
 __global__ __launch_bounds__(kBlock) void emit_size_kernel(EmitArgs a) {
   __shared__ kwk_emit_piece s_pieces[kLds ? kLdsPieces : 1];
   __shared__ uint32_t s_lits[kLds ? kLdsLits / 4 : 1];
   __shared__ uint2 s_sksz[kLds ? kLdsSkels : 1];
   __shared__ uint32_t s_i[kWaves];
   __shared__ unsigned long long s_b[kWaves];
+  if (*a.sticky) return;  // an earlier emission in flight exceeded its set
   const Tables T = stage_tables<kLds>(a, s_pieces, s_lits, s_sksz);
-  const uint32_t n = min(*a.count, a.max_recs), n_tiles = (n + kTile - 1) / kTile;
+  const uint32_t n = list_len<kSrc>(a), n_tiles = (n + kTile - 1) / kTile;
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  uint32_t* s_win = nullptr;
+  if constexpr (kSrc == kSrc16) s_win = seg_win_lds();
   for (uint32_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
     uint32_t it = 0;
     unsigned long long by = 0;
     const uint32_t r = t * kTile + threadIdx.x;
+    SegWin sw{};
+    if constexpr (kSrc == kSrc16) sw = tile_segs(a, t, n, s_win);
     if (r < n) {
-      const Rec x = fetch(a, r);
+      Rec x;
+      if constexpr (kSrc == kSrc16) x = fetch16(a, r, sw, s_win);
+      else x = fetch(a, r);
       const uint64_t w = x.valid ? a.words[x.slot] : 0ull;
       const Size s = rec_size(a, T, x, w, Vals{nullptr, 0u, a.lencache ? (uint32_t)(w >> 24) & 0xFFu : 0xFFu});
       it = s.items;
@@ -417,7 +506,11 @@ constexpr uint32_t kScanPer = 8;
 __global__ __launch_bounds__(kScanBlock) void emit_scan_kernel(EmitArgs a) {
   __shared__ uint32_t s_i[kScanBlock / 64];
   __shared__ unsigned long long s_b[kScanBlock / 64];
-  const uint32_t n = min(*a.count, a.max_recs), n_tiles = (n + kTile - 1) / kTile;
+  if (*a.sticky) {  // nothing was sized: this emission reads KWK_ECAP too
+    if (threadIdx.x < 5u) a.totals[threadIdx.x] = threadIdx.x == 4u ? 1ull : 0ull;
+    return;
+  }
+  const uint32_t n = a.p16 ? list_len<kSrc16>(a) : list_len<kSrc32>(a), n_tiles = (n + kTile - 1) / kTile;
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   uint32_t run_i = 0;
   unsigned long long run_b = 0;
@@ -471,6 +564,54 @@ __global__ __launch_bounds__(kScanBlock) void emit_scan_kernel(EmitArgs a) {
     a.totals[1] = run_b;
     a.totals[2] = *a.count > a.max_recs ? 1ull : 0ull;
     a.totals[3] = 0;
+    a.totals[4] = 0;
+    if (a.sticky_on && (run_i > a.cap_items || run_b > a.cap_bytes || a.totals[2])) *a.sticky = 1u;
+  }
+}
+
+// The 2-byte source's segment bases, once per emission before the size kernel: the exclusive prefix
+// of the list's records per segment (~49k segments at 100M pods), one workgroup as emit_scan_kernel
+__global__ __launch_bounds__(kScanBlock) void emit_seg_base_kernel(EmitArgs a) {
+  __shared__ uint32_t s_w[kScanBlock / 64];
+  if (*a.sticky) return;
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  uint32_t run = 0;
+  for (uint32_t base = 0; base < a.n_segs; base += kScanBlock * kScanPer) {
+    const uint32_t t0 = base + threadIdx.x * kScanPer;
+    uint32_t v[kScanPer], s = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < kScanPer; ++k) {
+      v[k] = t0 + k < a.n_segs ? a.seg_counts[t0 + k] : 0u;
+      s += v[k];
+    }
+    const uint32_t incl = wave_incl(s, lane);
+    if (lane == 63) s_w[wave] = incl;
+    __syncthreads();
+    uint32_t p = 0, tot = 0;
+    for (uint32_t w = 0; w < kScanBlock / 64; ++w) {
+      if (w < wave) p += s_w[w];
+      tot += s_w[w];
+    }
+    uint32_t e = run + p + incl - s;
+#pragma unroll
+    for (uint32_t k = 0; k < kScanPer; ++k) {
+      if (t0 + k < a.n_segs) a.seg_base[t0 + k] = e;
+      e += v[k];
+    }
+    run += tot;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) a.seg_base[a.n_segs] = run;
+}
+
+// ... and the segment of every tile's first record: segment s owns the tile starts inside
+// [seg_base[s], seg_base[s + 1]) (at most 1 + its records / kTile of them; each tile start once)
+__global__ __launch_bounds__(kBlock) void emit_tile_seg_kernel(EmitArgs a) {
+  if (*a.sticky) return;
+  const uint32_t t_max = a.max_recs / kTile;  // tile_seg holds t_max + 1 entries
+  for (uint32_t s = blockIdx.x * blockDim.x + threadIdx.x; s < a.n_segs; s += gridDim.x * blockDim.x) {
+    const uint32_t b0 = a.seg_base[s], b1 = a.seg_base[s + 1u];
+    for (uint32_t t = (b0 + kTile - 1u) / kTile; t <= t_max && t * kTile < b1; ++t) a.tile_seg[t] = s;
   }
 }
 
@@ -685,7 +826,7 @@ __device__ __forceinline__ void produce_line(SegIter& it, uint32_t L, uint32_t (
 // finding each chunk's record and segment: r5f, 3.1 vs 2.4 ms.)  Records of more than kRecSk items
 // and !kChunk: Acc, four bytes per append.  kLds: the skeleton tables and the records' call-value
 // rows (at most kLdsCols columns of 16 bytes) staged in LDS
-template <bool kLds, bool kChunk>
+template <bool kLds, bool kChunk, uint32_t kSrc = kSrc32>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kChunk ? 5 : 1))) void emit_write_kernel(EmitArgs a) {
   static_assert(kLds || !kChunk, "the chunk writer reads its tables from LDS");
   __shared__ __attribute__((aligned(16))) uint32_t s_tpl[kChunk ? kTplBytes / 4 + 8 : 1];
@@ -705,9 +846,12 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kChunk ?
   __shared__ unsigned long long s_wb[kWaves];
   __shared__ uint32_t s_now[kNowWords];
   __shared__ uint4 s_mlo[kChunk ? 17 : 1], s_mhi[kChunk ? 17 : 1];  // merge16_lut's byte masks
-  const uint32_t n = min(*a.count, a.max_recs), n_tiles = (n + kTile - 1) / kTile;
+  if (*a.sticky) return;  // this emission or an earlier one in flight exceeded its set: nothing is written
+  const uint32_t n = list_len<kSrc>(a), n_tiles = (n + kTile - 1) / kTile;
   const unsigned long long tot_i = a.totals[0], tot_b = a.totals[1];
   if (tot_i > a.cap_items || tot_b > a.cap_bytes || a.totals[2]) return;  // KWK_ECAP: nothing is written
+  uint32_t* s_win = nullptr;
+  if constexpr (kSrc == kSrc16) s_win = seg_win_lds();
   if constexpr (kLds)
     for (uint32_t j = threadIdx.x; j < a.p.n_skels; j += blockDim.x) s_skels[j] = a.p.skels[j];
   if (threadIdx.x < kNowWords) {
@@ -796,8 +940,11 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kChunk ?
     Size sz{0u, 0u, 0ull};
     Vals V{nullptr, lr};
     if constexpr (kLds) V.lds = reinterpret_cast<const uint8_t*>(s_vals);
+    SegWin sw{};
+    if constexpr (kSrc == kSrc16) sw = tile_segs(a, t, n, s_win);
     if (r < n) {
-      x = fetch(a, r);
+      if constexpr (kSrc == kSrc16) x = fetch16(a, r, sw, s_win);
+      else x = fetch(a, r);
       w = x.valid ? a.words[x.slot] : 0ull;
       if constexpr (kLds) {  // the record's value rows, one 16-byte gather per column (stages with patches only)
         const bool any = x.valid && x.stage < a.p.n_stages && a.p.stage_tpl_ptr[x.stage + 1] > a.p.stage_tpl_ptr[x.stage];
@@ -913,7 +1060,7 @@ struct kwk_emitter {
                                  // KWK_TUNE_STREAM_PRIORITY re-creates it, so it is never cached across calls)
   int device = 0;
   uint32_t capacity = 0, n_columns = 0, max_tiles = 0, grid = 0, cus = 1;
-  int write_occ[3] = {0, 0, 0};   // resident blocks per CU of each write kernel variant (0: not asked yet)
+  int write_occ[6] = {0, 0, 0, 0, 0, 0};  // resident blocks per CU of each write kernel variant (0: not asked yet)
   Prog p{};
   std::vector<void*> allocs;
   std::vector<uint32_t> stride;
@@ -921,13 +1068,30 @@ struct kwk_emitter {
   uint64_t* d_words = nullptr;
   uint32_t* d_tile_items = nullptr;
   unsigned long long* d_tile_bytes = nullptr;
-  unsigned long long* d_totals = nullptr;
-  kwk_emit_item* d_items = nullptr;
-  uint64_t* d_offsets = nullptr;
-  char* d_out = nullptr;
-  uint64_t cap_items = 0, cap_bytes = 0;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  bool emitted = false;
+  // The output sets (kwk_emit_reserve_sets; one by default): emissions rotate through them, so
+  // that the emissions of a fused group are enqueued back to back and all read afterwards
+  struct OutSet {
+    unsigned long long* d_totals = nullptr;  // 8 words of d_totals_all
+    kwk_emit_item* d_items = nullptr;
+    uint64_t* d_offsets = nullptr;
+    char* d_out = nullptr;
+    uint64_t cap_items = 0, cap_bytes = 0;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    bool emitted = false;
+  };
+  std::vector<OutSet> sets;
+  uint32_t cur = 0;               // the set of the last emission
+  uint32_t n_emitted = 0;         // emissions since the sets were made (kwk_emit_select's range)
+  uint32_t sel = 0;               // the readers' emission: `sel` before the last
+  unsigned long long* d_totals_all = nullptr;
+  uint32_t* d_sticky = nullptr;   // device flag: an emission in flight exceeded its set
+  uint32_t* d_zero = nullptr;     // a zero length word (a ring list of no segments is empty)
+  bool sticky_armed = false;      // an emission that may set d_sticky was enqueued since it was cleared
+  bool saw_cap = false;           // the host has read KWK_ECAP: the next emission clears d_sticky
+  uint32_t* d_seg_base = nullptr; // the 2-byte source's segment bases (n_segs + 1) ...
+  uint32_t seg_cap = 0;
+  uint32_t* d_tile_seg = nullptr; // ... and every tile's first segment (max_tiles + 1)
+  OutSet& selected() { return sets[(cur + (uint32_t)sets.size() - sel) % (uint32_t)sets.size()]; }
   bool chunk_ok = false;          // skeletons own consecutive, disjoint piece ranges (the chunk writer's templates)
   bool lencache = false;          // words' bits 24-31 cache the value lengths (emit_lens_kernel)
   uint64_t tpl_lits = 0;          // literal bytes of every skeleton's pieces
@@ -938,11 +1102,16 @@ struct kwk_emitter {
     void* s = nullptr;
     if (eng && kwk_stream(eng, &s) == KWK_OK && s) hipStreamSynchronize(static_cast<hipStream_t>(s));
     for (void* x : allocs) hipFree(x);
-    if (d_items) hipFree(d_items);
-    if (d_offsets) hipFree(d_offsets);
-    if (d_out) hipFree(d_out);
-    if (ev0) hipEventDestroy(ev0);
-    if (ev1) hipEventDestroy(ev1);
+    if (d_seg_base) hipFree(d_seg_base);
+    for (OutSet& o : sets) free_set(o);
+  }
+  static void free_set(OutSet& o) {
+    if (o.d_items) hipFree(o.d_items);
+    if (o.d_offsets) hipFree(o.d_offsets);
+    if (o.d_out) hipFree(o.d_out);
+    if (o.ev0) hipEventDestroy(o.ev0);
+    if (o.ev1) hipEventDestroy(o.ev1);
+    o = OutSet{};
   }
 };
 
@@ -987,6 +1156,23 @@ kwk_status upload(kwk_emitter* em, T** dst, const T* src, size_t n) {
   em->allocs.push_back(d);
   if (kwk_status st = copy_in(em, d, src, n * sizeof(T))) return st;
   *dst = static_cast<T*>(d);
+  return KWK_OK;
+}
+
+constexpr uint32_t kMaxSets = 8;
+
+// n fresh output sets (the stream idle): the rotation starts over
+kwk_status make_sets(kwk_emitter* em, uint32_t n) {
+  for (kwk_emitter::OutSet& o : em->sets) kwk_emitter::free_set(o);
+  em->sets.assign(n, kwk_emitter::OutSet{});
+  for (uint32_t i = 0; i < n; ++i) {
+    em->sets[i].d_totals = em->d_totals_all + 8u * i;
+    HIP_TRY(hipEventCreate(&em->sets[i].ev0));
+    HIP_TRY(hipEventCreate(&em->sets[i].ev1));
+  }
+  em->cur = n - 1u;
+  em->n_emitted = 0;
+  em->sel = 0;
   return KWK_OK;
 }
 
@@ -1097,17 +1283,24 @@ kwk_status emitter_init(kwk_emitter* em, const kwk_emit_program* g) {
   HIP_TRY(hipMalloc(&d, (size_t)em->max_tiles * 8));
   em->allocs.push_back(d);
   em->d_tile_bytes = static_cast<unsigned long long*>(d);
-  HIP_TRY(hipMalloc(&d, 4 * 8));
+  HIP_TRY(hipMalloc(&d, kMaxSets * 8 * 8));
   em->allocs.push_back(d);
-  em->d_totals = static_cast<unsigned long long*>(d);
-  if (kwk_status st = fill(em, d, 0, 4 * 8)) return st;
+  em->d_totals_all = static_cast<unsigned long long*>(d);
+  if (kwk_status st = fill(em, d, 0, kMaxSets * 8 * 8)) return st;
+  HIP_TRY(hipMalloc(&d, 2 * 4));
+  em->allocs.push_back(d);
+  em->d_sticky = static_cast<uint32_t*>(d);
+  em->d_zero = em->d_sticky + 1;
+  if (kwk_status st = fill(em, d, 0, 2 * 4)) return st;
+  HIP_TRY(hipMalloc(&d, ((size_t)em->max_tiles + 1) * 4));
+  em->allocs.push_back(d);
+  em->d_tile_seg = static_cast<uint32_t*>(d);
+  if (kwk_status st = make_sets(em, 1)) return st;
   int cus = 0;
   HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, em->device));
   em->grid = std::max(1u, std::min(em->max_tiles, (uint32_t)std::max(1, cus) * 8u));
   em->cus = (uint32_t)std::max(1, cus);
   if (kwk_status st = refresh_lens(em, 0, em->capacity)) return st;
-  HIP_TRY(hipEventCreate(&em->ev0));
-  HIP_TRY(hipEventCreate(&em->ev1));
   return KWK_OK;
 }
 
@@ -1177,28 +1370,163 @@ kwk_status kwk_emit_set_column(kwk_emitter* em, uint32_t c, uint32_t first, uint
   return refresh_lens(em, first, n);
 }
 
+}  // extern "C"
+
+namespace {
+
+// room of max_items / max_bytes in each of n_sets output sets (the stream idle afterwards); a set
+// that grows loses its emission's outputs, another number of sets starts the rotation over
+kwk_status reserve_sets(kwk_emitter* em, uint32_t n_sets, uint32_t max_items, uint64_t max_bytes) {
+  if (kwk_status st = bind(em)) return st;
+  HIP_TRY(hipStreamSynchronize(em->stream));
+  if (n_sets != em->sets.size())
+    if (kwk_status st = make_sets(em, n_sets)) return st;
+  for (kwk_emitter::OutSet& o : em->sets) {
+    if (max_items > o.cap_items) {
+      if (o.d_items) HIP_TRY(hipFree(o.d_items));
+      if (o.d_offsets) HIP_TRY(hipFree(o.d_offsets));
+      o.d_items = nullptr;
+      o.d_offsets = nullptr;
+      o.cap_items = 0;
+      HIP_TRY(hipMalloc(&o.d_items, (size_t)max_items * sizeof(kwk_emit_item)));
+      HIP_TRY(hipMalloc(&o.d_offsets, ((size_t)max_items + 1) * 8));
+      o.cap_items = max_items;
+    }
+    if (max_bytes > o.cap_bytes) {
+      if (o.d_out) HIP_TRY(hipFree(o.d_out));
+      o.d_out = nullptr;
+      o.cap_bytes = 0;
+      HIP_TRY(hipMalloc(&o.d_out, (size_t)max_bytes));
+      o.cap_bytes = max_bytes;
+    }
+  }
+  if (em->sticky_armed) {  // the host reserves again: later emissions run
+    if (kwk_status st = fill(em, em->d_sticky, 0, 4)) return st;
+    em->sticky_armed = false;
+  }
+  em->saw_cap = false;
+  return KWK_OK;
+}
+
+// the three launches (five for the 2-byte source) of one emission into the next output set; `a`
+// holds the list (recs / packed / p16 ..., count)
+kwk_status enqueue_emission(kwk_emitter* em, EmitArgs& a, int64_t now_ns) {
+  if (kwk_status st = bind(em)) return st;
+  if (!em->sets[0].d_offsets)
+    if (kwk_status st = reserve_sets(em, (uint32_t)em->sets.size(), 1, 1)) return st;
+  const bool src16 = a.p16 != nullptr;
+  if (src16 && a.n_segs + 1u > em->seg_cap) {
+    if (em->d_seg_base) HIP_TRY(hipFree(em->d_seg_base));  // (synchronises the device: no kernel still reads it)
+    em->d_seg_base = nullptr;
+    em->seg_cap = 0;
+    HIP_TRY(hipMalloc((void**)&em->d_seg_base, ((size_t)a.n_segs + 1u) * 4));
+    em->seg_cap = a.n_segs + 1u;
+  }
+  const uint32_t n_sets = (uint32_t)em->sets.size();
+  kwk_emitter::OutSet& o = em->sets[(em->cur + 1u) % n_sets];
+  a.p = em->p;
+  a.words = em->d_words;
+  a.capacity = em->capacity;
+  a.max_recs = (em->max_tiles - 1) * kTile;
+  a.tile_items = em->d_tile_items;
+  a.tile_bytes = em->d_tile_bytes;
+  a.totals = o.d_totals;
+  a.items = o.d_items;
+  a.offsets = o.d_offsets;
+  a.out = o.d_out;
+  a.cap_items = o.cap_items;
+  a.cap_bytes = o.cap_bytes;
+  a.lencache = em->lencache ? 1u : 0u;
+  a.sticky = em->d_sticky;
+  a.sticky_on = n_sets > 1u ? 1u : 0u;  // (one set: every emission stands alone, as before the sets)
+  a.seg_base = em->d_seg_base;
+  a.tile_seg = em->d_tile_seg;
+  const std::string now = kwkfmt::rfc3339nano(now_ns);
+  if (now.size() >= sizeof a.now) return fail(KWK_EINVAL, "Now() text too long");
+  memcpy(a.now, now.data(), now.size());
+  a.now_len = (uint32_t)now.size();
+  if (em->saw_cap && em->sticky_armed) {  // the host has seen the overflow and emits again
+    HIP_TRY(hipMemsetAsync(em->d_sticky, 0, 4, em->stream));
+    em->sticky_armed = false;
+  }
+  em->saw_cap = false;
+  if (a.sticky_on) em->sticky_armed = true;
+  // the list's count lives on the device: every tile loop reads it; the grid covers the capacity
+  HIP_TRY(hipEventRecord(o.ev0, em->stream));
+  bool lds = em->p.n_pieces <= kLdsPieces && em->p.n_lits + 8u <= kLdsLits && em->p.n_skels <= kLdsSkels;
+  bool vals16 = em->n_columns <= kLdsCols;
+  for (uint32_t c = 0; c < em->n_columns; ++c) vals16 = vals16 && em->stride[c] == 16u;
+  if (src16) {
+    hipLaunchKernelGGL(emit_seg_base_kernel, dim3(1), dim3(kScanBlock), 0, em->stream, a);
+    HIP_TRY(hipGetLastError());
+    const uint32_t sgrid = std::max(1u, std::min((a.n_segs + kBlock - 1u) / kBlock, em->cus * 8u));
+    hipLaunchKernelGGL(emit_tile_seg_kernel, dim3(sgrid), dim3(kBlock), 0, em->stream, a);
+    HIP_TRY(hipGetLastError());
+    if (lds)
+      hipLaunchKernelGGL((emit_size_kernel<true, kSrc16>), dim3(em->grid), dim3(kBlock), 0, em->stream, a);
+    else
+      hipLaunchKernelGGL((emit_size_kernel<false, kSrc16>), dim3(em->grid), dim3(kBlock), 0, em->stream, a);
+  } else if (lds) {
+    hipLaunchKernelGGL(emit_size_kernel<true>, dim3(em->grid), dim3(kBlock), 0, em->stream, a);
+  } else {
+    hipLaunchKernelGGL(emit_size_kernel<false>, dim3(em->grid), dim3(kBlock), 0, em->stream, a);
+  }
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(emit_scan_kernel, dim3(1), dim3(kScanBlock), 0, em->stream, a);
+  HIP_TRY(hipGetLastError());
+  const bool wl = lds && vals16;  // the write kernel's LDS path also stages the value rows
+  // the chunk writer: templates (literals + Now per slot) within kTplBytes, pieces in skeleton order
+  const bool chunk = wl && em->chunk_ok && em->tpl_lits + (uint64_t)em->tpl_now_slots * a.now_len + 16u <= kTplBytes;
+  const void* wk = src16 ? (chunk ? (const void*)emit_write_kernel<true, true, kSrc16>
+                            : wl  ? (const void*)emit_write_kernel<true, false, kSrc16>
+                                  : (const void*)emit_write_kernel<false, false, kSrc16>)
+                         : (chunk ? (const void*)emit_write_kernel<true, true>
+                            : wl  ? (const void*)emit_write_kernel<true, false>
+                                  : (const void*)emit_write_kernel<false, false>);
+  void* wargs[] = {&a};
+  // the write kernel's grid: every block resident at once (one round; its tile loop does the rest)
+  const int vi = (chunk ? 0 : wl ? 1 : 2) + (src16 ? 3 : 0);
+  if (!em->write_occ[vi]) {
+    int occ = 0;
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, wk, kBlock, 0));
+    em->write_occ[vi] = std::max(1, occ);
+  }
+  const uint32_t wgrid = std::max(1u, std::min(em->max_tiles, em->cus * (uint32_t)em->write_occ[vi]));
+  HIP_TRY(hipLaunchKernel(wk, dim3(wgrid), dim3(kBlock), wargs, 0, em->stream));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(o.ev1, em->stream));
+  o.emitted = true;
+  em->cur = (em->cur + 1u) % n_sets;
+  em->n_emitted = std::min(em->n_emitted + 1u, n_sets);
+  em->sel = 0;
+  return KWK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
 kwk_status kwk_emit_reserve(kwk_emitter* em, uint32_t max_items, uint64_t max_bytes) {
   ErrScope es_(em ? &em->err : nullptr);
   if (!em) return fail(KWK_EINVAL, "null emitter");
-  if (kwk_status st = bind(em)) return st;
-  HIP_TRY(hipStreamSynchronize(em->stream));
-  if (max_items > em->cap_items) {
-    if (em->d_items) HIP_TRY(hipFree(em->d_items));
-    if (em->d_offsets) HIP_TRY(hipFree(em->d_offsets));
-    em->d_items = nullptr;
-    em->d_offsets = nullptr;
-    em->cap_items = 0;
-    HIP_TRY(hipMalloc(&em->d_items, (size_t)max_items * sizeof(kwk_emit_item)));
-    HIP_TRY(hipMalloc(&em->d_offsets, ((size_t)max_items + 1) * 8));
-    em->cap_items = max_items;
-  }
-  if (max_bytes > em->cap_bytes) {
-    if (em->d_out) HIP_TRY(hipFree(em->d_out));
-    em->d_out = nullptr;
-    em->cap_bytes = 0;
-    HIP_TRY(hipMalloc(&em->d_out, (size_t)max_bytes));
-    em->cap_bytes = max_bytes;
-  }
+  return reserve_sets(em, (uint32_t)em->sets.size(), max_items, max_bytes);
+}
+
+kwk_status kwk_emit_reserve_sets(kwk_emitter* em, uint32_t n_sets, uint32_t max_items, uint64_t max_bytes) {
+  ErrScope es_(em ? &em->err : nullptr);
+  if (!em) return fail(KWK_EINVAL, "null emitter");
+  if (n_sets < 1u || n_sets > kMaxSets) return fail(KWK_EINVAL, "kwk_emit_reserve_sets: 1..8 output sets");
+  return reserve_sets(em, n_sets, max_items, max_bytes);
+}
+
+kwk_status kwk_emit_select(kwk_emitter* em, uint32_t back) {
+  ErrScope es_(em ? &em->err : nullptr);
+  if (!em) return fail(KWK_EINVAL, "null emitter");
+  if (back >= em->sets.size())
+    return fail(KWK_EINVAL, "kwk_emit_select: the emitter has " + std::to_string(em->sets.size()) + " output set(s)");
+  if (back && back >= em->n_emitted)
+    return fail(KWK_ESTATE, "kwk_emit_select: only " + std::to_string(em->n_emitted) + " emission(s) since the sets were made");
+  em->sel = back;
   return KWK_OK;
 }
 
@@ -1206,7 +1534,6 @@ kwk_status kwk_emit(kwk_emitter* em, int64_t now_ns, uint32_t source) {
   ErrScope es_(em ? &em->err : nullptr);
   if (!em) return fail(KWK_EINVAL, "null emitter");
   EmitArgs a{};
-  a.p = em->p;
   const uint32_t from = source & 0xFFu;
   if (from != KWK_EMIT_FROM_RECORDS && from != KWK_EMIT_FROM_PACKED)
     return fail(KWK_EINVAL, "source must be KWK_EMIT_FROM_RECORDS or KWK_EMIT_FROM_PACKED");
@@ -1217,72 +1544,66 @@ kwk_status kwk_emit(kwk_emitter* em, int64_t now_ns, uint32_t source) {
   if (from == KWK_EMIT_FROM_PACKED) a.packed = static_cast<const uint32_t*>(list);
   else a.recs = static_cast<const kwk_fired_rec*>(list);
   if (source & ~0xFFu) return fail(KWK_EINVAL, "unknown source flags");
-  if (kwk_status st = bind(em)) return st;
-  if (!em->d_offsets)
-    if (kwk_status st = kwk_emit_reserve(em, 1, 1)) return st;
-  a.words = em->d_words;
-  a.capacity = em->capacity;
-  a.max_recs = (em->max_tiles - 1) * kTile;
-  a.tile_items = em->d_tile_items;
-  a.tile_bytes = em->d_tile_bytes;
-  a.totals = em->d_totals;
-  a.items = em->d_items;
-  a.offsets = em->d_offsets;
-  a.out = em->d_out;
-  a.cap_items = em->cap_items;
-  a.cap_bytes = em->cap_bytes;
-  a.lencache = em->lencache ? 1u : 0u;
-  const std::string now = kwkfmt::rfc3339nano(now_ns);
-  if (now.size() >= sizeof a.now) return fail(KWK_EINVAL, "Now() text too long");
-  memcpy(a.now, now.data(), now.size());
-  a.now_len = (uint32_t)now.size();
-  // the list's count lives on the device: every tile loop reads it; the grid covers the capacity
-  HIP_TRY(hipEventRecord(em->ev0, em->stream));
-  bool lds = em->p.n_pieces <= kLdsPieces && em->p.n_lits + 8u <= kLdsLits && em->p.n_skels <= kLdsSkels;
-  bool vals16 = em->n_columns <= kLdsCols;
-  for (uint32_t c = 0; c < em->n_columns; ++c) vals16 = vals16 && em->stride[c] == 16u;
-  if (lds)
-    hipLaunchKernelGGL(emit_size_kernel<true>, dim3(em->grid), dim3(kBlock), 0, em->stream, a);
-  else
-    hipLaunchKernelGGL(emit_size_kernel<false>, dim3(em->grid), dim3(kBlock), 0, em->stream, a);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(emit_scan_kernel, dim3(1), dim3(kScanBlock), 0, em->stream, a);
-  HIP_TRY(hipGetLastError());
-  const bool wl = lds && vals16;  // the write kernel's LDS path also stages the value rows
-  // the chunk writer: templates (literals + Now per slot) within kTplBytes, pieces in skeleton order
-  const bool chunk = wl && em->chunk_ok && em->tpl_lits + (uint64_t)em->tpl_now_slots * a.now_len + 16u <= kTplBytes;
-  const void* wk = chunk ? (const void*)emit_write_kernel<true, true>
-                   : wl  ? (const void*)emit_write_kernel<true, false>
-                         : (const void*)emit_write_kernel<false, false>;
-  void* wargs[] = {&a};
-  // the write kernel's grid: every block resident at once (one round; its tile loop does the rest)
-  const int vi = chunk ? 0 : wl ? 1 : 2;
-  if (!em->write_occ[vi]) {
-    int occ = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, wk, kBlock, 0));
-    em->write_occ[vi] = std::max(1, occ);
+  return enqueue_emission(em, a, now_ns);
+}
+
+kwk_status kwk_emit_step(kwk_emitter* em, uint64_t step, int64_t now_ns) {
+  ErrScope es_(em ? &em->err : nullptr);
+  if (!em) return fail(KWK_EINVAL, "null emitter");
+  kwk_fired_view v;
+  if (kwk_ring_view(em->eng, step, &v) != KWK_OK)
+    return fail(KWK_ESTATE, std::string("kwk_ring_view: ") + kwk_last_error(em->eng));
+  EmitArgs a{};
+  a.count = v.count;
+  switch (v.format) {
+    case KWK_COMPACT_REC: a.recs = static_cast<const kwk_fired_rec*>(v.list); break;
+    case KWK_COMPACT_PACKED: a.packed = static_cast<const uint32_t*>(v.list); break;
+    case KWK_COMPACT_PACKED16:
+      if (!v.seg_counts) return fail(KWK_ESTATE, "the 2-byte list of step " + std::to_string(v.step) + " has no segment counts");
+      a.p16 = static_cast<const uint16_t*>(v.list);
+      a.seg_counts = v.seg_counts;
+      a.n_segs = v.n_segs;
+      a.region_slots = v.region_slots;
+      break;
+    case KWK_COMPACT_BITS:
+      return fail(KWK_ESTATE, "the list of step " + std::to_string(v.step) +
+                                  " is in KWK_COMPACT_BITS: the bitmap format is not emitted (compact it as "
+                                  "KWK_COMPACT_PACKED16, _PACKED or _REC)");
+    default: return fail(KWK_ESTATE, "the list of step " + std::to_string(v.step) + " is in an unknown format");
   }
-  const uint32_t wgrid = std::max(1u, std::min(em->max_tiles, em->cus * (uint32_t)em->write_occ[vi]));
-  HIP_TRY(hipLaunchKernel(wk, dim3(wgrid), dim3(kBlock), wargs, 0, em->stream));
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(em->ev1, em->stream));
-  em->emitted = true;
-  return KWK_OK;
+  if (v.n_segs == 0) {  // a step that swept nothing: an empty list, whatever its length word holds
+    a.recs = nullptr;
+    a.packed = nullptr;
+    a.p16 = nullptr;
+    a.count = em->d_zero;
+  }
+  return enqueue_emission(em, a, now_ns);
 }
 
 kwk_status kwk_emit_result(kwk_emitter* em, uint32_t* n_items, uint64_t* n_bytes) {
   ErrScope es_(em ? &em->err : nullptr);
   if (!em || !n_items || !n_bytes) return fail(KWK_EINVAL, "null argument");
-  if (!em->emitted) return fail(KWK_ESTATE, "kwk_emit must come first");
+  const kwk_emitter::OutSet& o = em->selected();
+  if (!o.emitted) return fail(KWK_ESTATE, "kwk_emit must come first");
   if (kwk_status st = bind(em)) return st;
-  unsigned long long t[3];
-  if (kwk_status st = copy_out(em, t, em->d_totals, sizeof t)) return st;
+  unsigned long long t[5];
+  if (kwk_status st = copy_out(em, t, o.d_totals, sizeof t)) return st;
   *n_items = (uint32_t)t[0];
   *n_bytes = t[1];
-  if (t[2]) return fail(KWK_ECAP, "the fired list is longer than the emitter's capacity");
-  if (t[0] > em->cap_items || t[1] > em->cap_bytes)
+  if (t[4]) {
+    em->saw_cap = true;
+    return fail(KWK_ECAP, "an earlier emission in flight exceeded its reservation: nothing was written — reserve "
+                          "and emit again from the first step that failed");
+  }
+  if (t[2]) {
+    em->saw_cap = true;
+    return fail(KWK_ECAP, "the fired list is longer than the emitter's capacity");
+  }
+  if (t[0] > o.cap_items || t[1] > o.cap_bytes) {
+    em->saw_cap = true;
     return fail(KWK_ECAP, "emission exceeds the reservation: kwk_emit_reserve(" + std::to_string(t[0]) + ", " +
                               std::to_string(t[1]) + ") and emit again");
+  }
   return KWK_OK;
 }
 
@@ -1291,7 +1612,7 @@ kwk_status kwk_emit_stats(kwk_emitter* em, uint32_t* n_items, uint32_t* n_emitte
   if (!em || !n_items || !n_emitted || !n_bytes) return fail(KWK_EINVAL, "null argument");
   if (kwk_status st = kwk_emit_result(em, n_items, n_bytes)) return st;
   unsigned long long t = 0;
-  if (kwk_status st = copy_out(em, &t, em->d_totals + 3, 8)) return st;
+  if (kwk_status st = copy_out(em, &t, em->selected().d_totals + 3, 8)) return st;
   *n_emitted = (uint32_t)t;
   return KWK_OK;
 }
@@ -1299,9 +1620,10 @@ kwk_status kwk_emit_stats(kwk_emitter* em, uint32_t* n_items, uint32_t* n_emitte
 kwk_status kwk_emit_device(kwk_emitter* em, const kwk_emit_item** items, const uint64_t** offsets, const char** bytes) {
   ErrScope es_(em ? &em->err : nullptr);
   if (!em) return fail(KWK_EINVAL, "null emitter");
-  if (items) *items = em->d_items;
-  if (offsets) *offsets = em->d_offsets;
-  if (bytes) *bytes = em->d_out;
+  const kwk_emitter::OutSet& o = em->selected();
+  if (items) *items = o.d_items;
+  if (offsets) *offsets = o.d_offsets;
+  if (bytes) *bytes = o.d_out;
   return KWK_OK;
 }
 
@@ -1311,23 +1633,25 @@ kwk_status kwk_emit_copy(kwk_emitter* em, kwk_emit_item* items, uint64_t* offset
   uint64_t nb = 0;
   if (kwk_status st = kwk_emit_result(em, &ni, &nb)) return st;
   if ((ni && (!items || !offsets)) || (nb && !bytes) || !offsets) return fail(KWK_EINVAL, "null argument");
+  const kwk_emitter::OutSet& o = em->selected();
   if (ni) {
-    if (kwk_status st = copy_out(em, items, em->d_items, (size_t)ni * sizeof(kwk_emit_item))) return st;
-    if (kwk_status st = copy_out(em, offsets, em->d_offsets, ((size_t)ni + 1) * 8)) return st;
+    if (kwk_status st = copy_out(em, items, o.d_items, (size_t)ni * sizeof(kwk_emit_item))) return st;
+    if (kwk_status st = copy_out(em, offsets, o.d_offsets, ((size_t)ni + 1) * 8)) return st;
   } else {
     offsets[0] = 0;
   }
-  if (kwk_status st = copy_out(em, bytes, em->d_out, (size_t)nb)) return st;
+  if (kwk_status st = copy_out(em, bytes, o.d_out, (size_t)nb)) return st;
   return KWK_OK;
 }
 
 kwk_status kwk_emit_elapsed(kwk_emitter* em, float* ms) {
   ErrScope es_(em ? &em->err : nullptr);
   if (!em || !ms) return fail(KWK_EINVAL, "null argument");
-  if (!em->emitted) return fail(KWK_ESTATE, "kwk_emit must come first");
+  const kwk_emitter::OutSet& o = em->selected();
+  if (!o.emitted) return fail(KWK_ESTATE, "kwk_emit must come first");
   if (kwk_status st = bind(em)) return st;
-  HIP_TRY(hipEventSynchronize(em->ev1));
-  HIP_TRY(hipEventElapsedTime(ms, em->ev0, em->ev1));
+  HIP_TRY(hipEventSynchronize(o.ev1));
+  HIP_TRY(hipEventElapsedTime(ms, o.ev0, o.ev1));
   return KWK_OK;
 }
 

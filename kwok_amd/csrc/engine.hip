@@ -6507,6 +6507,37 @@ kwk_status kwk_fired_fetch(kwk_engine* e, uint64_t step, void* out, uint64_t cap
                               std::to_string(n) + " compactions: kwk_fired_keep)");
 }
 
+// slot i where it lies (kwk_ring_view): no device work
+static kwk_status hb_view(const kwk_engine* e, uint32_t i, kwk_fired_view* out) {
+  const kwk_engine::HbSlot& h = e->hb[i];
+  if (!h.list || !h.offsets) return fail(KWK_ESTATE, "the ring slot of step " + std::to_string(h.step) + " holds no list");
+  out->list = h.list;
+  out->count = h.mode == HbFmt::Bits ? h.tot : h.offsets;
+  out->seg_counts = h.mode == HbFmt::Packed16 ? h.counts : nullptr;
+  out->format = hb_code(h.mode);
+  out->n_segs = h.n_segs;
+  out->region_slots = h.region_slots;
+  out->step = h.step;
+  return KWK_OK;
+}
+
+kwk_status kwk_ring_view(kwk_engine* e, uint64_t step, kwk_fired_view* out) {
+  ErrScope es_(e);
+  if (!e || !out) return fail(KWK_EINVAL, "null argument");
+  memset(out, 0, sizeof(*out));
+  const uint32_t n = (uint32_t)e->hb.size();
+  if (step == KWK_STEP_LAST) {  // the engine's last list
+    if (!e->compacted) return fail(KWK_ESTATE, "kwk_ring_view needs the step's list compacted (kwk_fired_compact)");
+    return hb_view(e, e->hb_cur, out);
+  }
+  for (uint32_t k = 0; k < n; ++k) {  // newest first
+    const uint32_t i = (e->hb_cur + n - k) % n;
+    if (e->hb[i].valid && e->hb[i].step == step) return hb_view(e, i, out);
+  }
+  return fail(KWK_ESTATE, "no kept list of step " + std::to_string(step) + " (the ring holds the last " +
+                              std::to_string(n) + " compactions: kwk_fired_keep)");
+}
+
 kwk_status kwk_fired_fetch_wait(kwk_engine* e) {
   ErrScope es_(e);
   if (!e) return fail(KWK_EINVAL, "null engine");

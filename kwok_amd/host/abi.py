@@ -83,6 +83,12 @@ class FetchInfo(C.Structure):
                 ("step", C.c_uint64)]
 
 
+class FiredView(C.Structure):
+    """kwk_fired_view (kwk_ring_view): a kept list where it lies on the device."""
+    _fields_ = [("list", C.c_void_p), ("count", C.c_void_p), ("seg_counts", C.c_void_p), ("format", C.c_uint32),
+                ("n_segs", C.c_uint32), ("region_slots", C.c_uint32), ("reserved", C.c_uint32), ("step", C.c_uint64)]
+
+
 class SweepInfo(C.Structure):
     _fields_ = [(k, C.c_uint32) for k in ("kernel", "q", "persistent", "depth", "grid", "tiles", "harness", "steps")]
 
@@ -187,7 +193,7 @@ EXPORTS = [
     "kwk_metrics_load", "kwk_metrics_inputs", "kwk_metrics_eval", "kwk_aggregate", "kwk_aggregate_read",
     "kwk_last_sweep", "kwk_tick_bind", "kwk_tick", "kwk_tick_n", "kwk_histograms_load", "kwk_histograms_eval",
     "kwk_fired_fetch", "kwk_fired_fetch_wait", "kwk_fired_keep",
-    "kwk_metrics_eval_device", "kwk_histograms_eval_device", "kwk_metrics_series_device",
+    "kwk_metrics_eval_device", "kwk_histograms_eval_device", "kwk_metrics_series_device", "kwk_ring_view",
 ]
 ABI_VERSION = 3  # KWK_ABI_VERSION of include/kwok_engine.h: the library must match the structs above
 TICK_COMPACT = 1 << 0  # KWK_TICK_COMPACT
@@ -256,6 +262,7 @@ def lib():
     L.kwk_fired_keep.argtypes = [C.c_void_p, C.c_uint32]
     L.kwk_fired_fetch.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, _p(FetchInfo)]
     L.kwk_fired_fetch_wait.argtypes = [C.c_void_p]
+    L.kwk_ring_view.argtypes = [C.c_void_p, C.c_uint64, _p(FiredView)]
     L.kwk_step_n.argtypes = [C.c_void_p, C.c_uint32, C.c_int64, C.c_int64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32,
                              C.c_uint32]
     L.kwk_step_n_pair.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int64, C.c_int64, C.c_uint64, C.c_uint64,

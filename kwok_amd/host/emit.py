@@ -282,6 +282,9 @@ def lib():
         L.kwk_emit_set_column.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
         L.kwk_emit_reserve.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64]
         L.kwk_emit.argtypes = [C.c_void_p, C.c_int64, C.c_uint32]
+        L.kwk_emit_step.argtypes = [C.c_void_p, C.c_uint64, C.c_int64]
+        L.kwk_emit_reserve_sets.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64]
+        L.kwk_emit_select.argtypes = [C.c_void_p, C.c_uint32]
         L.kwk_emit_result.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
         L.kwk_emit_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
         L.kwk_emit_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -296,7 +299,8 @@ def lib():
 
 EXPORTS = ("kwk_emit_last_error", "kwk_emitter_create", "kwk_emitter_destroy", "kwk_emit_set_words",
            "kwk_emit_get_words", "kwk_emit_set_column", "kwk_emit_reserve", "kwk_emit", "kwk_emit_result",
-           "kwk_emit_stats", "kwk_emit_device", "kwk_emit_copy", "kwk_emit_elapsed")
+           "kwk_emit_stats", "kwk_emit_device", "kwk_emit_copy", "kwk_emit_elapsed", "kwk_emit_step",
+           "kwk_emit_reserve_sets", "kwk_emit_select")
 
 
 class Emitter:
@@ -355,6 +359,44 @@ class Emitter:
 
     def reserve(self, items: int, nbytes: int):
         self._check(lib().kwk_emit_reserve(self.h, int(items), int(nbytes)), "kwk_emit_reserve")
+
+    def reserve_sets(self, n_sets: int, items: int, nbytes: int):
+        """kwk_emit_reserve_sets: n_sets (1..8) output sets of this room; emissions take them in turn."""
+        self._check(lib().kwk_emit_reserve_sets(self.h, int(n_sets), int(items), int(nbytes)), "kwk_emit_reserve_sets")
+
+    def select(self, back: int = 0):
+        """kwk_emit_select: result / stats / collect / elapsed_ms refer to the emission `back` before
+        the last (0 = the last; every new emission selects 0 again)."""
+        self._check(lib().kwk_emit_select(self.h, int(back)), "kwk_emit_select")
+
+    def emit_step(self, step: int, now_ns: int):
+        """kwk_emit_step: enqueue the emission of the ring list of `step` (any step of a step_n call
+        the engine's ring still holds), in the format its compaction left."""
+        self._check(lib().kwk_emit_step(self.h, int(step), int(now_ns)), "kwk_emit_step")
+
+    def collect(self):
+        """The selected emission copied to the host -> (items structured array, offsets, bytes);
+        abi.EngineError (KWK_ECAP) when it, or an emission in flight before it, exceeded its set."""
+        ni, nb = C.c_uint32(), C.c_uint64()
+        self._check(lib().kwk_emit_result(self.h, C.byref(ni), C.byref(nb)), "kwk_emit_result")
+        ni, nb = int(ni.value), int(nb.value)
+        items = np.zeros(ni, dtype=ITEM_DTYPE)
+        offs = np.zeros(ni + 1, dtype=np.uint64)
+        out = np.zeros(max(nb, 1), dtype=np.uint8)
+        self._check(lib().kwk_emit_copy(self.h, abi.ptr(items) if ni else None, abi.ptr(offs), abi.ptr(out)),
+                    "kwk_emit_copy")
+        return items, offs, out[:nb].tobytes()
+
+    def run_step(self, step: int, now_ns: int):
+        """emit_step + collect, emitting again with enough room when the set is too small (twice:
+        an emission held back by an earlier one in flight first reports no size of its own)."""
+        for _ in range(3):
+            self.emit_step(step, now_ns)
+            ni, nb = self.result()
+            if ni >= 0:
+                return self.collect()
+            self.reserve(-ni - 1, max(nb, 1))
+        raise abi.EngineError("kwk_emit_step: reservation still too small")
 
     def emit(self, now_ns: int, packed: bool = True):
         """Enqueue the emission of the engine's last compacted list."""

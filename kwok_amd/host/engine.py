@@ -331,6 +331,15 @@ class Engine:
         """kwk_fired_fetch_wait: the last fetch's copies are in the host buffers."""
         self._check(abi.lib().kwk_fired_fetch_wait(self.h), "kwk_fired_fetch_wait")
 
+    def fired_view(self, step: int = abi.STEP_LAST) -> dict:
+        """kwk_ring_view: step `step`'s kept list where it lies on the device (the kwk_fired_view
+        fields; list / count / seg_counts are device addresses, None for a null pointer).  Nothing is
+        synchronised or copied: the pointers are for work enqueued on the engine's stream before
+        its next sweep or compaction, and a list whose n_segs is 0 is empty whatever its count holds."""
+        v = abi.FiredView()
+        self._check(abi.lib().kwk_ring_view(self.h, step, C.byref(v)), "kwk_ring_view")
+        return {k: getattr(v, k) for k, _ in abi.FiredView._fields_}
+
     def set_tuning(self, key: int, value: int):
         """kwk_set_tuning: an explicit kernel choice (abi.TUNE_*)."""
         self._check(abi.lib().kwk_set_tuning(self.h, key, value), "kwk_set_tuning")
