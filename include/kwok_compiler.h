@@ -84,6 +84,12 @@ kwk_status kwk_program_class_keys(kwk_program* p, const char** json);
 kwk_status kwk_program_encoder_spec(kwk_program* p, const char** json);
 kwk_status kwk_program_patch_spec(kwk_program* p, const char* funcs_json, const char* version, const char** json,
                                   int32_t* template_of, uint32_t cap);
+/* the finalizer program, the "finalizers" member of the patch spec (kwok_patch.h) and the source of
+ * kwk_emit_fin_program: {"values": [dictionary values, id order], "stages": [{"flags", "add": [ids in
+ * the Stage's order, duplicates kept], "remove": [ids]}]}.  KWK_EINVAL naming the cause for the two
+ * shapes the host keeps: more than 15 dictionary values; a value with a byte outside
+ * [A-Za-z0-9._/-] (Go's json.Marshal escaping of other bytes is pinned by no reference vector) */
+kwk_status kwk_program_finalizer_spec(kwk_program* p, const char** json);
 
 #ifdef __cplusplus
 }

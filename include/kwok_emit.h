@@ -149,6 +149,66 @@ kwk_status kwk_emit_copy(kwk_emitter* em, kwk_emit_item* items, uint64_t* offset
 /* HIP events around the last kwk_emit's kernels (bench timing): milliseconds between them */
 kwk_status kwk_emit_elapsed(kwk_emitter* em, float* ms);
 
+/* ---- Finalizer patches (DESIGN.md §5 "Finalizer patches"): Next.Finalizers' JSON patch of every
+ * fired object (pkg/utils/lifecycle/next.go:43-60, finalizersModify, finalizers.go:83-111), which
+ * playStage sends before the object's delete or merge patches — byte-equal to
+ * kwk_patch_finalizers (kwok_patch.h) of the same stage and list.
+ *
+ * State: one order word per slot (kwok_patch.h: bits 4k..4k+3 the dictionary id of list position
+ * k < 7, 15 = a value outside the dictionary; bits 28-31 the length 0..7, or 0xF = more than 7
+ * entries, not representable), set by the host at ingest and after every kwk_upsert /
+ * kwk_replace round trip (kwk_patch_finalizer_word), as it sets the guard words.  A fired record
+ * whose stage has KWK_NEXT_FIN and whose ops are not empty gives one item: `[` + the ops joined by
+ * `,` + `]`; its word becomes the list after the ops (0xF when that is longer than 7); a fired
+ * KWK_NEXT_DELETE stage leaves word 0 after its item (the harness re-creates the object without
+ * finalizers).  A word of 0xF (or a slot beyond the capacity) on a KWK_NEXT_FIN stage gives an
+ * item with KWK_EMIT_HOST and no bytes, the word kept: the host renders it and sets the word.
+ * The word's update does not depend on where the record's merge-patch items were rendered.
+ *
+ * The finalizer items are a stream of their own beside the merge-patch items of the same output
+ * set; the merge-patch outputs are what they are without a finalizer program.  The overflow
+ * protocol is the sets': an emission whose finalizer totals exceed kwk_emit_reserve_fin's room
+ * writes nothing — neither stream, neither word array — raises the in-flight flag, and every
+ * reader of it and of the emissions behind it returns KWK_ECAP; a merge-patch overflow leaves the
+ * order words alone in the same way. */
+typedef struct {
+  uint32_t n_values;              /* dictionary values, <= 15 */
+  uint32_t n_stages;              /* the emit program's */
+  const uint32_t* value_off;      /* n_values + 1: value i is values[value_off[i] .. value_off[i + 1]) */
+  const char* values;             /* bytes of [A-Za-z0-9._/-] */
+  const uint8_t* stage_flags;     /* n_stages: KWK_NEXT_DELETE | _FIN | _FIN_EMPTY | _FIN_REMOVE */
+  const uint16_t* stage_remove;   /* n_stages: bit id = the stage removes value id */
+  const uint32_t* stage_add_ptr;  /* n_stages + 1 */
+  const uint8_t* stage_add;       /* ids in the Stage's order, duplicates kept; at most 16 per stage */
+} kwk_emit_fin_program;
+
+typedef struct {
+  uint32_t rec;      /* index in the fired list */
+  uint8_t status;    /* KWK_EMIT_* */
+  uint8_t n_ops;
+  uint16_t reserved;
+} kwk_emit_fin_item;
+
+/* after it, every kwk_emit / kwk_emit_step also emits the finalizer patches of its list (once per
+ * emitter; the order words start at 0: no finalizers).  A program none of whose stages has
+ * KWK_NEXT_FIN launches nothing: its stream is empty and the words stay as the host set them */
+kwk_status kwk_emit_finalizers_load(kwk_emitter* em, const kwk_emit_fin_program* prog);
+kwk_status kwk_emit_set_fin_words(kwk_emitter* em, uint32_t first, uint32_t n, const uint32_t* words);
+kwk_status kwk_emit_get_fin_words(kwk_emitter* em, uint32_t first, uint32_t n, uint32_t* words);
+/* room for the finalizer items and bytes of one emission, in every output set (synchronises; clears
+ * the in-flight flag as kwk_emit_reserve does).  A set keeps the room it has: a smaller reservation
+ * applies only to the sets made afterwards (kwk_emit_reserve_sets with another number of sets) */
+kwk_status kwk_emit_reserve_fin(kwk_emitter* em, uint32_t max_items, uint64_t max_bytes);
+/* the selected emission's finalizer stream (kwk_emit_select): totals (KWK_ECAP exactly when
+ * kwk_emit_result returns it), device outputs, host copies (offsets: n_items + 1 entries).  With
+ * KWK_ECAP the totals are the room to reserve only when the finalizer stream itself was too large
+ * (kwk_emit_last_error names kwk_emit_reserve_fin); for an emission whose merge patches overflowed,
+ * or that stood down behind an earlier one, they mean nothing (0 where the stream was not sized) */
+kwk_status kwk_emit_fin_result(kwk_emitter* em, uint32_t* n_items, uint64_t* n_bytes);
+kwk_status kwk_emit_fin_device(kwk_emitter* em, const kwk_emit_fin_item** items, const uint64_t** offsets,
+                               const char** bytes);
+kwk_status kwk_emit_fin_copy(kwk_emitter* em, kwk_emit_fin_item* items, uint64_t* offsets, char* bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -98,6 +98,36 @@ kwk_status kwk_patch_object_values(kwk_patcher* p, uint32_t tid, uint32_t n, con
                                    const char* skeleton, uint64_t skeleton_len, kwk_patch_fn fn, void* user,
                                    uint32_t n_threads, uint32_t n_calls, uint32_t stride, uint8_t* values, uint8_t* ok);
 
+/* ---- finalizer JSON patches (Next.Finalizers, pkg/utils/lifecycle/next.go:43-60, built by
+ * finalizersModify, finalizers.go:83-111): the second thing playStage sends for a fired object,
+ * before its delete or its merge patches.
+ *
+ * The spec's optional "finalizers": {"values": [<the Stage set's finalizer dictionary, id order>],
+ * "stages": [{"flags": KWK_NEXT_DELETE | _FIN | _FIN_EMPTY | _FIN_REMOVE bits, "add": [ids in the
+ * Stage's order, duplicates kept], "remove": [ids]}, ...]} (kwok_amd/host/compiler.py:
+ * finalizer_spec / kwk_program_finalizer_spec).  Ids are 0..14; KWK_FIN_OTHER stands for a value of an
+ * object's list that is not in the dictionary.
+ *
+ * The order word of an object's metadata.finalizers (the device emitter's per-slot state,
+ * kwok_emit.h): bits 4k..4k+3 (k < 7) the id of list position k, bits 28-31 the length 0..7 or 0xF
+ * for a list of more than 7 entries (KWK_FIN_WORD_HOST, every other bit 0); unused nibbles 0. */
+#define KWK_FIN_MAX_VALUES 15u
+#define KWK_FIN_OTHER 15u
+#define KWK_FIN_MAX_LEN 7u
+#define KWK_FIN_WORD_HOST 0xF0000000u
+
+/* Next.Finalizers: the JSON patch bytes for `stage` against the object's metadata.finalizers
+ * (fins: n NUL-separated values in list order); *len = 0 when there are no ops (the reference sends nothing).
+ * The bytes are Go's json.Marshal([]jsonpathOperation): compact, keys op, path, value.  KWK_ECAP
+ * with *len = the bytes needed when cap is too small; KWK_ESTATE without a finalizer program. */
+kwk_status kwk_patch_finalizers(kwk_patcher* p, uint32_t stage, uint32_t n, const char* fins, uint64_t fins_len,
+                                char* out, uint64_t cap, uint64_t* len);
+/* the order word of a list (values outside the dictionary: KWK_FIN_OTHER; n > 7: KWK_FIN_WORD_HOST) */
+kwk_status kwk_patch_finalizer_word(kwk_patcher* p, uint32_t n, const char* fins, uint64_t fins_len, uint32_t* word);
+/* ... and the list of a word of known ids: *n values, NUL-terminated each, *len bytes.  KWK_EINVAL
+ * (the message names the cause) for KWK_FIN_WORD_HOST and for an entry KWK_FIN_OTHER */
+kwk_status kwk_patch_finalizer_list(kwk_patcher* p, uint32_t word, uint32_t* n, char* out, uint64_t cap, uint64_t* len);
+
 #ifdef __cplusplus
 }
 #endif

@@ -970,6 +970,46 @@ struct kwk_program {
     return o;
   }
 
+  // compiler.KindProgram.finalizer_spec: the finalizer program of the patch / emit spec — the
+  // dictionary values in id order; per stage the flags, the add ids in the Stage's order
+  // (duplicates kept) and the remove id set.  Two shapes stay with the host, refused by name
+  std::string finalizer_spec() const {
+    if (fin_bits.size() > 15)
+      throw CompileError("finalizer program not supported natively: " + std::to_string(fin_bits.size()) +
+                         " dictionary values (more than 15); the host renders the finalizer patches");
+    PJ values = PJ::list();
+    for (const auto& fb : fin_bits) {
+      for (const char c : fb.first)
+        if (!((c >= 'A' && c <= 'Z') || (c >= 'a' && c <= 'z') || (c >= '0' && c <= '9') || c == '.' || c == '_' || c == '/' ||
+              c == '-'))
+          throw CompileError("finalizer program not supported natively: value \"" + fb.first +
+                             "\" has a byte outside [A-Za-z0-9._/-] (Go's json.Marshal escaping of it is not pinned by a "
+                             "reference vector); the host renders the finalizer patches");
+      values.push(PJ::str(fb.first));
+    }
+    auto id_of = [&](const std::string& v) {
+      for (size_t i = 0; i < fin_bits.size(); ++i)
+        if (fin_bits[i].first == v) return (long long)i;
+      throw CompileError("finalizer value outside the dictionary: " + v);
+    };
+    PJ sl = PJ::list();
+    for (size_t si = 0; si < stages.size(); ++si) {
+      const Stage& st = stages[si];
+      PJ add = PJ::list(), rm = PJ::list();
+      if (st.has_fin) {
+        for (const std::string& v : st.fin_add) add.push(PJ::integer(id_of(v)));
+        std::set<long long> ids;
+        for (const std::string& v : st.fin_remove) ids.insert(id_of(v));
+        for (long long id : ids) rm.push(PJ::integer(id));
+      }
+      const uint32_t keep = KWK_NEXT_DELETE | KWK_NEXT_FIN | KWK_NEXT_FIN_EMPTY | KWK_NEXT_FIN_REMOVE;
+      sl.push(PJ::dict().set("flags", PJ::integer((long long)(desc[si].flags & keep))).set("add", add).set("remove", rm));
+    }
+    std::string o;
+    kwkpatch::pj_dump(o, PJ::dict().set("values", values).set("stages", sl));
+    return o;
+  }
+
   // patchtpl.PatchProgram: the spec and (stage, patch) -> template id
   std::string patch_spec(const JV& funcs, const std::string& version, std::vector<std::vector<int>>& template_of) {
     std::map<std::string, std::pair<bool, std::string>> fmap;  // name -> (callback, const)
@@ -1182,6 +1222,18 @@ kwk_status kwk_program_encoder_spec(kwk_program* p, const char** json) {
   if (!p || !json) return fail(KWK_EINVAL, "null argument");
   try {
     p->out_json = p->encoder_spec();
+  } catch (const std::exception& e) {
+    return fail(KWK_EINVAL, e.what());
+  }
+  *json = p->out_json.c_str();
+  return KWK_OK;
+}
+
+kwk_status kwk_program_finalizer_spec(kwk_program* p, const char** json) {
+  ErrScope es_(p ? &p->err : nullptr);
+  if (!p || !json) return fail(KWK_EINVAL, "null argument");
+  try {
+    p->out_json = p->finalizer_spec();
   } catch (const std::exception& e) {
     return fail(KWK_EINVAL, e.what());
   }

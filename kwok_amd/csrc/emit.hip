@@ -19,6 +19,10 @@
 // record's segment, hence its slot.  Emissions rotate through output sets (kwk_emit_reserve_sets), so
 // the emissions of a fused group are enqueued back to back; a device flag stops the ones behind an
 // emission that exceeded its set.
+// With a finalizer program (kwk_emit_finalizers_load) three more per emission write the fired
+// objects' finalizer JSON patches into a stream of their own: emit_fin_size_kernel and
+// emit_scan_kernel over its tile arrays between the merge patches' scan and writer (an overflow of
+// either stream stops both writers), emit_fin_write_kernel last ("finalizer patches" below).
 // The skeleton pieces and literal runs are staged in LDS when they fit (12 KiB of literals).
 // Roofline: HBM-bound on the patch bytes written (plus 8 bytes read per record and the literal
 // runs, L2-resident); the byte copy is 1-byte stores coalesced per wave.
@@ -1051,6 +1055,291 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kChunk ?
   if (lane == 0 && n_ok) atomicAdd(&a.totals[3], (unsigned long long)n_ok);
 }
 
+// ---- finalizer patches (kwok_emit.h "Finalizer patches"; finalizersModify, finalizers.go:83-111) ----
+// A record's JSON patch is `[` + ops joined by `,` + `]`, every op one of a fixed set of literals:
+// the remove-all op, the remove op of list index 0..6, the add op of dictionary id 0..14 and each
+// stage's whole-list add.  Which ops a record has follows from its stage's entry and its slot's
+// order word alone (fin_plan), so the passes are the merge patches': emit_fin_size_kernel (per
+// tile: items and bytes), emit_scan_kernel over the finalizer tile arrays, emit_fin_write_kernel
+// (items, offsets, the new order words, the bytes).  The stage entries and the literal table sit in
+// LDS.  The bytes of a tile are contiguous in the output: each thread copies its record's literals
+// into an LDS window of the tile's byte range, and the block stores the window as 16-byte chunks,
+// consecutive threads consecutive chunks (the two chunks a tile shares with its neighbours: byte
+// stores of the tile's own bytes).
+constexpr uint32_t kFinLitBytes = 8192;  // the op literals (LDS)
+constexpr uint32_t kFinMaxAdd = 16;      // add ids of one stage: 4 bits each in the stage entry
+constexpr uint32_t kFinWin = 16384;      // bytes of a tile assembled in LDS per pass
+constexpr uint32_t kFinLitRemoveAll = 0, kFinLitRemoveIdx = 1, kFinLitAddId = 8, kFinLitAddList = 23;
+constexpr uint32_t kFinLitMax = kFinLitAddList + KWK_MAX_STAGES;
+constexpr uint32_t kFinWordHost = 0xF0000000u;
+
+struct FinArgs {
+  const uint4* stages;   // per stage: x = remove set | flags << 16 | adds << 24, y / z = the add ids, 4 bits each
+  const uint32_t* lit;   // kFinLitMax entries: byte offset | length << 16
+  const uint32_t* lits;  // the literals' bytes as dwords
+  uint32_t n_stages, n_lit_words;
+  uint32_t* words;
+  uint32_t* tile_items;
+  unsigned long long* tile_bytes;
+  unsigned long long* totals;  // the finalizer stream's (EmitArgs::totals' layout)
+  kwk_emit_fin_item* items;
+  uint64_t* offsets;
+  char* out;
+  unsigned long long cap_items, cap_bytes;
+};
+
+// a record's ops: bits 0-6 the remove op of list index k, 7 the remove-all op, 8 the stage's
+// whole-list add, 9 + j the add op of the stage's j-th add id
+struct FinPlan {
+  uint32_t desc, n_ops;
+  uint32_t status;  // 0: no item, 1: an item with bytes, 2: an item for the host
+  uint32_t nw;      // the order word afterwards
+};
+
+__device__ __forceinline__ FinPlan fin_plan(const uint4 S, uint32_t w, bool valid) {
+  const uint32_t flags = (S.x >> 16) & 0xFFu, n_add = S.x >> 24, remove = S.x & 0xFFFFu;
+  FinPlan p{0u, 0u, 0u, w};
+  if (!(flags & KWK_NEXT_FIN)) {
+    if (flags & KWK_NEXT_DELETE) p.nw = 0u;
+    return p;
+  }
+  const uint32_t n = w >> 28;
+  if (!valid || n > 7u) {
+    p.status = 2u;
+    return p;
+  }
+  uint32_t present = 0, rm = 0;
+#pragma unroll
+  for (uint32_t k = 0; k < 7u; ++k) {
+    const uint32_t id = (w >> (4u * k)) & 15u;
+    if (k < n) {
+      present |= 1u << id;
+      if (id != 15u && ((remove >> id) & 1u)) rm |= 1u << k;
+    }
+  }
+  bool empty = (flags & KWK_NEXT_FIN_EMPTY) != 0;
+  if (empty || !(flags & KWK_NEXT_FIN_REMOVE)) {
+    rm = 0;
+  } else if ((uint32_t)__popc(rm) == n) {  // every entry removed (0 == 0 too): the list goes as a whole
+    empty = true;
+    rm = 0;
+  }
+  uint32_t list = 0, m = 0;
+  auto push = [&](uint32_t id) __attribute__((always_inline)) {
+    if (m < 7u) list |= id << (4u * m);
+    ++m;
+  };
+  uint32_t desc = rm;
+  if (!empty) {
+#pragma unroll
+    for (uint32_t k = 0; k < 7u; ++k)
+      if (k < n && !((rm >> k) & 1u)) push((w >> (4u * k)) & 15u);
+  } else if (n) {
+    desc |= 1u << 7;
+  }
+  const uint64_t adds = (uint64_t)S.y | (uint64_t)S.z << 32;
+  if (n_add) {
+    if (empty || n == 0u) {  // finalizersAdd over no list: one add of the whole list
+      desc |= 1u << 8;
+      for (uint32_t j = 0; j < n_add; ++j) push((uint32_t)(adds >> (4u * j)) & 15u);
+    } else {
+      for (uint32_t j = 0; j < n_add; ++j) {  // membership in the original list
+        const uint32_t id = (uint32_t)(adds >> (4u * j)) & 15u;
+        if (!((present >> id) & 1u)) {
+          desc |= 1u << (9u + j);
+          push(id);
+        }
+      }
+    }
+  }
+  p.desc = desc;
+  p.n_ops = (uint32_t)__popc(desc);
+  p.status = p.n_ops ? 1u : 0u;
+  p.nw = m > 7u ? kFinWordHost : list | m << 28;
+  if (flags & KWK_NEXT_DELETE) p.nw = 0u;
+  return p;
+}
+
+// the word is gathered only for the stages that read or reset it (most records of a list have neither)
+__device__ __forceinline__ bool fin_reads_word(const uint4 S, const Rec& x) {
+  return x.valid && ((S.x >> 16) & (KWK_NEXT_FIN | KWK_NEXT_DELETE)) != 0u;
+}
+
+// the literal of every op of a plan, in the patch's order: removes from the highest index down
+template <typename F>
+__device__ __forceinline__ void fin_ops(uint32_t desc, uint32_t stage, const uint4 S, F&& f) {
+  for (int k = 6; k >= 0; --k)
+    if ((desc >> k) & 1u) f(kFinLitRemoveIdx + (uint32_t)k);
+  if (desc & (1u << 7)) f(kFinLitRemoveAll);
+  if (desc & (1u << 8)) f(kFinLitAddList + stage);
+  const uint64_t adds = (uint64_t)S.y | (uint64_t)S.z << 32;
+  for (uint32_t sel = desc >> 9; sel; sel &= sel - 1u) {
+    const uint32_t j = (uint32_t)__ffs((int)sel) - 1u;
+    f(kFinLitAddId + ((uint32_t)(adds >> (4u * j)) & 15u));
+  }
+}
+
+__device__ __forceinline__ uint32_t fin_bytes(const FinPlan& p, uint32_t stage, const uint4 S, const uint32_t* s_lit) {
+  if (!p.n_ops) return 0u;
+  uint32_t b = p.n_ops + 1u;  // [ ] and the commas
+  fin_ops(p.desc, stage, S, [&](uint32_t li) { b += s_lit[li] >> 16; });
+  return b;
+}
+
+__device__ __forceinline__ void fin_stage_tables(const FinArgs& f, uint4* s_stage, uint32_t* s_lit) {
+  for (uint32_t j = threadIdx.x; j < KWK_MAX_STAGES; j += blockDim.x)
+    s_stage[j] = j < f.n_stages ? f.stages[j] : make_uint4(0u, 0u, 0u, 0u);
+  for (uint32_t j = threadIdx.x; j < kFinLitMax; j += blockDim.x) s_lit[j] = f.lit[j];
+}
+
+template <uint32_t kSrc>
+__global__ __launch_bounds__(kBlock) void emit_fin_size_kernel(EmitArgs a, FinArgs f) {
+  __shared__ uint4 s_stage[KWK_MAX_STAGES];
+  __shared__ uint32_t s_lit[kFinLitMax];
+  __shared__ uint32_t s_i[kWaves];
+  __shared__ unsigned long long s_b[kWaves];
+  if (*a.sticky) return;  // this emission's merge patches or an earlier emission exceeded a set
+  fin_stage_tables(f, s_stage, s_lit);
+  __syncthreads();
+  const uint32_t n = list_len<kSrc>(a), n_tiles = (n + kTile - 1) / kTile;
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  uint32_t* s_win = nullptr;
+  if constexpr (kSrc == kSrc16) s_win = seg_win_lds();
+  for (uint32_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+    uint32_t it = 0;
+    unsigned long long by = 0;
+    const uint32_t r = t * kTile + threadIdx.x;
+    SegWin sw{};
+    if constexpr (kSrc == kSrc16) sw = tile_segs(a, t, n, s_win);
+    if (r < n) {
+      Rec x;
+      if constexpr (kSrc == kSrc16) x = fetch16(a, r, sw, s_win);
+      else x = fetch(a, r);
+      if (x.stage < f.n_stages) {
+        const uint4 S = s_stage[x.stage];
+        const FinPlan p = fin_plan(S, fin_reads_word(S, x) ? f.words[x.slot] : 0u, x.valid);
+        it = p.status ? 1u : 0u;
+        by = fin_bytes(p, x.stage, S, s_lit);
+      }
+    }
+    it = wave_sum(it);
+    by = wave_sum(by);
+    if (lane == 0) {
+      s_i[wave] = it;
+      s_b[wave] = by;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      uint32_t ti = 0;
+      unsigned long long tb = 0;
+      for (uint32_t w = 0; w < kWaves; ++w) {
+        ti += s_i[w];
+        tb += s_b[w];
+      }
+      f.tile_items[t] = ti;
+      f.tile_bytes[t] = tb;
+    }
+    __syncthreads();
+  }
+}
+
+template <uint32_t kSrc>
+__global__ __launch_bounds__(kBlock) void emit_fin_write_kernel(EmitArgs a, FinArgs f) {
+  __shared__ uint4 s_stage[KWK_MAX_STAGES];
+  __shared__ uint32_t s_lit[kFinLitMax];
+  __shared__ uint32_t s_lits[kFinLitBytes / 4];
+  __shared__ __attribute__((aligned(16))) uint4 s_out[kFinWin / 16];
+  __shared__ uint32_t s_wi[kWaves], s_wb[kWaves];
+  __shared__ uint32_t s_tend;
+  if (*a.sticky) return;  // an emission in flight (this one included) exceeded a set: nothing is written
+  if (a.totals[0] > a.cap_items || a.totals[1] > a.cap_bytes || a.totals[2]) return;  // the merge patches did
+  const unsigned long long tot_i = f.totals[0], tot_b = f.totals[1];
+  if (tot_i > f.cap_items || tot_b > f.cap_bytes) return;
+  fin_stage_tables(f, s_stage, s_lit);
+  for (uint32_t j = threadIdx.x; j < f.n_lit_words && j < kFinLitBytes / 4; j += blockDim.x) s_lits[j] = f.lits[j];
+  __syncthreads();
+  const uint32_t n = list_len<kSrc>(a), n_tiles = (n + kTile - 1) / kTile;
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  uint32_t* s_win = nullptr;
+  if constexpr (kSrc == kSrc16) s_win = seg_win_lds();
+  if (blockIdx.x == 0 && threadIdx.x == 0) f.offsets[tot_i] = tot_b;
+  uint8_t* const sb = reinterpret_cast<uint8_t*>(s_out);
+  const uint8_t* const lb = reinterpret_cast<const uint8_t*>(s_lits);
+  for (uint32_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+    const uint32_t lr = threadIdx.x, r = t * kTile + lr;
+    Rec x{0u, 0xFFFFFFFFu, false};
+    FinPlan p{0u, 0u, 0u, 0u};
+    uint4 S = make_uint4(0u, 0u, 0u, 0u);
+    uint32_t w = 0, by = 0;
+    SegWin sw{};
+    if constexpr (kSrc == kSrc16) sw = tile_segs(a, t, n, s_win);
+    if (r < n) {
+      if constexpr (kSrc == kSrc16) x = fetch16(a, r, sw, s_win);
+      else x = fetch(a, r);
+      if (x.stage < f.n_stages) {
+        S = s_stage[x.stage];
+        w = fin_reads_word(S, x) ? f.words[x.slot] : 0u;
+        p = fin_plan(S, w, x.valid);
+        by = fin_bytes(p, x.stage, S, s_lit);
+      }
+    }
+    const uint32_t has = p.status ? 1u : 0u;
+    const uint32_t ii = wave_incl(has, lane), ib = wave_incl(by, lane);
+    if (lane == 63) {
+      s_wi[wave] = ii;
+      s_wb[wave] = ib;
+    }
+    __syncthreads();
+    const unsigned long long tb = f.tile_bytes[t];
+    const uint32_t head = (uint32_t)(tb & 15ull);  // positions below are relative to the tile's 16-byte aligned base
+    uint32_t item = f.tile_items[t] + ii - has, g0 = head + ib - by;
+    for (uint32_t v = 0; v < wave; ++v) {
+      item += s_wi[v];
+      g0 += s_wb[v];
+    }
+    const uint32_t g1 = g0 + by;
+    if (lr == kTile - 1u) s_tend = g1;
+    if (has) {
+      f.items[item] = kwk_emit_fin_item{r, (uint8_t)(p.status == 2u ? KWK_EMIT_HOST : KWK_EMIT_OK), (uint8_t)p.n_ops, 0};
+      f.offsets[item] = (tb & ~15ull) + g0;
+    }
+    if (x.stage < f.n_stages && fin_reads_word(S, x) && p.status != 2u && p.nw != w) f.words[x.slot] = p.nw;
+    __syncthreads();  // s_tend
+    const uint32_t tend = s_tend;
+    char* const base = f.out + (tb & ~15ull);
+    for (uint32_t W = 0; W < tend; W += kFinWin) {  // (block-uniform)
+      if (by && g1 > W && g0 < W + kFinWin) {  // this record's bytes inside the window
+        uint32_t q = g0 - W;                    // (wraps below the window: such bytes are skipped)
+        auto put = [&](uint32_t c) __attribute__((always_inline)) {
+          if (q < kFinWin) sb[q] = (uint8_t)c;
+          ++q;
+        };
+        put('[');
+        bool first = true;
+        fin_ops(p.desc, x.stage, S, [&](uint32_t li) {
+          if (!first) put(',');
+          first = false;
+          const uint32_t e = s_lit[li], off = e & 0xFFFFu, len = e >> 16;
+          for (uint32_t b = 0; b < len; ++b) put(lb[off + b]);
+        });
+        put(']');
+      }
+      __syncthreads();
+      for (uint32_t c = threadIdx.x; c < kFinWin / 16u; c += kBlock) {
+        const uint32_t P = W + 16u * c;
+        const uint32_t lo = max(P, head), hi = min(P + 16u, tend);
+        if (lo >= hi) continue;
+        if (hi - lo == 16u) {
+          *reinterpret_cast<uint4*>(base + P) = s_out[c];
+        } else {  // a chunk shared with the neighbouring tile: this tile's bytes only
+          for (uint32_t b = lo; b < hi; ++b) base[b] = (char)sb[b - W];
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
 }  // namespace
 
 struct kwk_emitter {
@@ -1078,6 +1367,12 @@ struct kwk_emitter {
     uint64_t cap_items = 0, cap_bytes = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool emitted = false;
+    // the finalizer stream (kwk_emit_finalizers_load)
+    unsigned long long* d_fin_totals = nullptr;  // 8 words of d_fin_totals_all
+    kwk_emit_fin_item* d_fin_items = nullptr;
+    uint64_t* d_fin_offsets = nullptr;
+    char* d_fin_out = nullptr;
+    uint64_t fin_cap_items = 0, fin_cap_bytes = 0;
   };
   std::vector<OutSet> sets;
   uint32_t cur = 0;               // the set of the last emission
@@ -1094,6 +1389,11 @@ struct kwk_emitter {
   OutSet& selected() { return sets[(cur + (uint32_t)sets.size() - sel) % (uint32_t)sets.size()]; }
   bool chunk_ok = false;          // skeletons own consecutive, disjoint piece ranges (the chunk writer's templates)
   bool lencache = false;          // words' bits 24-31 cache the value lengths (emit_lens_kernel)
+  bool fin = false;               // a finalizer program is loaded: every emission also emits its stream
+  bool fin_any = false;           // ... and some stage of it has KWK_NEXT_FIN (else its launches are skipped)
+  FinArgs f{};                    // its device tables, order words and tile arrays
+  unsigned long long* d_fin_totals_all = nullptr;
+  uint64_t fin_req_items = 0, fin_req_bytes = 0;  // kwk_emit_reserve_fin's room, given to every set
   uint64_t tpl_lits = 0;          // literal bytes of every skeleton's pieces
   uint32_t tpl_now_slots = 0;     // Now slots of every skeleton's pieces
 
@@ -1109,6 +1409,9 @@ struct kwk_emitter {
     if (o.d_items) hipFree(o.d_items);
     if (o.d_offsets) hipFree(o.d_offsets);
     if (o.d_out) hipFree(o.d_out);
+    if (o.d_fin_items) hipFree(o.d_fin_items);
+    if (o.d_fin_offsets) hipFree(o.d_fin_offsets);
+    if (o.d_fin_out) hipFree(o.d_fin_out);
     if (o.ev0) hipEventDestroy(o.ev0);
     if (o.ev1) hipEventDestroy(o.ev1);
     o = OutSet{};
@@ -1167,6 +1470,7 @@ kwk_status make_sets(kwk_emitter* em, uint32_t n) {
   em->sets.assign(n, kwk_emitter::OutSet{});
   for (uint32_t i = 0; i < n; ++i) {
     em->sets[i].d_totals = em->d_totals_all + 8u * i;
+    em->sets[i].d_fin_totals = em->d_fin_totals_all ? em->d_fin_totals_all + 8u * i : nullptr;
     HIP_TRY(hipEventCreate(&em->sets[i].ev0));
     HIP_TRY(hipEventCreate(&em->sets[i].ev1));
   }
@@ -1400,6 +1704,29 @@ kwk_status reserve_sets(kwk_emitter* em, uint32_t n_sets, uint32_t max_items, ui
       o.cap_bytes = max_bytes;
     }
   }
+  if (em->fin) {  // the finalizer stream's room, in every set
+    for (kwk_emitter::OutSet& o : em->sets) {
+      if (em->fin_req_items > o.fin_cap_items || !o.d_fin_offsets) {
+        if (o.d_fin_items) HIP_TRY(hipFree(o.d_fin_items));
+        if (o.d_fin_offsets) HIP_TRY(hipFree(o.d_fin_offsets));
+        o.d_fin_items = nullptr;
+        o.d_fin_offsets = nullptr;
+        o.fin_cap_items = 0;
+        const size_t ni = (size_t)std::max<uint64_t>(1, em->fin_req_items);
+        HIP_TRY(hipMalloc(&o.d_fin_items, ni * sizeof(kwk_emit_fin_item)));
+        HIP_TRY(hipMalloc(&o.d_fin_offsets, (ni + 1) * 8));
+        o.fin_cap_items = ni;
+      }
+      if (em->fin_req_bytes > o.fin_cap_bytes || !o.d_fin_out) {
+        if (o.d_fin_out) HIP_TRY(hipFree(o.d_fin_out));
+        o.d_fin_out = nullptr;
+        o.fin_cap_bytes = 0;
+        const size_t nb = (size_t)std::max<uint64_t>(1, em->fin_req_bytes);
+        HIP_TRY(hipMalloc(&o.d_fin_out, nb + 16));
+        o.fin_cap_bytes = nb;
+      }
+    }
+  }
   if (em->sticky_armed) {  // the host reserves again: later emissions run
     if (kwk_status st = fill(em, em->d_sticky, 0, 4)) return st;
     em->sticky_armed = false;
@@ -1414,6 +1741,8 @@ kwk_status enqueue_emission(kwk_emitter* em, EmitArgs& a, int64_t now_ns) {
   if (kwk_status st = bind(em)) return st;
   if (!em->sets[0].d_offsets)
     if (kwk_status st = reserve_sets(em, (uint32_t)em->sets.size(), 1, 1)) return st;
+  if (em->fin && !em->sets[0].d_fin_offsets)
+    if (kwk_status st = reserve_sets(em, (uint32_t)em->sets.size(), 0, 0)) return st;
   const bool src16 = a.p16 != nullptr;
   if (src16 && a.n_segs + 1u > em->seg_cap) {
     if (em->d_seg_base) HIP_TRY(hipFree(em->d_seg_base));  // (synchronises the device: no kernel still reads it)
@@ -1445,12 +1774,30 @@ kwk_status enqueue_emission(kwk_emitter* em, EmitArgs& a, int64_t now_ns) {
   if (now.size() >= sizeof a.now) return fail(KWK_EINVAL, "Now() text too long");
   memcpy(a.now, now.data(), now.size());
   a.now_len = (uint32_t)now.size();
-  if (em->saw_cap && em->sticky_armed) {  // the host has seen the overflow and emits again
+  // (one set with a finalizer program: the flag only joins the emission's two streams — a finalizer
+  // overflow stops its merge-patch writer — and every emission stands alone, so it starts cleared)
+  if ((em->saw_cap || (em->fin && n_sets == 1u)) && em->sticky_armed) {  // the host has seen the overflow and emits again
     HIP_TRY(hipMemsetAsync(em->d_sticky, 0, 4, em->stream));
     em->sticky_armed = false;
   }
   em->saw_cap = false;
-  if (a.sticky_on) em->sticky_armed = true;
+  if (a.sticky_on || em->fin) em->sticky_armed = true;
+  FinArgs f = em->f;
+  EmitArgs fa = a;  // emit_scan_kernel over the finalizer stream's tile arrays and totals
+  if (em->fin) {
+    f.totals = o.d_fin_totals;
+    f.items = o.d_fin_items;
+    f.offsets = o.d_fin_offsets;
+    f.out = o.d_fin_out;
+    f.cap_items = o.fin_cap_items;
+    f.cap_bytes = o.fin_cap_bytes;
+    fa.tile_items = f.tile_items;
+    fa.tile_bytes = f.tile_bytes;
+    fa.totals = f.totals;
+    fa.cap_items = f.cap_items;
+    fa.cap_bytes = f.cap_bytes;
+    fa.sticky_on = 1u;
+  }
   // the list's count lives on the device: every tile loop reads it; the grid covers the capacity
   HIP_TRY(hipEventRecord(o.ev0, em->stream));
   bool lds = em->p.n_pieces <= kLdsPieces && em->p.n_lits + 8u <= kLdsLits && em->p.n_skels <= kLdsSkels;
@@ -1474,6 +1821,15 @@ kwk_status enqueue_emission(kwk_emitter* em, EmitArgs& a, int64_t now_ns) {
   HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(emit_scan_kernel, dim3(1), dim3(kScanBlock), 0, em->stream, a);
   HIP_TRY(hipGetLastError());
+  if (em->fin && !em->fin_any) {  // no stage has a finalizers op: an empty stream, no launch
+    HIP_TRY(hipMemsetAsync(f.totals, 0, 5 * 8, em->stream));
+  } else if (em->fin) {  // sized and scanned before either writer runs: an overflow of one stream stops both
+    if (src16) hipLaunchKernelGGL(emit_fin_size_kernel<kSrc16>, dim3(em->grid), dim3(kBlock), 0, em->stream, a, f);
+    else hipLaunchKernelGGL(emit_fin_size_kernel<kSrc32>, dim3(em->grid), dim3(kBlock), 0, em->stream, a, f);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(emit_scan_kernel, dim3(1), dim3(kScanBlock), 0, em->stream, fa);
+    HIP_TRY(hipGetLastError());
+  }
   const bool wl = lds && vals16;  // the write kernel's LDS path also stages the value rows
   // the chunk writer: templates (literals + Now per slot) within kTplBytes, pieces in skeleton order
   const bool chunk = wl && em->chunk_ok && em->tpl_lits + (uint64_t)em->tpl_now_slots * a.now_len + 16u <= kTplBytes;
@@ -1494,6 +1850,11 @@ kwk_status enqueue_emission(kwk_emitter* em, EmitArgs& a, int64_t now_ns) {
   const uint32_t wgrid = std::max(1u, std::min(em->max_tiles, em->cus * (uint32_t)em->write_occ[vi]));
   HIP_TRY(hipLaunchKernel(wk, dim3(wgrid), dim3(kBlock), wargs, 0, em->stream));
   HIP_TRY(hipGetLastError());
+  if (em->fin && em->fin_any) {
+    if (src16) hipLaunchKernelGGL(emit_fin_write_kernel<kSrc16>, dim3(em->grid), dim3(kBlock), 0, em->stream, a, f);
+    else hipLaunchKernelGGL(emit_fin_write_kernel<kSrc32>, dim3(em->grid), dim3(kBlock), 0, em->stream, a, f);
+    HIP_TRY(hipGetLastError());
+  }
   HIP_TRY(hipEventRecord(o.ev1, em->stream));
   o.emitted = true;
   em->cur = (em->cur + 1u) % n_sets;
@@ -1604,6 +1965,15 @@ kwk_status kwk_emit_result(kwk_emitter* em, uint32_t* n_items, uint64_t* n_bytes
     return fail(KWK_ECAP, "emission exceeds the reservation: kwk_emit_reserve(" + std::to_string(t[0]) + ", " +
                               std::to_string(t[1]) + ") and emit again");
   }
+  if (em->fin && o.d_fin_totals) {
+    unsigned long long ft[2];
+    if (kwk_status st = copy_out(em, ft, o.d_fin_totals, sizeof ft)) return st;
+    if (ft[0] > o.fin_cap_items || ft[1] > o.fin_cap_bytes) {
+      em->saw_cap = true;
+      return fail(KWK_ECAP, "the emission's finalizer patches exceed their reservation: kwk_emit_reserve_fin(" +
+                                std::to_string(ft[0]) + ", " + std::to_string(ft[1]) + ") and emit again");
+    }
+  }
   return KWK_OK;
 }
 
@@ -1652,6 +2022,168 @@ kwk_status kwk_emit_elapsed(kwk_emitter* em, float* ms) {
   if (kwk_status st = bind(em)) return st;
   HIP_TRY(hipEventSynchronize(o.ev1));
   HIP_TRY(hipEventElapsedTime(ms, o.ev0, o.ev1));
+  return KWK_OK;
+}
+
+
+kwk_status kwk_emit_finalizers_load(kwk_emitter* em, const kwk_emit_fin_program* g) {
+  ErrScope es_(em ? &em->err : nullptr);
+  if (!em || !g) return fail(KWK_EINVAL, "null argument");
+  if (em->fin) return fail(KWK_ESTATE, "kwk_emit_finalizers_load: the emitter has a finalizer program");
+  if (g->n_values > 15u)
+    return fail(KWK_EINVAL, "finalizer program: " + std::to_string(g->n_values) + " dictionary values (more than 15)");
+  if (g->n_stages != em->p.n_stages || g->n_stages > KWK_MAX_STAGES)
+    return fail(KWK_EINVAL, "finalizer program: " + std::to_string(g->n_stages) + " stages, the emit program has " +
+                                std::to_string(em->p.n_stages));
+  if ((g->n_values && (!g->value_off || !g->values)) || (g->n_stages && (!g->stage_flags || !g->stage_remove || !g->stage_add_ptr)))
+    return fail(KWK_EINVAL, "finalizer program: null array");
+  std::vector<std::string> vals;
+  for (uint32_t i = 0; i < g->n_values; ++i) {
+    if (g->value_off[i + 1] < g->value_off[i]) return fail(KWK_EINVAL, "finalizer program: value offsets");
+    vals.emplace_back(g->values + g->value_off[i], g->values + g->value_off[i + 1]);
+    for (const char c : vals.back())
+      if (!((c >= 'A' && c <= 'Z') || (c >= 'a' && c <= 'z') || (c >= '0' && c <= '9') || c == '.' || c == '_' || c == '/' ||
+            c == '-'))
+        return fail(KWK_EINVAL, "finalizer program: value \"" + vals.back() + "\" has a byte outside [A-Za-z0-9._/-]");
+  }
+  std::vector<std::string> lit(kFinLitMax);
+  lit[kFinLitRemoveAll] = "{\"op\":\"remove\",\"path\":\"/metadata/finalizers\"}";
+  for (uint32_t k = 0; k < 7u; ++k)
+    lit[kFinLitRemoveIdx + k] = "{\"op\":\"remove\",\"path\":\"/metadata/finalizers/" + std::to_string(k) + "\"}";
+  for (uint32_t i = 0; i < g->n_values; ++i)
+    lit[kFinLitAddId + i] = "{\"op\":\"add\",\"path\":\"/metadata/finalizers/-\",\"value\":\"" + vals[i] + "\"}";
+  std::vector<uint4> stages(std::max(1u, g->n_stages), make_uint4(0u, 0u, 0u, 0u));
+  if (g->n_stages && g->stage_add_ptr[0] != 0) return fail(KWK_EINVAL, "finalizer program: stage_add_ptr[0] != 0");
+  for (uint32_t s = 0; s < g->n_stages; ++s) {
+    const uint32_t a0 = g->stage_add_ptr[s], a1 = g->stage_add_ptr[s + 1];
+    if (a1 < a0 || a1 - a0 > kFinMaxAdd)
+      return fail(KWK_EINVAL, "finalizer program: stage " + std::to_string(s) + " adds more than 16 values");
+    if (a1 > a0 && !g->stage_add) return fail(KWK_EINVAL, "finalizer program: null array");
+    if (g->stage_remove[s] >> g->n_values) return fail(KWK_EINVAL, "finalizer program: remove id out of range");
+    uint64_t adds = 0;
+    std::string whole = "{\"op\":\"add\",\"path\":\"/metadata/finalizers\",\"value\":[";
+    for (uint32_t j = a0; j < a1; ++j) {
+      const uint32_t id = g->stage_add[j];
+      if (id >= g->n_values) return fail(KWK_EINVAL, "finalizer program: add id out of range");
+      adds |= (uint64_t)id << (4u * (j - a0));
+      whole += (j > a0 ? ",\"" : "\"") + vals[id] + "\"";
+    }
+    if (a1 > a0) lit[kFinLitAddList + s] = whole + "]}";
+    const uint32_t keep = KWK_NEXT_DELETE | KWK_NEXT_FIN | KWK_NEXT_FIN_EMPTY | KWK_NEXT_FIN_REMOVE;
+    stages[s] = make_uint4((uint32_t)g->stage_remove[s] | (g->stage_flags[s] & keep) << 16 | (a1 - a0) << 24, (uint32_t)adds,
+                           (uint32_t)(adds >> 32), 0u);
+  }
+  std::vector<uint32_t> ent(kFinLitMax, 0u);
+  std::string bytes;
+  for (uint32_t i = 0; i < kFinLitMax; ++i) {
+    if (bytes.size() + lit[i].size() > kFinLitBytes)
+      return fail(KWK_EINVAL, "finalizer program: more than " + std::to_string(kFinLitBytes) + " bytes of op literals");
+    ent[i] = (uint32_t)bytes.size() | (uint32_t)lit[i].size() << 16;
+    bytes += lit[i];
+  }
+  bytes.resize((bytes.size() + 3u) & ~size_t(3), '\0');
+  std::vector<uint32_t> words(std::max<size_t>(1, bytes.size() / 4), 0u);
+  memcpy(words.data(), bytes.data(), bytes.size());
+  if (kwk_status st = bind(em)) return st;
+  HIP_TRY(hipStreamSynchronize(em->stream));
+  FinArgs f{};
+  if (kwk_status st = upload(em, const_cast<uint4**>(&f.stages), stages.data(), stages.size())) return st;
+  if (kwk_status st = upload(em, const_cast<uint32_t**>(&f.lit), ent.data(), ent.size())) return st;
+  if (kwk_status st = upload(em, const_cast<uint32_t**>(&f.lits), words.data(), words.size())) return st;
+  f.n_stages = g->n_stages;
+  f.n_lit_words = (uint32_t)(bytes.size() / 4);
+  void* d = nullptr;
+  HIP_TRY(hipMalloc(&d, (size_t)std::max(1u, em->capacity) * 4));
+  em->allocs.push_back(d);
+  if (kwk_status st = fill(em, d, 0, (size_t)std::max(1u, em->capacity) * 4)) return st;
+  f.words = static_cast<uint32_t*>(d);
+  HIP_TRY(hipMalloc(&d, (size_t)em->max_tiles * 4));
+  em->allocs.push_back(d);
+  f.tile_items = static_cast<uint32_t*>(d);
+  HIP_TRY(hipMalloc(&d, (size_t)em->max_tiles * 8));
+  em->allocs.push_back(d);
+  f.tile_bytes = static_cast<unsigned long long*>(d);
+  HIP_TRY(hipMalloc(&d, kMaxSets * 8 * 8));
+  em->allocs.push_back(d);
+  if (kwk_status st = fill(em, d, 0, kMaxSets * 8 * 8)) return st;
+  em->d_fin_totals_all = static_cast<unsigned long long*>(d);
+  for (size_t i = 0; i < em->sets.size(); ++i) em->sets[i].d_fin_totals = em->d_fin_totals_all + 8u * i;
+  em->f = f;
+  em->fin = true;
+  for (uint32_t s = 0; s < g->n_stages; ++s) em->fin_any = em->fin_any || (g->stage_flags[s] & KWK_NEXT_FIN);
+  return KWK_OK;
+}
+
+kwk_status kwk_emit_set_fin_words(kwk_emitter* em, uint32_t first, uint32_t n, const uint32_t* words) {
+  ErrScope es_(em ? &em->err : nullptr);
+  if (!em || (n && !words)) return fail(KWK_EINVAL, "null argument");
+  if (!em->fin) return fail(KWK_ESTATE, "kwk_emit_finalizers_load must come first");
+  if ((uint64_t)first + n > em->capacity) return fail(KWK_EINVAL, "rows beyond the capacity");
+  if (kwk_status st = bind(em)) return st;
+  return copy_in(em, em->f.words + first, words, (size_t)n * 4);
+}
+
+kwk_status kwk_emit_get_fin_words(kwk_emitter* em, uint32_t first, uint32_t n, uint32_t* words) {
+  ErrScope es_(em ? &em->err : nullptr);
+  if (!em || (n && !words)) return fail(KWK_EINVAL, "null argument");
+  if (!em->fin) return fail(KWK_ESTATE, "kwk_emit_finalizers_load must come first");
+  if ((uint64_t)first + n > em->capacity) return fail(KWK_EINVAL, "rows beyond the capacity");
+  if (kwk_status st = bind(em)) return st;
+  return copy_out(em, words, em->f.words + first, (size_t)n * 4);
+}
+
+kwk_status kwk_emit_reserve_fin(kwk_emitter* em, uint32_t max_items, uint64_t max_bytes) {
+  ErrScope es_(em ? &em->err : nullptr);
+  if (!em) return fail(KWK_EINVAL, "null emitter");
+  if (!em->fin) return fail(KWK_ESTATE, "kwk_emit_finalizers_load must come first");
+  em->fin_req_items = max_items;  // (a set keeps the room it has; sets made later get this)
+  em->fin_req_bytes = max_bytes;
+  return reserve_sets(em, (uint32_t)em->sets.size(), 0, 0);
+}
+
+kwk_status kwk_emit_fin_result(kwk_emitter* em, uint32_t* n_items, uint64_t* n_bytes) {
+  ErrScope es_(em ? &em->err : nullptr);
+  if (!em || !n_items || !n_bytes) return fail(KWK_EINVAL, "null argument");
+  if (!em->fin) return fail(KWK_ESTATE, "kwk_emit_finalizers_load must come first");
+  uint32_t mi = 0;
+  uint64_t mb = 0;
+  const kwk_status st = kwk_emit_result(em, &mi, &mb);
+  if (st != KWK_OK && st != KWK_ECAP) return st;
+  unsigned long long ft[2] = {0, 0};
+  const std::string msg = em->err;
+  if (em->selected().d_fin_totals)
+    if (kwk_status s2 = copy_out(em, ft, em->selected().d_fin_totals, sizeof ft)) return s2;
+  *n_items = (uint32_t)ft[0];
+  *n_bytes = ft[1];
+  return st == KWK_OK ? KWK_OK : fail(st, msg);
+}
+
+kwk_status kwk_emit_fin_device(kwk_emitter* em, const kwk_emit_fin_item** items, const uint64_t** offsets,
+                               const char** bytes) {
+  ErrScope es_(em ? &em->err : nullptr);
+  if (!em) return fail(KWK_EINVAL, "null emitter");
+  if (!em->fin) return fail(KWK_ESTATE, "kwk_emit_finalizers_load must come first");
+  const kwk_emitter::OutSet& o = em->selected();
+  if (items) *items = o.d_fin_items;
+  if (offsets) *offsets = o.d_fin_offsets;
+  if (bytes) *bytes = o.d_fin_out;
+  return KWK_OK;
+}
+
+kwk_status kwk_emit_fin_copy(kwk_emitter* em, kwk_emit_fin_item* items, uint64_t* offsets, char* bytes) {
+  ErrScope es_(em ? &em->err : nullptr);
+  uint32_t ni = 0;
+  uint64_t nb = 0;
+  if (kwk_status st = kwk_emit_fin_result(em, &ni, &nb)) return st;
+  if ((ni && !items) || (nb && !bytes) || !offsets) return fail(KWK_EINVAL, "null argument");
+  const kwk_emitter::OutSet& o = em->selected();
+  if (ni) {
+    if (kwk_status st = copy_out(em, items, o.d_fin_items, (size_t)ni * sizeof(kwk_emit_fin_item))) return st;
+    if (kwk_status st = copy_out(em, offsets, o.d_fin_offsets, ((size_t)ni + 1) * 8)) return st;
+  } else {
+    offsets[0] = 0;
+  }
+  if (kwk_status st = copy_out(em, bytes, o.d_fin_out, (size_t)nb)) return st;
   return KWK_OK;
 }
 

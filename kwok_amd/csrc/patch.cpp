@@ -244,6 +244,16 @@ struct kwk_patcher {
   std::vector<JV> consts;
   std::string out;  // the last render's patches
   std::string skel;  // the last kwk_patch_skeleton result
+  // the finalizer program (the spec's optional "finalizers"): dictionary values in id order, and
+  // per stage the KWK_NEXT_* flags, the add ids in YAML order and the remove id set
+  struct FinStage {
+    uint32_t flags = 0;
+    std::vector<uint8_t> add;
+    uint32_t remove = 0;
+  };
+  bool has_fin = false;
+  std::vector<std::string> fin_values;
+  std::vector<FinStage> fin_stages;
 };
 
 namespace {
@@ -1052,6 +1062,26 @@ kwk_status kwk_patcher_create(const char* spec_json, kwk_patcher** out) {
       t.body = load_node(member(tj, "body"));
       p->templates.push_back(std::move(t));
     }
+    if (const JV* fj = spec.get("finalizers"); fj && fj->t == JV::OBJ) {
+      for (const JV& v : member(*fj, "values").a) p->fin_values.push_back(str(v));
+      if (p->fin_values.size() > KWK_FIN_MAX_VALUES) throw BadSpec{"finalizers: more than 15 dictionary values"};
+      for (const JV& sj : member(*fj, "stages").a) {
+        kwk_patcher::FinStage fs;
+        fs.flags = (uint32_t)num(member(sj, "flags"));
+        for (const JV& a : member(sj, "add").a) {
+          const int id = num(a);
+          if (id < 0 || (size_t)id >= p->fin_values.size()) throw BadSpec{"finalizers: add id out of range"};
+          fs.add.push_back((uint8_t)id);
+        }
+        for (const JV& r : member(sj, "remove").a) {
+          const int id = num(r);
+          if (id < 0 || (size_t)id >= p->fin_values.size()) throw BadSpec{"finalizers: remove id out of range"};
+          fs.remove |= 1u << id;
+        }
+        p->fin_stages.push_back(std::move(fs));
+      }
+      p->has_fin = true;
+    }
   } catch (const BadSpec& b) {
     return fail(KWK_EINVAL, "patch spec: " + b.what);
   }
@@ -1334,6 +1364,116 @@ kwk_status kwk_patch_object_values(kwk_patcher* p, uint32_t tid, uint32_t n, con
     for (uint32_t t = 0; t < nt; ++t) th.emplace_back(work, t);
     for (auto& x : th) x.join();
   }
+  return KWK_OK;
+}
+
+// ---- finalizer JSON patches (Next.Finalizers, next.go:43-60; finalizersModify, finalizers.go:83-111)
+
+namespace {
+
+// the NUL-separated values of a metadata.finalizers list -> dictionary ids (KWK_FIN_OTHER: not in it)
+kwk_status fin_ids(const kwk_patcher* p, uint32_t n, const char* fins, uint64_t fins_len, std::vector<uint8_t>& ids) {
+  if (!p->has_fin) return fail(KWK_ESTATE, "the patch spec has no finalizer program");
+  if (n && !fins) return fail(KWK_EINVAL, "null argument");
+  uint64_t pos = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    if (pos > fins_len) return fail(KWK_EINVAL, "finalizers: fewer than n values");
+    const char* b = fins + pos;
+    const char* e = static_cast<const char*>(memchr(b, 0, fins_len - pos));
+    const uint64_t len = e ? (uint64_t)(e - b) : fins_len - pos;
+    if (!e && i + 1 < n) return fail(KWK_EINVAL, "finalizers: fewer than n values");
+    uint8_t id = KWK_FIN_OTHER;
+    for (size_t k = 0; k < p->fin_values.size(); ++k)
+      if (p->fin_values[k].size() == len && memcmp(p->fin_values[k].data(), b, len) == 0) id = (uint8_t)k;
+    ids.push_back(id);
+    pos += len + 1;
+  }
+  return KWK_OK;
+}
+
+}  // namespace
+
+kwk_status kwk_patch_finalizers(kwk_patcher* p, uint32_t stage, uint32_t n, const char* fins, uint64_t fins_len, char* out,
+                                uint64_t cap, uint64_t* len) {
+  ErrScope es_(p ? &p->err : nullptr);
+  if (!p || !len || (cap && !out)) return fail(KWK_EINVAL, "null argument");
+  std::vector<uint8_t> meta;
+  if (kwk_status st = fin_ids(p, n, fins, fins_len, meta)) return st;
+  if (stage >= p->fin_stages.size()) return fail(KWK_EINVAL, "stage out of range");
+  const kwk_patcher::FinStage& S = p->fin_stages[stage];
+  std::vector<std::string> ops;
+  if (S.flags & KWK_NEXT_FIN) {
+    bool empty = (S.flags & KWK_NEXT_FIN_EMPTY) != 0;
+    if (!empty && S.remove) {
+      std::vector<std::string> removed;  // from the highest index down (finalizers.go:69-77)
+      for (size_t i = meta.size(); i-- > 0;)
+        if (meta[i] != KWK_FIN_OTHER && ((S.remove >> meta[i]) & 1u))
+          removed.push_back("{\"op\":\"remove\",\"path\":\"/metadata/finalizers/" + std::to_string(i) + "\"}");
+      if (removed.size() == meta.size()) empty = true;
+      else ops = std::move(removed);
+    }
+    const bool whole = empty || meta.empty();  // finalizersAdd over no list: one add of the whole list
+    if (empty && !meta.empty()) ops.push_back("{\"op\":\"remove\",\"path\":\"/metadata/finalizers\"}");
+    if (!S.add.empty()) {
+      if (whole) {
+        std::string o = "{\"op\":\"add\",\"path\":\"/metadata/finalizers\",\"value\":[";
+        for (size_t j = 0; j < S.add.size(); ++j) o += (j ? ",\"" : "\"") + p->fin_values[S.add[j]] + "\"";
+        ops.push_back(o + "]}");
+      } else {
+        for (uint8_t id : S.add) {  // membership in the original list
+          bool present = false;
+          for (uint8_t m : meta) present |= m == id;
+          if (!present) ops.push_back("{\"op\":\"add\",\"path\":\"/metadata/finalizers/-\",\"value\":\"" + p->fin_values[id] + "\"}");
+        }
+      }
+    }
+  }
+  std::string o;
+  if (!ops.empty()) {
+    o = "[";
+    for (size_t i = 0; i < ops.size(); ++i) o += (i ? "," : "") + ops[i];
+    o += "]";
+  }
+  *len = o.size();
+  if (o.size() > cap) return fail(KWK_ECAP, "kwk_patch_finalizers: " + std::to_string(o.size()) + " bytes needed");
+  if (!o.empty()) memcpy(out, o.data(), o.size());
+  return KWK_OK;
+}
+
+kwk_status kwk_patch_finalizer_word(kwk_patcher* p, uint32_t n, const char* fins, uint64_t fins_len, uint32_t* word) {
+  ErrScope es_(p ? &p->err : nullptr);
+  if (!p || !word) return fail(KWK_EINVAL, "null argument");
+  std::vector<uint8_t> meta;
+  if (kwk_status st = fin_ids(p, n, fins, fins_len, meta)) return st;
+  if (meta.size() > KWK_FIN_MAX_LEN) {
+    *word = KWK_FIN_WORD_HOST;
+    return KWK_OK;
+  }
+  uint32_t w = (uint32_t)meta.size() << 28;
+  for (size_t k = 0; k < meta.size(); ++k) w |= (uint32_t)meta[k] << (4u * k);
+  *word = w;
+  return KWK_OK;
+}
+
+kwk_status kwk_patch_finalizer_list(kwk_patcher* p, uint32_t word, uint32_t* n, char* out, uint64_t cap, uint64_t* len) {
+  ErrScope es_(p ? &p->err : nullptr);
+  if (!p || !n || !len || (cap && !out)) return fail(KWK_EINVAL, "null argument");
+  if (!p->has_fin) return fail(KWK_ESTATE, "the patch spec has no finalizer program");
+  const uint32_t cnt = word >> 28;
+  if (cnt > KWK_FIN_MAX_LEN) return fail(KWK_EINVAL, "finalizer word: the list is not representable (more than 7 entries)");
+  std::string o;
+  for (uint32_t k = 0; k < cnt; ++k) {
+    const uint32_t id = (word >> (4u * k)) & 15u;
+    if (id >= p->fin_values.size())
+      return fail(KWK_EINVAL, id == KWK_FIN_OTHER ? "finalizer word: entry " + std::to_string(k) + " is a value outside the dictionary"
+                                                  : "finalizer word: id " + std::to_string(id) + " out of range");
+    o += p->fin_values[id];
+    o.push_back('\0');
+  }
+  *n = cnt;
+  *len = o.size();
+  if (o.size() > cap) return fail(KWK_ECAP, "kwk_patch_finalizer_list: " + std::to_string(o.size()) + " bytes needed");
+  if (!o.empty()) memcpy(out, o.data(), o.size());
   return KWK_OK;
 }
 

@@ -643,6 +643,29 @@ class KindProgram:
     def uses_deletion_column(self) -> bool:
         return any(d.delay_slot == abi.SLOT_DELETION or d.jitter_slot == abi.SLOT_DELETION for d in self.stage_desc)
 
+    def finalizer_spec(self) -> str:
+        """The finalizer program of the patch / emit spec (kwok_patch.h "finalizers"): the dictionary
+        values in id order and, per stage, the flags, the add ids in the Stage's order (duplicates
+        kept) and the remove id set.  Refused by name (the host renders these): more than 15
+        dictionary values, a value with a byte outside [A-Za-z0-9._/-]."""
+        values = list(self.fin_bits)
+        if len(values) > 15:
+            raise CompileError(f"finalizer program not supported natively: {len(values)} dictionary values (more than "
+                               "15); the host renders the finalizer patches")
+        for v in values:
+            if not re.fullmatch(r"[A-Za-z0-9._/-]*", v):
+                raise CompileError(f"finalizer program not supported natively: value {json.dumps(v)} has a byte outside "
+                                   "[A-Za-z0-9._/-] (Go's json.Marshal escaping of it is not pinned by a reference "
+                                   "vector); the host renders the finalizer patches")
+        ids = {v: i for i, v in enumerate(values)}
+        keep = abi.NEXT_DELETE | abi.NEXT_FIN | abi.NEXT_FIN_EMPTY | abi.NEXT_FIN_REMOVE
+        stages = []
+        for st, d in zip(self.stages, self.stage_desc):
+            f = st.next.finalizers
+            stages.append({"flags": d.flags & keep, "add": [ids[v] for v in f.add] if f is not None else [],
+                           "remove": sorted({ids[v] for v in f.remove}) if f is not None else []})
+        return json.dumps({"values": values, "stages": stages})
+
     def describe(self) -> dict:
         feats = []
         for f in self.features.values():

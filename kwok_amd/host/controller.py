@@ -46,12 +46,20 @@ class KindController:
         self.host_renders = 0     # patches the native renderer handed back (NEEDS_RENDER / unsupported)
         self.last_rows = {}       # slot -> kwk_encode row of every object the last step fired (native)
         self.last_patches = {}    # (slot, patch index) -> the patch bytes the last step applied (native)
+        self.last_fin_patches = {}  # slot -> the finalizer JSON patch bytes the last step sent first (native)
+        self.fin_refused = None   # why kwk_patch_finalizers is not used (the host mirror renders the ops)
         if native:
             from .encoder import NativeIngest
             from .patchtpl import PatchProgram
             self.nenc = NativeIngest(program, n_threads=n_threads)
             native_prog = program if hasattr(program, "patch_spec") else None  # libkwok_compiler's spec
-            self.patcher = PatchProgram(program.stages, self.funcs, n_threads=n_threads, program=native_prog)
+            fin = None
+            try:
+                fin = program.finalizer_spec() if hasattr(program, "finalizer_spec") else None
+            except ValueError as e:  # a shape the native program refuses by name: the Python mirror renders
+                self.fin_refused = str(e)
+            self.patcher = PatchProgram(program.stages, self.funcs, n_threads=n_threads, program=native_prog,
+                                        finalizers=fin)
 
     def close(self):
         if self.native:
@@ -67,14 +75,22 @@ class KindController:
         from .nextstate import finalizers_modify, json_patch, merge_patch
         from .patchtpl import render_patch_bytes
         items, jobs = [], []  # jobs: (item index, patch index, template id | None)
+        self.last_fin_patches = {}
         for rec in fired:
             i, s = int(rec["slot"]), int(rec["stage"])
             st = self.p.stages[s]
             obj = copy.deepcopy(self.objs[i])
             changed = False
             if st.next.finalizers is not None:
-                ops = finalizers_modify((obj.get("metadata") or {}).get("finalizers"), st.next.finalizers)
+                meta = (obj.get("metadata") or {}).get("finalizers")
+                if self.patcher.has_finalizers:  # kwk_patch_finalizers: the bytes playStage sends first
+                    b = self.patcher.finalizers(s, meta)
+                    ops = json.loads(b) if b else []
+                else:
+                    ops = finalizers_modify(meta, st.next.finalizers)
+                    b = json.dumps(ops, separators=(",", ":")).encode() if ops else b""
                 if ops:
+                    self.last_fin_patches[i] = b
                     new = prune_empty(json_patch(obj, ops))
                     changed = json.dumps(new, sort_keys=True) != json.dumps(obj, sort_keys=True)
                     obj = new

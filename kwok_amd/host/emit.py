@@ -58,6 +58,66 @@ class EmitItem(C.Structure):
 ITEM_DTYPE = np.dtype([("rec", "<u4"), ("tid", "<u2"), ("status", "u1"), ("reserved", "u1")])
 
 
+class EmitFinProgramStruct(C.Structure):
+    """kwk_emit_fin_program."""
+    _fields_ = [("n_values", C.c_uint32), ("n_stages", C.c_uint32), ("value_off", C.c_void_p), ("values", C.c_void_p),
+                ("stage_flags", C.c_void_p), ("stage_remove", C.c_void_p), ("stage_add_ptr", C.c_void_p),
+                ("stage_add", C.c_void_p)]
+
+
+class EmitFinItem(C.Structure):
+    _fields_ = [("rec", C.c_uint32), ("status", C.c_uint8), ("n_ops", C.c_uint8), ("reserved", C.c_uint16)]
+
+
+FIN_ITEM_DTYPE = np.dtype([("rec", "<u4"), ("status", "u1"), ("n_ops", "u1"), ("reserved", "<u2")])
+FIN_WORD_HOST = 0xF0000000
+FIN_OTHER = 15
+
+
+def fin_word_ids(word: int) -> Optional[List[int]]:
+    """The dictionary ids of an order word in list order (None: not representable)."""
+    n = word >> 28
+    return None if n > 7 else [(word >> (4 * k)) & 15 for k in range(n)]
+
+
+class FinProgram:
+    """kwk_emit_fin_program from a finalizer spec (KindProgram.finalizer_spec() /
+    kwk_program_finalizer_spec: values in id order; per stage flags, add ids in order, remove ids)."""
+
+    def __init__(self, spec):
+        d = json.loads(spec) if isinstance(spec, (str, bytes)) else spec
+        self.values: List[str] = list(d["values"])
+        self.stages = list(d["stages"])
+        vb = [v.encode() for v in self.values]
+        ptr = [0]
+        flat: List[int] = []
+        for st in self.stages:
+            flat += [int(i) for i in st["add"]]
+            ptr.append(len(flat))
+        self._a = {
+            "value_off": np.asarray(np.cumsum([0] + [len(b) for b in vb]), dtype=np.uint32),
+            "values": b"".join(vb) or b"\0",
+            "flags": np.asarray([st["flags"] for st in self.stages] or [0], dtype=np.uint8),
+            "remove": np.asarray([sum(1 << int(i) for i in st["remove"]) for st in self.stages] or [0], dtype=np.uint16),
+            "add_ptr": np.asarray(ptr, dtype=np.uint32),
+            "add": np.asarray(flat or [0], dtype=np.uint8),
+        }
+        a = self._a
+        self.struct = EmitFinProgramStruct(len(self.values), len(self.stages), abi.ptr(a["value_off"]),
+                                           C.cast(C.c_char_p(a["values"]), C.c_void_p), abi.ptr(a["flags"]),
+                                           abi.ptr(a["remove"]), abi.ptr(a["add_ptr"]), abi.ptr(a["add"]))
+
+    def word(self, fins: Optional[Sequence[str]]) -> int:
+        """The order word of a metadata.finalizers list (kwk_patch_finalizer_word's value)."""
+        fins = list(fins or [])
+        if len(fins) > 7:
+            return FIN_WORD_HOST
+        w = len(fins) << 28
+        for k, v in enumerate(fins):
+            w |= (self.values.index(v) if v in self.values else FIN_OTHER) << (4 * k)
+        return w
+
+
 def _get(obj, path):
     v = obj
     for k in path:
@@ -290,6 +350,13 @@ def lib():
         L.kwk_emit_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.kwk_emit_copy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.kwk_emit_elapsed.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        L.kwk_emit_finalizers_load.argtypes = [C.c_void_p, C.POINTER(EmitFinProgramStruct)]
+        L.kwk_emit_set_fin_words.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+        L.kwk_emit_get_fin_words.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+        L.kwk_emit_reserve_fin.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64]
+        L.kwk_emit_fin_result.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+        L.kwk_emit_fin_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.kwk_emit_fin_copy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         for n in EXPORTS:
             if n != "kwk_emit_last_error":
                 getattr(L, n).restype = C.c_int32
@@ -300,7 +367,9 @@ def lib():
 EXPORTS = ("kwk_emit_last_error", "kwk_emitter_create", "kwk_emitter_destroy", "kwk_emit_set_words",
            "kwk_emit_get_words", "kwk_emit_set_column", "kwk_emit_reserve", "kwk_emit", "kwk_emit_result",
            "kwk_emit_stats", "kwk_emit_device", "kwk_emit_copy", "kwk_emit_elapsed", "kwk_emit_step",
-           "kwk_emit_reserve_sets", "kwk_emit_select")
+           "kwk_emit_reserve_sets", "kwk_emit_select", "kwk_emit_finalizers_load", "kwk_emit_set_fin_words",
+           "kwk_emit_get_fin_words", "kwk_emit_reserve_fin", "kwk_emit_fin_result", "kwk_emit_fin_device",
+           "kwk_emit_fin_copy")
 
 
 class Emitter:
@@ -433,6 +502,44 @@ class Emitter:
         out = np.zeros(max(nb, 1), dtype=np.uint8)
         self._check(lib().kwk_emit_copy(self.h, abi.ptr(items) if ni else None, abi.ptr(offs), abi.ptr(out)),
                     "kwk_emit_copy")
+        return items, offs, out[:nb].tobytes()
+
+    # -- finalizer patches (kwok_emit.h "Finalizer patches")
+    def load_finalizers(self, fin: FinProgram):
+        """kwk_emit_finalizers_load: every later emission also emits its list's finalizer patches."""
+        self.fin_program = fin
+        self._check(lib().kwk_emit_finalizers_load(self.h, C.byref(fin.struct)), "kwk_emit_finalizers_load")
+
+    def set_fin_words(self, first: int, words: np.ndarray):
+        w = np.ascontiguousarray(words, dtype=np.uint32)
+        self._check(lib().kwk_emit_set_fin_words(self.h, int(first), len(w), abi.ptr(w)), "kwk_emit_set_fin_words")
+
+    def fin_words(self, first: int, n: int) -> np.ndarray:
+        w = np.zeros(n, dtype=np.uint32)
+        self._check(lib().kwk_emit_get_fin_words(self.h, int(first), n, abi.ptr(w)), "kwk_emit_get_fin_words")
+        return w
+
+    def reserve_fin(self, items: int, nbytes: int):
+        self._check(lib().kwk_emit_reserve_fin(self.h, int(items), int(nbytes)), "kwk_emit_reserve_fin")
+
+    def fin_result(self) -> Tuple[int, int, int]:
+        """(status, items, bytes) of the selected emission's finalizer stream; status abi.KWK_ECAP
+        exactly when the emission's readers return it."""
+        ni, nb = C.c_uint32(), C.c_uint64()
+        st = lib().kwk_emit_fin_result(self.h, C.byref(ni), C.byref(nb))
+        if st != abi.KWK_ECAP:
+            self._check(st, "kwk_emit_fin_result")
+        return int(st), int(ni.value), int(nb.value)
+
+    def collect_fin(self):
+        """The selected emission's finalizer stream -> (items structured array, offsets, bytes)."""
+        st, ni, nb = self.fin_result()
+        self._check(st, "kwk_emit_fin_result")
+        items = np.zeros(ni, dtype=FIN_ITEM_DTYPE)
+        offs = np.zeros(ni + 1, dtype=np.uint64)
+        out = np.zeros(max(nb, 1), dtype=np.uint8)
+        self._check(lib().kwk_emit_fin_copy(self.h, abi.ptr(items) if ni else None, abi.ptr(offs), abi.ptr(out)),
+                    "kwk_emit_fin_copy")
         return items, offs, out[:nb].tobytes()
 
     def elapsed_ms(self) -> float:

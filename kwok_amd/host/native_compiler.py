@@ -41,8 +41,10 @@ def lib():
         L.kwk_program_deltas.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.kwk_program_harness.argtypes = [C.c_void_p, C.c_void_p]
         L.kwk_program_value_slots.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
-        for n in ("kwk_program_describe", "kwk_program_class_keys", "kwk_program_encoder_spec"):
+        for n in ("kwk_program_describe", "kwk_program_class_keys", "kwk_program_encoder_spec",
+                  "kwk_program_finalizer_spec"):
             getattr(L, n).argtypes = [C.c_void_p, C.POINTER(C.c_char_p)]
+        L.kwk_program_finalizer_spec.restype = C.c_int32
         L.kwk_program_patch_spec.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), C.c_void_p,
                                              C.c_uint32]
         for n in ("kwk_compile_stages", "kwk_program_destroy", "kwk_program_explore", "kwk_program_class",
@@ -167,6 +169,10 @@ class NativeProgram:
 
     def encoder_spec(self) -> str:
         return self._json(lib().kwk_program_encoder_spec)
+
+    def finalizer_spec(self) -> str:
+        """kwk_program_finalizer_spec: KindProgram.finalizer_spec's JSON (CompileError names a refusal)."""
+        return self._json(lib().kwk_program_finalizer_spec)
 
     def patch_spec(self, funcs: Optional[Dict[str, object]] = None, version: str = "v0.6.0"):
         """-> (spec JSON for kwk_patcher_create, {(stage, patch): template id}) — PatchProgram's

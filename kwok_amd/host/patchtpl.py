@@ -538,8 +538,14 @@ def lib():
         L.kwk_patch_object_values.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_void_p, C.c_char_p,
                                               C.c_uint64, _FN, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
                                               C.c_void_p]
+        L.kwk_patch_finalizers.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_uint64, C.c_void_p,
+                                           C.c_uint64, C.POINTER(C.c_uint64)]
+        L.kwk_patch_finalizer_word.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint32)]
+        L.kwk_patch_finalizer_list.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p, C.c_uint64,
+                                               C.POINTER(C.c_uint64)]
         for n in ("kwk_patcher_create", "kwk_patcher_destroy", "kwk_patch_render", "kwk_patch_skeleton",
-                  "kwk_patch_object_values"):
+                  "kwk_patch_object_values", "kwk_patch_finalizers", "kwk_patch_finalizer_word",
+                  "kwk_patch_finalizer_list"):
             getattr(L, n).restype = C.c_int32
         _lib = L
     return _lib
@@ -571,9 +577,12 @@ class PatchProgram:
     """
 
     def __init__(self, stages, funcs: Optional[Dict[str, object]] = None, version: str = "v0.6.0",
-                 n_threads: int = 1, program=None):
+                 n_threads: int = 1, program=None, finalizers: Optional[str] = None):
         """program: a native_compiler.NativeProgram — the spec and template ids come from
-        libkwok_compiler (kwk_program_patch_spec) instead of this module's compiler."""
+        libkwok_compiler (kwk_program_patch_spec) instead of this module's compiler.
+        finalizers: the finalizer program (KindProgram.finalizer_spec() / kwk_program_finalizer_spec),
+        the spec's "finalizers": kwk_patch_finalizers and the order-word helpers need it."""
+        self.has_finalizers = finalizers is not None
         funcs = dict(funcs or {})
         self.n_threads = n_threads
         self.callbacks: Dict[int, Callable] = {}
@@ -597,6 +606,8 @@ class PatchProgram:
                 for pi in range(len(st.next.patches)):
                     if (si, pi) not in self.template_of:
                         self.unsupported[(si, pi)] = "not compiled by libkwok_compiler"
+            if finalizers is not None:
+                self.spec = json.dumps(dict(json.loads(self.spec), finalizers=json.loads(finalizers)))
             self.h = C.c_void_p()
             _check(lib().kwk_patcher_create(self.spec.encode(), C.byref(self.h)), "kwk_patcher_create")
             self._fn = _FN(self._callback)
@@ -613,7 +624,10 @@ class PatchProgram:
                     continue
                 self.template_of[(si, pi)] = len(self.templates)
                 self.templates.append(t)
-        self.spec = json.dumps({"templates": self.templates, "funcs": fspec, "consts": consts})
+        spec = {"templates": self.templates, "funcs": fspec, "consts": consts}
+        if finalizers is not None:
+            spec["finalizers"] = json.loads(finalizers)
+        self.spec = json.dumps(spec)
         self.h = C.c_void_p()
         _check(lib().kwk_patcher_create(self.spec.encode(), C.byref(self.h)), "kwk_patcher_create")
         self._fn = _FN(self._callback)
@@ -661,6 +675,37 @@ class PatchProgram:
         buf, offs = pack_json(objs)
         out, o, st = self.render_buffer(np.asarray(template_ids), buf, offs, now_ns)
         return [out[int(o[i]):int(o[i + 1])] if st[i] == STATUS_OK else None for i in range(len(objs))]
+
+    @staticmethod
+    def _fins(fins) -> bytes:
+        return b"\0".join(f.encode() for f in (fins or []))
+
+    def finalizers(self, stage: int, fins: Optional[Sequence[str]]) -> bytes:
+        """kwk_patch_finalizers: Next.Finalizers' JSON patch bytes of `stage` for an object whose
+        metadata.finalizers is `fins` (b"" = no ops: the reference sends nothing)."""
+        b, n = self._fins(fins), C.c_uint64()
+        out = C.create_string_buffer(256)
+        st = lib().kwk_patch_finalizers(self.h, int(stage), len(fins or []), b, len(b), out, len(out), C.byref(n))
+        if st == abi.KWK_ECAP:
+            out = C.create_string_buffer(n.value)
+            st = lib().kwk_patch_finalizers(self.h, int(stage), len(fins or []), b, len(b), out, len(out), C.byref(n))
+        _check(st, "kwk_patch_finalizers", self.h)
+        return out.raw[:n.value]
+
+    def finalizer_word(self, fins: Optional[Sequence[str]]) -> int:
+        """kwk_patch_finalizer_word: the order word of a metadata.finalizers list (kwok_patch.h)."""
+        b, w = self._fins(fins), C.c_uint32()
+        _check(lib().kwk_patch_finalizer_word(self.h, len(fins or []), b, len(b), C.byref(w)), "kwk_patch_finalizer_word",
+               self.h)
+        return int(w.value)
+
+    def finalizer_list(self, word: int) -> List[str]:
+        """kwk_patch_finalizer_list: the list of an order word of known ids."""
+        n, ln = C.c_uint32(), C.c_uint64()
+        out = C.create_string_buffer(2048)
+        _check(lib().kwk_patch_finalizer_list(self.h, int(word), C.byref(n), out, len(out), C.byref(ln)),
+               "kwk_patch_finalizer_list", self.h)
+        return [x.decode() for x in out.raw[:ln.value].split(b"\0")[:n.value]]
 
     def skeleton(self, tid: int, obj) -> dict:
         """kwk_patch_skeleton: the template's skeleton over obj's class (see kwok_patch.h)."""
