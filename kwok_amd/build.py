@@ -11,7 +11,7 @@ import sys
 PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 SRC = [os.path.join(PKG, "csrc", "engine.hip")]
-HDR = [os.path.join(ROOT, "include", "kwok_engine.h")]
+HDR = [os.path.join(ROOT, "include", "kwok_engine.h"), os.path.join(PKG, "csrc", "id8_compose.hpp")]
 OUT = os.path.join(PKG, "lib", "libkwok_engine.so")
 DOM_HDR = os.path.join(PKG, "csrc", "json_dom.hpp")
 ENC_SRC = [os.path.join(PKG, "csrc", "encoder.cpp")]

@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "../../include/kwok_engine.h"
+#include "id8_compose.hpp"
 
 static void engine_set_error(kwk_engine* e, const std::string& msg);
 
@@ -310,6 +311,7 @@ struct SweepArgs {
   const uint32_t* __restrict__ fsm;  // 2-byte sweep: per-(due ready, word) transition entries (or null)
   const int64_t* __restrict__ fsm_due;
   uint32_t fsm_bits;
+  const uint4* __restrict__ comp;    // fused 1-byte sweep: the launch's composite id table (id8_compose.hpp)
   int64_t dw_epoch_old;          // fused format: the epoch the records hold (fmt.epoch: the one written)
   uint32_t dw_rebase;            // fused format: the epoch moves this sweep (every pending record re-encoded)
   // sweep8_kernel<..., kSteps>: steps 1 .. kSteps - 1 of the launch (their times, segments and counts)
@@ -1416,15 +1418,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(Q >= 4 ?
 // so the idle test is two mask-and-shift ops per 4 objects, and the transition of a work item
 // is one lookup in a 512-entry id table staged in LDS (no L2 gather).  The column halves: the
 // C5 state stream is 100 MB instead of 200 MB, read once and rewritten as whole 128-byte lines.
-constexpr uint32_t kIdNeed = 0x80u, kIdPend = 0x40u, kIdAlive = 0x20u, kIdIndex = 0x1Fu;
-constexpr uint32_t kIdInvalid = 0xFFu;  // not in the dictionary (never stored: the host closes it)
+// (kId*: the id's bits, kId8*: the id transition entry, kId8c*: the composite row — id8_compose.hpp)
 constexpr int kQ8 = 2;                  // 16-byte chunks per lane: 32 ids per lane, 2048 per wave
-// id transition entry (dict_upload): [7:0] new id, [15:11] the 2-byte fired record's high bits
-// (stage 11-12 when the program has <= 4 stages, flags 13-15), [20:16] fired stage, [23:21]
-// fired flags, [28:24] algorithmic bytes of the item beyond its 1-byte read, [29] writes due =
-// now + fsm_due[entry], [30] matched, [31] fired.  Lookups the sweep never makes (and unused ids,
-// kIdInvalid among them) hold the id itself: no change, nothing fires.
-constexpr uint32_t kId8Rec16 = 0xF800u, kId8Due = 1u << 29, kId8Match = 1u << 30, kId8Fire = 1u << 31;
 // SweepArgs::fsm_bits of the 1-byte sweep: the table holds a kId8Due entry
 constexpr uint32_t kId8AnyDue = 1u;
 // fired records of the 1-byte sweep: 2 bytes {LDS offset: 11, stage: 2, flags: 3} after a 16-byte
@@ -1584,6 +1579,49 @@ __device__ __forceinline__ void id8_carryn(const uint32_t (&we)[kN], const uint3
   for (uint32_t j = 0; j < kN; ++j) *(lds_u8*)(size_t)we[j] = (uint8_t)fin[j];
 }
 
+// id8_carryn on the launch's composite id table (id8_compose.hpp, staged in LDS as s_comp): an item's
+// whole trajectory over the kSteps steps is a function of its first id, so the id byte and its 16-byte
+// row are read once, the last id is written once, and the pre-summed statistics are added once per
+// pass — stat: entries matched and bytes in the row's fields (the caller unpacks them once per tile),
+// n_lline: less the steps >= 1 on the list, stc[0]: the per-stage byte counters.  What is left per
+// step is the fired ballot and the 2-byte record into region s of the work list
+template <int kSteps, uint32_t kN>
+__device__ __forceinline__ void id8_carryc(const uint32_t (&we)[kN], const uint4* __restrict__ s_comp,
+                                           uint16_t* __restrict__ wl, uint32_t (&segs)[kSteps], uint32_t& stat,
+                                           uint32_t& n_lline, uint32_t (&stc)[4]) {
+  constexpr uint32_t kRegion = 2048u / (uint32_t)kSteps;
+  static_assert(kSteps <= kId8cMaxSteps && 2048u / (uint32_t)kSteps / 64u <= 16u, "row words, statistics fields");
+  uint32_t key[kN];
+  uint4 r[kN];
+#pragma unroll
+  for (uint32_t j = 0; j < kN; ++j) key[j] = (uint32_t)*(lds_u8*)(size_t)we[j];
+#pragma unroll
+  for (uint32_t j = 0; j < kN; ++j) r[j] = s_comp[key[j]];
+#pragma unroll
+  for (uint32_t j = 0; j < kN; ++j) *(lds_u8*)(size_t)we[j] = (uint8_t)r[j].x;
+#pragma unroll
+  for (uint32_t j = 0; j < kN; ++j) {
+    stat += r[j].y & kId8cStat;
+    n_lline -= r[j].z & kId8cLive;
+    stc[0] += r[j].w & kId8cStages;
+  }
+#pragma unroll
+  for (int s = 0; s < kSteps; ++s) {
+#pragma unroll
+    for (uint32_t j = 0; j < kN; ++j) {
+      const uint32_t w = s == 0 ? r[j].x : s == 1 ? r[j].y : s == 2 ? r[j].z : r[j].w;
+      const bool fire = (int32_t)w < 0;
+      const unsigned long long bal = ballot(fire);
+      if (bal) {  // wave-uniform
+        const uint32_t pos =
+            __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, segs[s]));
+        if (fire) wl[(uint32_t)s * kRegion + pos] = (uint16_t)((we[j] & 0x7FFu) | (w & kId8Rec16));
+        segs[s] += (uint32_t)__popcll(bal);
+      }
+    }
+  }
+}
+
 // the fired ballot of one pass: records staged at the list's consumed front (<= 4 stages) or
 // stored to the segment, per-stage counts
 template <bool kStages4>
@@ -1619,7 +1657,9 @@ __device__ __forceinline__ void id8_fire(const uint32_t addr, const uint32_t e, 
 // wave whose tile holds no queued id and at most 2048 / kSteps items builds its work list once and
 // carries it, two passes at a time, through all kSteps steps in registers (id8_carryn: kIdNeed is a
 // function of the id, so step s + 1's items are step s's whose new id still has it); any other tile
-// rebuilds its list at every step.  Both paths share one block of stores per step
+// rebuilds its list at every step.  Both paths share one block of stores per step.  The
+// persistent fused kernels carry on the launch's composite id table instead (id8_carryc: one row
+// read per item and launch, a.comp staged beside s_fsm; DESIGN §5 "Composite id rows")
 template <bool kPersist, int kDepth, bool kStages4, int kSteps = 1>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kPersist ? 1 : 6))) void sweep8_kernel(SweepArgs a) {
   constexpr int Q = kQ8;
@@ -1636,6 +1676,12 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kPersist
   __shared__ uint32_t s_inv[64];  // kIdInvalid bytes: the inactive lanes' entries (shared by the waves:
                                   // they only ever write 0xFF back)
   __shared__ uint32_t s_fsm[512];
+  // the carried passes of a fused persistent launch look up the launch's composite table (id8_carryc).
+  // The one-tile kernels stay on the id table (id8_carryn): with the composite's 4 KiB a workgroup
+  // holds 31,120 B of LDS, 5 and not 6 of which fit a CU's 160 KiB, and a 12.5M-id shard's 1526
+  // tiles would take two dispatch rounds
+  constexpr bool kCompose = kSteps > 1 && kPersist;
+  __shared__ __attribute__((aligned(16))) uint4 s_comp[kCompose ? 256 : 1];
   __shared__ unsigned int s_stat[kStatWords];
   const uint32_t lane = threadIdx.x & 63;
   const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1665,6 +1711,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kPersist
     const uint32_t t0 = a.fsm[threadIdx.x], t1 = a.fsm[threadIdx.x + kBlock];
     s_fsm[threadIdx.x] = t0;
     s_fsm[threadIdx.x + kBlock] = t1;
+  }
+  if constexpr (kCompose) {  // one 16-byte row per thread
+    static_assert(kBlock == 256, "composite table staging");
+    s_comp[threadIdx.x] = a.comp[threadIdx.x];
   }
   if (threadIdx.x < kStatWords) s_stat[threadIdx.x] = 0;
   if (wave == 0) s_inv[lane] = 0xFFFFFFFFu;
@@ -1727,6 +1777,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kPersist
     constexpr uint32_t kCarry = kWave / (uint32_t)kSteps;
     uint32_t segs[kSteps] = {};  // wave-uniform: the steps' record counts
     bool carry = false;          // wave-uniform
+    uint32_t cstat = 0;          // per lane: the composite rows' matched / bytes fields of this tile
     auto phase12 = [&](const uint4 (&ids)[Q], const int64_t now, const auto first_t, const bool in_lds, uint32_t& seg_n)
                        __attribute__((always_inline)) -> uint32_t {
       constexpr bool first = decltype(first_t)::value;
@@ -1833,10 +1884,18 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kPersist
             if constexpr (kSteps > 1 && first) {
               if (carry) {  // wave-uniform
                 // two passes at a time (all four: 96 / 22 SGPRs spilled in the 4-step persistent / one-tile
-                // kernel against 36 / 0, and no faster: 47.3-48.3 vs 47.1-47.3 us per C5 step)
+                // kernel against 36 / 0, and no faster: 47.3-48.3 vs 47.1-47.3 us per C5 step; on the composite
+                // rows all four fit, 123 VGPRs against 117 and 22 SGPRs spilled either way, and are no
+                // faster either: 44.0-45.0 vs 44.1-44.6 us)
                 static_assert(kB == 4, "two halves");
-                uint32_t live = 0;
                 const uint32_t wa[2] = {we[0], we[1]}, wb[2] = {we[2], we[3]};
+                if constexpr (kCompose) {
+                  id8_carryc<kSteps, 2>(wa, s_comp, wl, segs, cstat, n_lline, stc);
+                  if (c + 128u < n_work)  // wave-uniform
+                    id8_carryc<kSteps, 2>(wb, s_comp, wl, segs, cstat, n_lline, stc);
+                  continue;
+                }
+                uint32_t live = 0;
                 id8_carryn<kSteps, 2>(wa, s_fsm, wl, seg_rs, segs, n_bytes, n_matched, stc, live, s_stat, n_stages, lane);
                 if (c + 128u < n_work)  // wave-uniform
                   id8_carryn<kSteps, 2>(wb, s_fsm, wl, seg_rs, segs, n_bytes, n_matched, stc, live, s_stat, n_stages, lane);
@@ -1895,6 +1954,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kPersist
     };
     const uint32_t n_work = phase12(cur, a.now, std::true_type{}, false, segs[0]);
     uint32_t any_work = n_work;
+    if constexpr (kCompose) {
+      n_matched += cstat & 0xFFFFu;
+      n_bytes += cstat >> kId8cBytesShift;
+    }
 #pragma unroll
     for (int st = 1; st < kSteps; ++st) {
       // step st (a.nowx[st - 1]) on the ids the steps before left: the previous step's records go
@@ -4700,6 +4763,7 @@ struct kwk_engine {
   uint32_t* d_fsm8 = nullptr;     // [2][256] id transition table of sweep8_kernel
   int64_t* d_fsm8_due = nullptr;
   bool fsm8_due_any = false;      // some d_fsm8 entry schedules a delayed stage (kId8Due)
+  uint4* d_comp8 = nullptr;       // [2][256] composite rows of d_fsm8 for launches of 2 and of 4 fused steps
   int64_t* d_due = nullptr;   // due time per slot
   int64_t* d_del = nullptr;
   uint32_t* d_rec = nullptr;
@@ -5062,6 +5126,11 @@ static kwk_status dict_upload(kwk_engine* e) {
   HIP_TRY(upload(e, e->d_w2id, e->h_w2id.data(), 65536));
   HIP_TRY(upload(e, e->d_fsm8, t8.data(), sizeof(uint32_t) * 512));
   HIP_TRY(upload(e, e->d_fsm8_due, d8.data(), sizeof(int64_t) * 512));
+  // the composites change with the id table alone: built here, never per step or per launch
+  std::vector<uint32_t> c8(2 * 256 * kId8cRowWords);
+  id8_compose(t8.data(), 2, c8.data());
+  id8_compose(t8.data(), 4, c8.data() + 256 * kId8cRowWords);
+  HIP_TRY(upload(e, e->d_comp8, c8.data(), sizeof(uint32_t) * c8.size()));
   return KWK_OK;
 }
 
@@ -5243,6 +5312,7 @@ kwk_status kwk_engine_create(const kwk_engine_desc* d, kwk_engine** out) {
   ALLOC(e->d_w2id, 65536);
   ALLOC(e->d_fsm8, sizeof(uint32_t) * 512);
   ALLOC(e->d_fsm8_due, sizeof(int64_t) * 512);
+  ALLOC(e->d_comp8, sizeof(uint4) * 512);
   hipError_t er = hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking);
   if (er != hipSuccess) { kwk_engine_destroy(e); return fail(KWK_EHIP, "hipStreamCreate"); }
   hipMemsetAsync(e->d_st, 0, sizeof(uint2) * st_slots, e->stream);
@@ -5288,7 +5358,7 @@ kwk_status kwk_engine_destroy(kwk_engine* e) {
                   e->d_lease, e->d_lease_op, e->d_lease_ops, e->d_fsm, e->d_fsm_due, e->d_mixed, e->d_ckeys, e->d_ccum,
                   e->d_mbase, e->d_cptr, e->d_mops, e->d_pod_created, e->d_node_created, e->d_node_started, e->d_mout, e->d_alive_bits,
                   e->d_lease_nops, e->d_lease_stats, e->d_ukey8, e->d_kv, e->d_hops, e->d_hbuckets, e->d_hkeys,
-                  e->d_hbounds, e->d_hout, e->d_id2w, e->d_w2id, e->d_fsm8, e->d_fsm8_due};
+                  e->d_hbounds, e->d_hout, e->d_id2w, e->d_w2id, e->d_fsm8, e->d_fsm8_due, e->d_comp8};
   for (void* p : ptrs) if (p) hipFree(p);
   if (e->d_tick_ptr) hipFree(e->d_tick_ptr);
   if (e->ev_lease) hipEventDestroy(e->ev_lease);
@@ -5714,6 +5784,7 @@ static SweepArgs sweep_args(kwk_engine* e, int64_t now_ns, uint64_t seed, uint64
   a.fsm = nullptr;
   a.fsm_due = nullptr;
   a.fsm_bits = 0;
+  a.comp = nullptr;
   a.dw_epoch_old = e->fmt.epoch;
   a.dw_rebase = 0;
   a.tail = SweepArgs::TailHb{nullptr, nullptr, nullptr, nullptr, 0u, 0u};
@@ -5806,6 +5877,7 @@ static kwk_status launch_sweep(kwk_engine* e, int64_t now_ns, uint64_t seed, uin
         a.countsx[i] = e->d_countsx[i];
         a.nowx[i] = now_ns + (int64_t)(i + 1) * dt_ns;
       }
+      a.comp = e->d_comp8 + (steps == 4 ? 256 : 0);
     }
 #define K8(P, D)                                                                                        \
   (steps == 4   ? (const void*)sweep8_kernel<P, D, true, 4>                                            \
