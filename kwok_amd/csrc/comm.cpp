@@ -10,6 +10,7 @@
 
 #include "../../include/kwok_comm.h"
 #include "../../include/kwok_engine.h"
+#include "errscope.hpp"
 
 struct kwk_comm {
   int device = 0;
@@ -24,19 +25,6 @@ struct kwk_comm {
 };
 
 namespace {
-
-thread_local std::string g_err;
-thread_local std::string* tl_err = nullptr;
-struct ErrScope {
-  std::string* prev;
-  explicit ErrScope(kwk_comm* c) : prev(tl_err) { tl_err = c ? &c->err : nullptr; }
-  ~ErrScope() { tl_err = prev; }
-};
-kwk_status fail(kwk_status code, const std::string& msg) {
-  g_err = msg;
-  if (tl_err) *tl_err = msg;
-  return code;
-}
 
 #define HIP_OK(x)                                                                                   \
   do {                                                                                              \
@@ -106,7 +94,7 @@ kwk_status kwk_comm_destroy(kwk_comm* c) {
 }
 
 kwk_status kwk_comm_buffer(kwk_comm* c, uint64_t n, double** dev) {
-  ErrScope es_(c);
+  ErrScope es_(c ? &c->err : nullptr);
   if (!c || !dev) return fail(KWK_EINVAL, "null argument");
   HIP_OK(hipSetDevice(c->device));
   if (n > c->cap) {
@@ -125,7 +113,7 @@ kwk_status kwk_comm_buffer(kwk_comm* c, uint64_t n, double** dev) {
 }
 
 kwk_status kwk_comm_allreduce(kwk_comm* c, uint64_t n, kwk_engine* const* engines, uint32_t n_engines) {
-  ErrScope es_(c);
+  ErrScope es_(c ? &c->err : nullptr);
   if (!c || (n_engines && !engines)) return fail(KWK_EINVAL, "null argument");
   if (n > c->cap) return fail(KWK_EINVAL, "n beyond the communicator's buffer (kwk_comm_buffer)");
   HIP_OK(hipSetDevice(c->device));
@@ -149,7 +137,7 @@ kwk_status kwk_comm_allreduce(kwk_comm* c, uint64_t n, kwk_engine* const* engine
 }
 
 kwk_status kwk_comm_read(kwk_comm* c, double* host_out, uint64_t n) {
-  ErrScope es_(c);
+  ErrScope es_(c ? &c->err : nullptr);
   if (!c || (n && !host_out)) return fail(KWK_EINVAL, "null argument");
   if (n > c->cap) return fail(KWK_EINVAL, "n beyond the communicator's buffer");
   HIP_OK(hipSetDevice(c->device));

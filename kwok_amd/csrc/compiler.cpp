@@ -26,6 +26,7 @@
 
 #include "../../include/kwok_compiler.h"
 #include "../../include/kwok_engine.h"
+#include "errscope.hpp"
 #include "gotpl.hpp"
 #include "host_common.hpp"
 #include "labelsel.hpp"
@@ -38,20 +39,6 @@ using kwkjson::JV;
 using kwkpatch::PJ;
 using kwktpl::TplError;
 using namespace kwknext;
-
-thread_local std::string g_err;
-thread_local std::string* tl_err = nullptr;
-struct ErrScope {
-  std::string* prev;
-  explicit ErrScope(std::string* target) : prev(tl_err) { tl_err = target; }
-  ~ErrScope() { tl_err = prev; }
-};
-kwk_status fail(kwk_status code, const std::string& msg) {
-  g_err = msg;
-  if (tl_err) *tl_err = msg;
-  return code;
-}
-
 
 // Python str(v) of a YAML / JSON scalar (stage_from_v1alpha1's str(...) of values and map entries)
 std::string py_str(const JV& v) {

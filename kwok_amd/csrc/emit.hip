@@ -34,27 +34,10 @@
 #include <vector>
 
 #include "../../include/kwok_emit.h"
+#include "errscope.hpp"
 #include "timefmt.hpp"
 
 namespace {
-
-thread_local std::string g_err;
-thread_local std::string* tl_err = nullptr;
-struct ErrScope {
-  std::string* prev;
-  explicit ErrScope(std::string* target) : prev(tl_err) { tl_err = target; }
-  ~ErrScope() { tl_err = prev; }
-};
-kwk_status fail(kwk_status code, const std::string& msg) {
-  g_err = msg;
-  if (tl_err) *tl_err = msg;
-  return code;
-}
-#define HIP_TRY(x)                                                                                \
-  do {                                                                                            \
-    hipError_t e_ = (x);                                                                          \
-    if (e_ != hipSuccess) return fail(KWK_EHIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
-  } while (0)
 
 constexpr uint32_t kBlock = 256, kTile = kBlock;  // records per tile: one per thread, 64 per wave
 constexpr uint32_t kWaves = kBlock / 64, kWaveRecs = kTile / kWaves;

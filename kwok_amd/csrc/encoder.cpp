@@ -26,26 +26,12 @@
 
 #include "../../include/kwok_engine.h"
 #include "../../include/kwok_encoder.h"
+#include "errscope.hpp"
 #include "host_common.hpp"
 #include "labelsel.hpp"
 #include "nextstate.hpp"
 
 namespace {
-
-// the failing call's message: per handle (the call's own object, see ErrScope) and per thread
-// (calls without a handle: create)
-thread_local std::string g_err;
-thread_local std::string* tl_err = nullptr;
-struct ErrScope {
-  std::string* prev;
-  explicit ErrScope(std::string* target) : prev(tl_err) { tl_err = target; }
-  ~ErrScope() { tl_err = prev; }
-};
-kwk_status fail(kwk_status code, const std::string& msg) {
-  g_err = msg;
-  if (tl_err) *tl_err = msg;
-  return code;
-}
 
 using kwkjson::JV;
 using kwkjson::Parser;

@@ -34,8 +34,7 @@
 
 #include "../../include/kwok_engine.h"
 #include "id8_compose.hpp"
-
-static void engine_set_error(kwk_engine* e, const std::string& msg);
+#include "errscope.hpp"
 
 namespace {
 
@@ -47,31 +46,6 @@ constexpr int kWavesPerBlock = kBlock / 64;
 // counted as the whole lines / chunks the sweep stores)
 constexpr int kStatWords = 4 + KWK_MAX_STAGES;
 constexpr int kStatLine = 3 + KWK_MAX_STAGES;
-
-// Error messages: every failing call stores its message in the engine it was called on
-// (kwk_last_error(eng)), so a caller that moves between OS threads (a cgo goroutine) reads the
-// message of its own engine's call; calls without an engine (kwk_engine_create, pinned host
-// buffers) leave it in the calling thread's slot (kwk_last_error(NULL)).
-thread_local std::string g_err;
-thread_local kwk_engine* tl_eng = nullptr;  // the engine of the API call running on this thread
-
-struct ErrScope {  // marks the engine an API call works on, for fail()
-  kwk_engine* prev;
-  explicit ErrScope(const kwk_engine* e) : prev(tl_eng) { tl_eng = const_cast<kwk_engine*>(e); }
-  ~ErrScope() { tl_eng = prev; }
-};
-
-kwk_status fail(kwk_status code, const std::string& msg) {
-  g_err = msg;
-  if (tl_eng) engine_set_error(tl_eng, msg);
-  return code;
-}
-
-#define HIP_TRY(x)                                                                    \
-  do {                                                                                \
-    hipError_t e_ = (x);                                                              \
-    if (e_ != hipSuccess) return fail(KWK_EHIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
-  } while (0)
 
 // ------------------------------------------------------------------ Philox4x32-10
 __device__ __forceinline__ void philox10(uint32_t& c0, uint32_t& c1, uint32_t& c2, uint32_t& c3, uint32_t k0,
@@ -4878,8 +4852,6 @@ struct kwk_engine {
   std::string err;            // message of the last failing call on this engine (kwk_last_error)
 };
 
-static void engine_set_error(kwk_engine* e, const std::string& msg) { e->err = msg; }
-
 // live engines: a fused tick links a pod engine and a node engine; destroying either unlinks it
 static std::mutex g_live_mu;
 static std::set<kwk_engine*> g_live;
@@ -5374,7 +5346,7 @@ kwk_status kwk_engine_destroy(kwk_engine* e) {
 }
 
 kwk_status kwk_load_stages(kwk_engine* e, const kwk_stage_table* t, const kwk_delta* deltas) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   if (!e || !t) return fail(KWK_EINVAL, "null argument");
   if (t->n_stages > KWK_MAX_STAGES) return fail(KWK_EINVAL, "too many stages");
   if (t->n_classes == 0 && t->n_stages) return fail(KWK_EINVAL, "n_classes must be > 0");
@@ -5474,7 +5446,7 @@ kwk_status kwk_load_stages(kwk_engine* e, const kwk_stage_table* t, const kwk_de
 }
 
 kwk_status kwk_set_tuning(kwk_engine* e, uint32_t key, uint32_t value) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   if (!e) return fail(KWK_EINVAL, "null engine");
   if (kwk_status st = set_dev(e)) return st;
   switch (key) {
@@ -5539,7 +5511,7 @@ kwk_status kwk_set_tuning(kwk_engine* e, uint32_t key, uint32_t value) {
 }
 
 kwk_status kwk_set_harness(kwk_engine* e, const kwk_harness* h) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   if (!e || !h) return fail(KWK_EINVAL, "null argument");
   if (kwk_status st = set_dev(e)) return st;
   // the 1-byte ids encode what the harness makes "work": re-read the rows before it changes
@@ -5554,7 +5526,7 @@ kwk_status kwk_set_harness(kwk_engine* e, const kwk_harness* h) {
 
 kwk_status kwk_load(kwk_engine* e, uint32_t n, const kwk_hot* hot, const int64_t* del, const uint32_t* rec,
                     const uint16_t* cls, uint32_t n_records, const kwk_value* records) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   if (!e || (n && (!hot || !del || !rec || !cls))) return fail(KWK_EINVAL, "null argument");
   if (n > e->capacity) return fail(KWK_ECAP, "n exceeds capacity");
   if (n_records > e->max_records) return fail(KWK_ECAP, "n_records exceeds max_records");
@@ -5599,7 +5571,7 @@ kwk_status kwk_load(kwk_engine* e, uint32_t n, const kwk_hot* hot, const int64_t
 }
 
 kwk_status kwk_set_records(kwk_engine* e, uint32_t first, uint32_t n, const kwk_value* records) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   if (!e || (n && !records)) return fail(KWK_EINVAL, "null argument");
   if ((uint64_t)first + n > e->max_records) return fail(KWK_ECAP, "records exceed max_records");
   if (kwk_status st = set_dev(e)) return st;
@@ -5614,13 +5586,13 @@ static kwk_status scatter_rows(kwk_engine* e, uint32_t n, const uint32_t* slots,
 
 kwk_status kwk_upsert(kwk_engine* e, uint32_t n, const uint32_t* slots, const kwk_hot* hot, const int64_t* del,
                       const uint32_t* rec, const uint16_t* cls) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   return scatter_rows(e, n, slots, hot, del, rec, cls, 1u);
 }
 
 kwk_status kwk_replace(kwk_engine* e, uint32_t n, const uint32_t* slots, const kwk_hot* hot, const int64_t* del,
                        const uint32_t* rec, const uint16_t* cls) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   return scatter_rows(e, n, slots, hot, del, rec, cls, 0u);
 }
 
@@ -5672,7 +5644,7 @@ static kwk_status scatter_rows(kwk_engine* e, uint32_t n, const uint32_t* slots,
 }
 
 kwk_status kwk_delete(kwk_engine* e, uint32_t n, const uint32_t* slots) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   if (!e || (n && !slots)) return fail(KWK_EINVAL, "null argument");
   if (n == 0) return KWK_OK;
   for (uint32_t j = 0; j < n; ++j)
@@ -5691,7 +5663,7 @@ kwk_status kwk_delete(kwk_engine* e, uint32_t n, const uint32_t* slots) {
 kwk_status kwk_retry(kwk_engine* e, int64_t now_ns, uint64_t seed, uint64_t step, uint32_t n, const uint32_t* slots,
                      const kwk_hot* hot, const uint16_t* cls, const uint16_t* stages, const uint32_t* retry_count,
                      const kwk_backoff* backoff) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   if (!e || !backoff || (n && (!slots || !hot || !cls || !stages || !retry_count)))
     return fail(KWK_EINVAL, "null argument");
   if (n == 0) return KWK_OK;
@@ -5838,6 +5810,56 @@ struct TailReq {
 };
 static void hb_tail_args(kwk_engine* e, const TailReq& t, SweepArgs& a);
 
+// The sweep kernels by the choices launch_sweep makes.  The tables list the instantiations in the
+// order the host code has always first named them: the code object lays template kernels out in
+// that order, so a reordered table is a differently laid out (if equivalent) library.
+
+using SweepKernel = void (*)(SweepArgs);
+
+// 1-byte ids: a launch of 4, 2 or 1 steps; one step with at most 4 stages (`stages4`: per-stage
+// counts in scalar registers) or more
+static const void* sweep8_pick(bool persistent, uint32_t depth, bool stages4, uint32_t steps) {
+  // [persistent with depth 2, with depth 1, one block per tile][4 steps, 2 steps, 1 step, 1 step of > 4 stages]
+  static const SweepKernel k[3][4] = {
+      {sweep8_kernel<true, 2, true, 4>, sweep8_kernel<true, 2, true, 2>, sweep8_kernel<true, 2, true>,
+       sweep8_kernel<true, 2, false>},
+      {sweep8_kernel<true, 1, true, 4>, sweep8_kernel<true, 1, true, 2>, sweep8_kernel<true, 1, true>,
+       sweep8_kernel<true, 1, false>},
+      {sweep8_kernel<false, 1, true, 4>, sweep8_kernel<false, 1, true, 2>, sweep8_kernel<false, 1, true>,
+       sweep8_kernel<false, 1, false>}};
+  return (const void*)k[persistent ? (depth == 2 ? 0 : 1) : 2][steps == 4 ? 0 : steps == 2 ? 1 : stages4 ? 2 : 3];
+}
+
+// 2-byte words: `lean` the table-only kernel (its persistent variant with prefetch depth 2 or 1),
+// else the general one
+static const void* sweep16_pick(bool harness, uint32_t q, bool lean, bool persistent, uint32_t depth) {
+  // [q: 4, 1, 2][harness: on, off][persistent: table-only depth 2, depth 1, general; one block per
+  // tile: table-only, general]
+  static const SweepKernel k[3][2][5] = {
+      {{sweep16_fsm_kernel<true, 4, true, 2>, sweep16_fsm_kernel<true, 4, true, 1>, sweep16_kernel<true, 4, true>,
+        sweep16_fsm_kernel<true, 4, false, 1>, sweep16_kernel<true, 4, false>},
+       {sweep16_fsm_kernel<false, 4, true, 2>, sweep16_fsm_kernel<false, 4, true, 1>, sweep16_kernel<false, 4, true>,
+        sweep16_fsm_kernel<false, 4, false, 1>, sweep16_kernel<false, 4, false>}},
+      {{sweep16_fsm_kernel<true, 1, true, 2>, sweep16_fsm_kernel<true, 1, true, 1>, sweep16_kernel<true, 1, true>,
+        sweep16_fsm_kernel<true, 1, false, 1>, sweep16_kernel<true, 1, false>},
+       {sweep16_fsm_kernel<false, 1, true, 2>, sweep16_fsm_kernel<false, 1, true, 1>, sweep16_kernel<false, 1, true>,
+        sweep16_fsm_kernel<false, 1, false, 1>, sweep16_kernel<false, 1, false>}},
+      {{sweep16_fsm_kernel<true, 2, true, 2>, sweep16_fsm_kernel<true, 2, true, 1>, sweep16_kernel<true, 2, true>,
+        sweep16_fsm_kernel<true, 2, false, 1>, sweep16_kernel<true, 2, false>},
+       {sweep16_fsm_kernel<false, 2, true, 2>, sweep16_fsm_kernel<false, 2, true, 1>, sweep16_kernel<false, 2, true>,
+        sweep16_fsm_kernel<false, 2, false, 1>, sweep16_kernel<false, 2, false>}}};
+  const int v = persistent ? (lean ? (depth == 2 ? 0 : 1) : 2) : (lean ? 3 : 4);
+  return (const void*)k[q == 4 ? 0 : q == 1 ? 1 : 2][harness ? 0 : 1][v];
+}
+
+// 4- / 8-byte words: the fused records, the 4-byte words, the 8-byte words; [format][harness: on, off]
+static const void* sweepw_pick(bool harness, bool dw, bool narrow) {
+  static const SweepKernel k[3][2] = {{sweepw_kernel<true, 8, true>, sweepw_kernel<false, 8, true>},
+                                      {sweepw_kernel<true, 4>, sweepw_kernel<false, 4>},
+                                      {sweepw_kernel<true, 8>, sweepw_kernel<false, 8>}};
+  return (const void*)k[dw ? 0 : narrow ? 1 : 2][harness ? 0 : 1];
+}
+
 // steps > 1: the 1-byte sweep takes that many steps (now_ns + s * dt_ns) in one launch (step_group;
 // step s's segments and counts go to d_firedx / d_countsx[s - 1])
 static kwk_status launch_sweep(kwk_engine* e, int64_t now_ns, uint64_t seed, uint64_t step, bool fire,
@@ -5850,7 +5872,7 @@ static kwk_status launch_sweep(kwk_engine* e, int64_t now_ns, uint64_t seed, uin
   e->last_step_no = step + (steps ? steps - 1 : 0);
   if (e->n_active == 0) { e->last_blocks = 0; e->steps += steps; return KWK_OK; }
   SweepArgs a = sweep_args(e, now_ns, seed, step, fire);
-  const bool nar = e->fmt.narrow != 0;
+  const bool nar = e->fmt.narrow != 0, dw = e->fmt.dw != 0;
   const bool h = a.harness.enable != 0;
   // every sweep emits packed fired segments of 64 * K + 32 words per (tile, wave) and counts one
   // statistics row per block: the per-tile arrays are sized for the smallest tile
@@ -5860,15 +5882,18 @@ static kwk_status launch_sweep(kwk_engine* e, int64_t now_ns, uint64_t seed, uin
     a.fsm_bits = e->fsm_bits;
   }
 
+  // 1. the geometry: K words per lane (a tile is kBlock * K objects), and what the hand-back reads
+  //    of it (fired segments per record region = 1 << region_shift, the segments' record kind)
+  uint32_t K, region_shift = 0;
+  int rec = kRecSlot;
+  uint32_t q16 = e->q16;
+  bool lean = false, s4 = false;
   if (e->fmt.byte) {  // 1-byte ids: the table-only id sweep (fire only: kwk_match leaves the format)
     if (!fire) return fail(KWK_ESTATE, "the 1-byte format sweeps with fire only");
     a.fsm = e->d_fsm8;
     a.fsm_due = e->d_fsm8_due;
     a.fsm_bits = e->fsm8_due_any ? kId8AnyDue : 0u;
-    constexpr uint32_t tile = kBlock * 16 * kQ8;
-    const uint32_t tiles = (e->n_active + tile - 1) / tile;
-    const bool s4 = e->n_stages <= 4;  // per-stage counts in scalar registers
-
+    s4 = e->n_stages <= 4;  // per-stage counts in scalar registers
     if (fuse) {
       if (!s4 || (steps != 2 && steps != 4)) return fail(KWK_ESTATE, "fused steps: 2 or 4, 1-byte sweep with <= 4 stages");
       for (uint32_t i = 0; i + 1 < steps; ++i) {
@@ -5879,147 +5904,96 @@ static kwk_status launch_sweep(kwk_engine* e, int64_t now_ns, uint64_t seed, uin
       }
       a.comp = e->d_comp8 + (steps == 4 ? 256 : 0);
     }
-#define K8(P, D)                                                                                        \
-  (steps == 4   ? (const void*)sweep8_kernel<P, D, true, 4>                                            \
-   : steps == 2 ? (const void*)sweep8_kernel<P, D, true, 2>                                            \
-   : s4         ? (const void*)sweep8_kernel<P, D, true> : (const void*)sweep8_kernel<P, D, false>)
-    const void* pk = e->fsm_kernel == 2 ? K8(true, 2) : K8(true, 1);
-    uint32_t pg = e->persist16 ? persist_grid(e, pk, tiles) : tiles;
+    K = 16 * kQ8;
+    rec = s4 ? kRecId8Half : kRecId8;
+  } else if (e->fmt.half) {  // 2-byte words: whole-line write-back sweep
+    // small engines (a node kind, the cache-resident configs) take 2048-word tiles so that
+    // the grid still spreads over every CU
+    if (q16 > 1 && (e->n_active + kBlock * 8 * q16 - 1) / (kBlock * 8 * q16) < 4u * (uint32_t)e->n_cus) q16 = 1;
+    K = 8 * q16;
+    lean = a.fsm && e->fsm_kernel;
+  } else {  // 4- / 8-byte words: whole-line write-back word sweep
+    K = dw ? (uint32_t)kQWD * 2u : (uint32_t)kQW * (nar ? 4u : 2u);
+    region_shift = 2;  // log2(kWavesPerBlock): records carry tile-relative slots
+    static_assert(kWavesPerBlock == 4, "region shift");
+  }
+  const uint32_t tile = kBlock * K;
+  const uint32_t tiles = (e->n_active + tile - 1) / tile;
 
-    uint32_t blocks = tiles;
-    e->last_sweep = kwk_sweep_info{KWK_SWEEP_8, (uint32_t)kQ8, 0, 1, tiles, tiles, a.harness.enable ? 1u : 0u, 0};
-    const void* kern = K8(false, 1);
+  // 2. - 3. the kernel and its grid: persistent (the 1- and 2-byte sweeps: every block slot the
+  //    occupancy allows, the word sweep: several tiles per workgroup) or one block per tile
+  const void* kern;
+  uint32_t blocks = tiles;
+  if (e->fmt.byte || e->fmt.half) {
+    const uint32_t depth = e->fmt.byte ? e->fsm_kernel : lean ? e->fsm_kernel : 1;
+    const void* pk = e->fmt.byte ? sweep8_pick(true, depth, s4, steps) : sweep16_pick(h, q16, lean, true, depth);
+    const uint32_t pg = e->persist16 ? persist_grid(e, pk, tiles) : tiles;
+    const uint32_t kind = e->fmt.byte ? KWK_SWEEP_8 : lean ? KWK_SWEEP_16_FSM : KWK_SWEEP_16;
+    e->last_sweep = kwk_sweep_info{kind, e->fmt.byte ? (uint32_t)kQ8 : q16, 0, 1, tiles, tiles, h ? 1u : 0u, 0};
     if (2 * pg <= tiles) {  // else the persistent loop would run about once: one block per tile
       blocks = pg;
       e->last_sweep.persistent = 1;
       e->last_sweep.grid = pg;
-      e->last_sweep.depth = e->fsm_kernel;
+      e->last_sweep.depth = depth;
       kern = pk;
-    }
-#undef K8
-    void* args[] = {&a};
-    HIP_TRY(hipLaunchKernel(kern, dim3(blocks), dim3(kBlock), args, 0, e->stream));
-    HIP_TRY(hipGetLastError());
-    e->last_objs = 16 * kQ8;
-    e->last_region_shift = 0;
-    e->last_rec = s4 ? kRecId8Half : kRecId8;
-    e->last_blocks = tiles;
-    e->last_grid = blocks;
-    e->cum_rows = blocks > e->cum_rows ? blocks : e->cum_rows;
-    e->last_sweep.steps = steps;
-    e->steps += steps;
-    return KWK_OK;
-  }
-  if (e->fmt.half) {  // 2-byte words: whole-line write-back sweep
-    // small engines (a node kind, the cache-resident configs) take 2048-word tiles so that
-    // the grid still spreads over every CU
-    uint32_t q16 = e->q16;
-    if (q16 > 1 && (e->n_active + kBlock * 8 * q16 - 1) / (kBlock * 8 * q16) < 4u * (uint32_t)e->n_cus) q16 = 1;
-    const uint32_t K = 8 * q16, tile = kBlock * K;
-    const uint32_t tiles = (e->n_active + tile - 1) / tile;
-    uint32_t blocks = tiles;
-    const bool lean = a.fsm && e->fsm_kernel;
-#define LAUNCH16(HV, QV)                                                                                        \
-  do {                                                                                                          \
-    const void* pk = lean ? (e->fsm_kernel == 2 ? (const void*)sweep16_fsm_kernel<HV, QV, true, 2>              \
-                                                : (const void*)sweep16_fsm_kernel<HV, QV, true, 1>)             \
-                          : (const void*)sweep16_kernel<HV, QV, true>;                                          \
-    uint32_t pg = e->persist16 ? persist_grid(e, pk, tiles) : tiles;                                            \
-    e->last_sweep = kwk_sweep_info{lean ? (uint32_t)KWK_SWEEP_16_FSM : (uint32_t)KWK_SWEEP_16, QV, 0, 1, tiles,    \
-                                   tiles, HV ? 1u : 0u, 0};                                                     \
-    if (2 * pg > tiles) { /* the persistent loop would run about once: one block per tile */                   \
-      if (lean && tail && tiles * 4u <= (uint32_t)e->n_cus && tiles * kWavesPerBlock <= e->compact_small) {    \
-        hb_tail_args(e, *tail, a);                                                                              \
-        tail->done = true;                                                                                      \
-      }                                                                                                         \
-      if (lean)                                                                                                 \
-        hipLaunchKernelGGL((sweep16_fsm_kernel<HV, QV, false, 1>), dim3(blocks), dim3(kBlock), 0, e->stream, a); \
-      else                                                                                                      \
-        hipLaunchKernelGGL((sweep16_kernel<HV, QV, false>), dim3(blocks), dim3(kBlock), 0, e->stream, a);     \
-    } else {                                                                                                    \
-      blocks = pg;                                                                                              \
-      e->last_sweep.persistent = 1;                                                                             \
-      e->last_sweep.grid = pg;                                                                                  \
-      e->last_sweep.depth = lean ? e->fsm_kernel : 1;                                                           \
-      if (lean && e->fsm_kernel == 2)                                                                           \
-        hipLaunchKernelGGL((sweep16_fsm_kernel<HV, QV, true, 2>), dim3(blocks), dim3(kBlock), 0, e->stream, a); \
-      else if (lean)                                                                                            \
-        hipLaunchKernelGGL((sweep16_fsm_kernel<HV, QV, true, 1>), dim3(blocks), dim3(kBlock), 0, e->stream, a); \
-      else                                                                                                      \
-        hipLaunchKernelGGL((sweep16_kernel<HV, QV, true>), dim3(blocks), dim3(kBlock), 0, e->stream, a);      \
-    }                                                                                                           \
-  } while (0)
-    if (q16 == 4) {
-      if (h) LAUNCH16(true, 4); else LAUNCH16(false, 4);
-    } else if (q16 == 1) {
-      if (h) LAUNCH16(true, 1); else LAUNCH16(false, 1);
+    } else if (e->fmt.byte) {
+      kern = sweep8_pick(false, 1, s4, steps);
     } else {
-      if (h) LAUNCH16(true, 2); else LAUNCH16(false, 2);
+      if (lean && tail && tiles * 4u <= (uint32_t)e->n_cus && tiles * kWavesPerBlock <= e->compact_small) {
+        hb_tail_args(e, *tail, a);
+        tail->done = true;
+      }
+      kern = sweep16_pick(h, q16, lean, false, 1);
     }
-#undef LAUNCH16
-    e->last_objs = K;
-    e->last_region_shift = 0;
-    e->last_rec = kRecSlot;
-    HIP_TRY(hipGetLastError());
-    e->last_blocks = tiles;  // fired segments / wave counts are per (tile, wave)
-    e->last_grid = blocks;
-    e->cum_rows = blocks > e->cum_rows ? blocks : e->cum_rows;
-    ++e->steps;
-    return KWK_OK;
-  }
-  // 4- / 8-byte words: whole-line write-back word sweep, one block per tile
-  const bool dw = e->fmt.dw != 0;
-  const uint32_t K = dw ? (uint32_t)kQWD * 2u : (uint32_t)kQW * (nar ? 4u : 2u);
-  const uint32_t tile = kBlock * K;
-  const uint32_t tiles = (e->n_active + tile - 1) / tile;
-  // tiles per workgroup (the next tile's stream in flight while one is worked: 8 for the fused
-  // records, 4 for the 4-byte words, r3r), but at least ~5 workgroups per CU
-  // (an explicit KWK_TUNE_WORD_TILES is taken as it is: the parity tests loop small engines)
-  const uint32_t tpb = e->word_tpb ? e->word_tpb : dw ? 8u : 4u;
-  const uint32_t blocks = e->word_tpb ? (tiles + tpb - 1) / tpb
-                                      : std::min(tiles, std::max((tiles + tpb - 1) / tpb, (uint32_t)e->n_cus * 5u));
-  if (dw) {
-    // the fused records' epoch follows the clock: re-encoded (inside this sweep) once now is
-    // more than 2^34 ns (~17 s) past it or before it, so that due times up to ~51 s ahead of now
-    // stay in the 2^36 ns window
-    // (the host's epoch moves only once the re-encoding sweep is enqueued, below)
-    const int64_t e0 = e->fmt.epoch;
-    if (now_ns < e0 || (uint64_t)now_ns - (uint64_t)e0 > kDwRebase) {
-      a.fmt.epoch = now_ns;
-      a.dw_rebase = 1;
-    }
-    if (h) hipLaunchKernelGGL((sweepw_kernel<true, 8, true>), dim3(blocks), dim3(kBlock), 0, e->stream, a);
-    else hipLaunchKernelGGL((sweepw_kernel<false, 8, true>), dim3(blocks), dim3(kBlock), 0, e->stream, a);
-  } else if (nar) {
-    if (h) hipLaunchKernelGGL((sweepw_kernel<true, 4>), dim3(blocks), dim3(kBlock), 0, e->stream, a);
-    else hipLaunchKernelGGL((sweepw_kernel<false, 4>), dim3(blocks), dim3(kBlock), 0, e->stream, a);
+    if (e->fmt.byte) e->last_sweep.steps = steps;
   } else {
-    if (h) hipLaunchKernelGGL((sweepw_kernel<true, 8>), dim3(blocks), dim3(kBlock), 0, e->stream, a);
-    else hipLaunchKernelGGL((sweepw_kernel<false, 8>), dim3(blocks), dim3(kBlock), 0, e->stream, a);
+    // tiles per workgroup (the next tile's stream in flight while one is worked: 8 for the fused
+    // records, 4 for the 4-byte words, r3r), but at least ~5 workgroups per CU
+    // (an explicit KWK_TUNE_WORD_TILES is taken as it is: the parity tests loop small engines)
+    const uint32_t tpb = e->word_tpb ? e->word_tpb : dw ? 8u : 4u;
+    blocks = e->word_tpb ? (tiles + tpb - 1) / tpb
+                         : std::min(tiles, std::max((tiles + tpb - 1) / tpb, (uint32_t)e->n_cus * 5u));
+    if (dw) {
+      // the fused records' epoch follows the clock: re-encoded (inside this sweep) once now is
+      // more than 2^34 ns (~17 s) past it or before it, so that due times up to ~51 s ahead of now
+      // stay in the 2^36 ns window
+      // (the host's epoch moves only once the re-encoding sweep is enqueued, below)
+      const int64_t e0 = e->fmt.epoch;
+      if (now_ns < e0 || (uint64_t)now_ns - (uint64_t)e0 > kDwRebase) {
+        a.fmt.epoch = now_ns;
+        a.dw_rebase = 1;
+      }
+    }
+    kern = sweepw_pick(h, dw, nar);
+    e->last_sweep = kwk_sweep_info{dw ? (uint32_t)KWK_SWEEP_WD : nar ? (uint32_t)KWK_SWEEP_W4 : (uint32_t)KWK_SWEEP_W8,
+                                   (uint32_t)(dw ? kQWD : kQW), blocks < tiles ? 1u : 0u,
+                                   blocks < tiles ? 2u : 1u /* the next tile in flight */, blocks, tiles, h ? 1u : 0u, 0};
   }
-  e->last_sweep = kwk_sweep_info{dw ? (uint32_t)KWK_SWEEP_WD : nar ? (uint32_t)KWK_SWEEP_W4 : (uint32_t)KWK_SWEEP_W8,
-                                 (uint32_t)(dw ? kQWD : kQW), blocks < tiles ? 1u : 0u,
-                                 blocks < tiles ? 2u : 1u /* the next tile in flight */, blocks, tiles, h ? 1u : 0u, 0};
-  e->last_objs = K;
-  e->last_region_shift = 2;  // log2(kWavesPerBlock): records carry tile-relative slots
-  e->last_rec = kRecSlot;
-  static_assert(kWavesPerBlock == 4, "region shift");
+
+  // 4. the launch
+  void* args[] = {&a};
+  HIP_TRY(hipLaunchKernel(kern, dim3(blocks), dim3(kBlock), args, 0, e->stream));
   HIP_TRY(hipGetLastError());
+
+  // 5. what the hand-back and the statistics read of the launch
   if (dw) e->fmt.epoch = a.fmt.epoch;  // the records now hold due times relative to it
+  e->last_objs = K;
+  e->last_region_shift = region_shift;
+  e->last_rec = rec;
   e->last_blocks = tiles;  // fired segments / wave counts are per (tile, wave)
   e->last_grid = blocks;
   e->cum_rows = blocks > e->cum_rows ? blocks : e->cum_rows;
-  ++e->steps;
+  e->steps += steps;
   return KWK_OK;
 }
 
 kwk_status kwk_step(kwk_engine* e, int64_t now_ns, uint64_t seed, uint64_t step) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   return launch_sweep(e, now_ns, seed, step, true);
 }
 
 kwk_status kwk_match(kwk_engine* e, int64_t now_ns, uint64_t seed, uint64_t step) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   if (!e) return fail(KWK_EINVAL, "null engine");
   if (kwk_status st = set_dev(e)) return st;
   if (kwk_status st = leave_byte(e)) return st;  // match-only runs the general word sweep
@@ -6027,7 +6001,7 @@ kwk_status kwk_match(kwk_engine* e, int64_t now_ns, uint64_t seed, uint64_t step
 }
 
 kwk_status kwk_sync(kwk_engine* e) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   if (!e) return fail(KWK_EINVAL, "null engine");
   if (kwk_status st = set_dev(e)) return st;
   HIP_TRY(hipStreamSynchronize(e->stream));
@@ -6146,11 +6120,67 @@ static void hb_tail_args(kwk_engine* e, const TailReq& t, SweepArgs& a) {
                              e->tail_seq, t.mode == HbFmt::Packed ? 1u : 0u};
 }
 
+// the kernel that writes a one-step hand-back's list, by its format and the sweep's record kind:
+// `small` the one-launch hand-back (prefix sums inside the expansion), else the expansion behind the
+// segment scan.  (Listed in the order the host code has always first named them, like the sweeps.)
+// The record kind matters to the kwk_fired_rec / packed expansions only.  Every kernel here takes
+// the CompactArgs; the bitmap writer takes three pointers behind them (BitsWriteKernel; enqueue_compact's args).
+using BitsWriteKernel = void (*)(CompactArgs, const uint32_t*, const uint32_t*, uint32_t*);
+static const void* compact_pick(HbFmt mode, int rec, bool small) {
+  constexpr uint32_t W = kCompactSpw;
+  static_assert(std::is_same<decltype(&bits_write_kernel<true>), BitsWriteKernel>::value &&
+                    std::is_same<decltype(&bits_write_kernel<false>), BitsWriteKernel>::value &&
+                    std::is_same<decltype(&compact16_small_kernel), void (*)(CompactArgs)>::value &&
+                    std::is_same<decltype(&compact16_kernel<kCompact16Spw>), void (*)(CompactArgs)>::value &&
+                    std::is_same<decltype(&compact_small_kernel<kRecSlot>), void (*)(CompactArgs)>::value &&
+                    std::is_same<decltype(&compact_kernel<kRecSlot, false, W>), void (*)(CompactArgs)>::value,
+                "enqueue_compact's argument array");
+  static const void* const k[2][8] = {
+      {(const void*)bits_write_kernel<true>, (const void*)compact16_small_kernel,
+       (const void*)compact_small_kernel<kRecId8Half, true>, (const void*)compact_small_kernel<kRecId8, true>,
+       (const void*)compact_small_kernel<kRecSlot, true>, (const void*)compact_small_kernel<kRecId8Half>,
+       (const void*)compact_small_kernel<kRecId8>, (const void*)compact_small_kernel<kRecSlot>},
+      {(const void*)bits_write_kernel<false>, (const void*)compact16_kernel<kCompact16Spw>,
+       (const void*)compact_kernel<kRecId8Half, true, W>, (const void*)compact_kernel<kRecId8, true, W>,
+       (const void*)compact_kernel<kRecSlot, true, W>, (const void*)compact_kernel<kRecId8Half, false, W>,
+       (const void*)compact_kernel<kRecId8, false, W>, (const void*)compact_kernel<kRecSlot, false, W>}};
+  const int r = rec == kRecId8Half ? 0 : rec == kRecId8 ? 1 : 2;
+  const int col = mode == HbFmt::Bits ? 0 : mode == HbFmt::Packed16 ? 1 : mode == HbFmt::Packed ? 2 + r : 5 + r;
+  return k[small ? 0 : 1][col];
+}
+
+// the 2-byte hand-back of m steps' segments (c4.a[0 .. m)): one launch up to compact_small segments,
+// else the scan and the expansion; for m > 1 each is one launch of every step, blockIdx.y = the step
+static kwk_status launch_compact16(const kwk_engine* e, hipStream_t stream, uint32_t n_waves, CompactArgs4& c4,
+                                   uint32_t m) {
+  constexpr uint32_t W16 = kCompact16Spw;
+  const bool small = n_waves <= e->compact_small;
+  const uint32_t spb = small ? kSmall16Spb : W16 * kWavesPerBlock;  // segments per block
+  const dim3 grid((n_waves + spb - 1) / spb, m);
+  const dim3 scan_grid((n_waves + kScanGroup - 1) / kScanGroup, m);
+  CompactArgs& a = c4.a[0];
+  if (m > 1) {
+    if (small) {
+      hipLaunchKernelGGL(compact16_small_multi_kernel, grid, dim3(kBlock), 0, stream, c4);
+    } else {
+      hipLaunchKernelGGL(seg_scan_multi_kernel, scan_grid, dim3(kBlock), 0, stream, c4);
+      hipLaunchKernelGGL(compact16_multi_kernel<W16>, grid, dim3(kBlock), 0, stream, c4);
+    }
+  } else {
+    if (!small)
+      hipLaunchKernelGGL(seg_scan_kernel, scan_grid, dim3(kBlock), 0, stream, a.counts, n_waves, a.offsets,
+                         const_cast<uint32_t*>(a.group_tot));
+    void* args[] = {&a};
+    HIP_TRY(hipLaunchKernel(compact_pick(HbFmt::Packed16, e->last_rec, small), grid, dim3(kBlock), args, 0, stream));
+  }
+  HIP_TRY(hipGetLastError());
+  return KWK_OK;
+}
+
 static kwk_status enqueue_compact(kwk_engine* e, HbFmt mode) {
   const hipStream_t stream = e->stream;
   const uint32_t n_waves = e->last_blocks * kWavesPerBlock;
   if (hb_segmented(mode) && e->last_rec != kRecId8Half) mode = HbFmt::Packed;
-  const bool packed = mode == HbFmt::Packed, m16 = mode == HbFmt::Packed16, bits = mode == HbFmt::Bits;
   const uint32_t i = hb_next(e);
   if (kwk_status st = hb_prepare(e, i, mode, stream)) return st;
   kwk_engine::HbSlot& h = e->hb[i];
@@ -6160,53 +6190,33 @@ static kwk_status enqueue_compact(kwk_engine* e, HbFmt mode) {
     if (e->hb_track) HIP_TRY(hipMemsetAsync(e->h_len_dev + 2u * i, 0, 2 * sizeof(uint32_t), stream));
     return hb_commit(e, i, e->last_step_no, mode, 0, (int)i, stream, true);
   }
-  const uint32_t blocks = (n_waves + kSegsPerBlock - 1) / kSegsPerBlock;
-  CompactArgs a;
+  CompactArgs4 c4;
+  CompactArgs& a = c4.a[0];
   a.fired32 = reinterpret_cast<const uint32_t*>(e->d_fired);
   a.counts = e->d_wave_counts;
   hb_args(e, i, mode, a);
-  const int rk = e->last_rec;
-  void* args[] = {&a};
-  const uint32_t groups = (n_waves + kScanGroup - 1) / kScanGroup;
-  if (m16 && n_waves <= e->compact_small) {
-    hipLaunchKernelGGL(compact16_small_kernel, dim3((n_waves + kSmall16Spb - 1) / kSmall16Spb), dim3(kBlock), 0, stream, a);
-  } else if (bits && n_waves <= e->compact_small) {
-    hipLaunchKernelGGL(bits_size_kernel, dim3(blocks), dim3(kBlock), 0, stream, a, e->d_bits_wc, e->d_bits_bsum);
-    hipLaunchKernelGGL(bits_write_kernel<true>, dim3(blocks), dim3(kBlock), 0, stream, a, e->d_bits_wc, e->d_bits_bsum,
-                       h.tot);
-  } else if (!m16 && !bits && n_waves <= e->compact_small) {  // one launch: prefix sums inside the expansion
-    const void* k = packed ? (rk == kRecId8Half ? (const void*)compact_small_kernel<kRecId8Half, true>
-                              : rk == kRecId8   ? (const void*)compact_small_kernel<kRecId8, true>
-                                                : (const void*)compact_small_kernel<kRecSlot, true>)
-                           : (rk == kRecId8Half ? (const void*)compact_small_kernel<kRecId8Half>
-                              : rk == kRecId8   ? (const void*)compact_small_kernel<kRecId8>
-                                                : (const void*)compact_small_kernel<kRecSlot>);
-    HIP_TRY(hipLaunchKernel(k, dim3(blocks), dim3(kBlock), args, 0, stream));
-  } else if (bits) {
-    hipLaunchKernelGGL(bits_size_kernel, dim3(blocks), dim3(kBlock), 0, stream, a, e->d_bits_wc, e->d_bits_bsum);
-    hipLaunchKernelGGL(seg_scan_kernel, dim3(groups), dim3(kBlock), 0, stream, e->d_bits_wc, n_waves, h.offsets, h.groups);
-    hipLaunchKernelGGL(bits_write_kernel<false>, dim3(blocks), dim3(kBlock), 0, stream, a, e->d_bits_wc, e->d_bits_bsum,
-                       h.tot);
+  if (mode == HbFmt::Packed16) {
+    if (kwk_status st = launch_compact16(e, stream, n_waves, c4, 1)) return st;
   } else {
-    hipLaunchKernelGGL(seg_scan_kernel, dim3(groups), dim3(kBlock), 0, stream, e->d_wave_counts, n_waves, h.offsets,
-                       h.groups);
-    if (m16) {
-      constexpr uint32_t W16 = kCompact16Spw;
-      hipLaunchKernelGGL(compact16_kernel<W16>, dim3((n_waves + W16 * kWavesPerBlock - 1) / (W16 * kWavesPerBlock)),
-                         dim3(kBlock), 0, stream, a);
-    } else {
-      constexpr uint32_t W = kCompactSpw;
-      const void* k = packed ? (rk == kRecId8Half ? (const void*)compact_kernel<kRecId8Half, true, W>
-                                : rk == kRecId8   ? (const void*)compact_kernel<kRecId8, true, W>
-                                                  : (const void*)compact_kernel<kRecSlot, true, W>)
-                             : (rk == kRecId8Half ? (const void*)compact_kernel<kRecId8Half, false, W>
-                                : rk == kRecId8   ? (const void*)compact_kernel<kRecId8, false, W>
-                                                  : (const void*)compact_kernel<kRecSlot, false, W>);
-      const uint32_t eblocks = (n_waves + W * kWavesPerBlock - 1) / (W * kWavesPerBlock);
-      HIP_TRY(hipLaunchKernel(k, dim3(eblocks), dim3(kBlock), args, 0, stream));
-    }
+    // the bitmap hand-back sizes its segments first and scans those sizes; one workgroup per
+    // kSegsPerBlock segments, the scanned expansion kCompactSpw segments per wave
+    const bool bits = mode == HbFmt::Bits, small = n_waves <= e->compact_small;
+    const uint32_t blocks = (n_waves + kSegsPerBlock - 1) / kSegsPerBlock;
+    const uint32_t eblocks = (n_waves + kCompactSpw * kWavesPerBlock - 1) / (kCompactSpw * kWavesPerBlock);
+    if (bits)
+      hipLaunchKernelGGL(bits_size_kernel, dim3(blocks), dim3(kBlock), 0, stream, a, e->d_bits_wc, e->d_bits_bsum);
+    if (!small)
+      hipLaunchKernelGGL(seg_scan_kernel, dim3((n_waves + kScanGroup - 1) / kScanGroup), dim3(kBlock), 0, stream,
+                         bits ? e->d_bits_wc : e->d_wave_counts, n_waves, h.offsets, h.groups);
+    // the bitmap writer's parameters behind `a` (BitsWriteKernel), which the others do not read
+    const uint32_t* wc = e->d_bits_wc;
+    const uint32_t* bsum = e->d_bits_bsum;
+    uint32_t* tot = h.tot;
+    void* args[] = {&a, &wc, &bsum, &tot};
+    HIP_TRY(hipLaunchKernel(compact_pick(mode, e->last_rec, small), dim3(bits || small ? blocks : eblocks), dim3(kBlock),
+                            args, 0, stream));
+    HIP_TRY(hipGetLastError());
   }
-  HIP_TRY(hipGetLastError());
   return hb_commit(e, i, e->last_step_no, mode, n_waves, (int)i, stream, true);
 }
 
@@ -6295,18 +6305,7 @@ static kwk_status step_group(kwk_engine* e, uint32_t m, int64_t now, int64_t dt,
       a.counts = i ? e->d_countsx[i - 1] : e->d_wave_counts;
       hb_args(e, hb_next(e, i + 1), HbFmt::Packed16, a);
     }
-    const uint32_t blocks = (n_waves + kSegsPerBlock - 1) / kSegsPerBlock;
-    if (n_waves <= e->compact_small) {
-      hipLaunchKernelGGL(compact16_small_multi_kernel, dim3((n_waves + kSmall16Spb - 1) / kSmall16Spb, m), dim3(kBlock), 0,
-                         e->stream, c4);
-    } else {
-      constexpr uint32_t W16 = kCompact16Spw;
-      hipLaunchKernelGGL(seg_scan_multi_kernel, dim3((n_waves + kScanGroup - 1) / kScanGroup, m), dim3(kBlock), 0,
-                         e->stream, c4);
-      hipLaunchKernelGGL(compact16_multi_kernel<W16>, dim3((n_waves + W16 * kWavesPerBlock - 1) / (W16 * kWavesPerBlock), m),
-                         dim3(kBlock), 0, e->stream, c4);
-    }
-    HIP_TRY(hipGetLastError());
+    if (kwk_status st = launch_compact16(e, e->stream, n_waves, c4, m)) return st;
     for (uint32_t i = 1; i < m; ++i) {  // the last step's segments and counts where the engine reads them
       std::swap(e->d_fired, e->d_firedx[i - 1]);
       std::swap(e->d_wave_counts, e->d_countsx[i - 1]);
@@ -6346,7 +6345,7 @@ static int ev_of_group(uint32_t ev_every, uint32_t j, uint32_t m) {
 
 kwk_status kwk_step_n(kwk_engine* e, uint32_t n, int64_t now0_ns, int64_t dt_ns, uint64_t seed, uint64_t step0,
                       uint32_t compact, uint32_t ev_every, uint32_t ev_j0) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   if (!e) return fail(KWK_EINVAL, "null engine");
   if (compact == KWK_COMPACT_PACKED || compact == KWK_COMPACT_PACKED16)
     if (kwk_status st = packed_ok(e)) return st;
@@ -6370,7 +6369,7 @@ kwk_status kwk_step_n(kwk_engine* e, uint32_t n, int64_t now0_ns, int64_t dt_ns,
 
 kwk_status kwk_step_n_pair(kwk_engine* e, kwk_engine* other, uint32_t n, int64_t now0_ns, int64_t dt_ns, uint64_t seed,
                            uint64_t step0, uint32_t compact, uint32_t ev_every, uint32_t ev_j0) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   if (!e || !other) return fail(KWK_EINVAL, "null engine");
   if (e == other) return fail(KWK_EINVAL, "the two engines must differ");
   if (e->device != other->device) return fail(KWK_EINVAL, "the two engines are on different devices");
@@ -6398,7 +6397,7 @@ kwk_status kwk_step_n_pair(kwk_engine* e, kwk_engine* other, uint32_t n, int64_t
 }
 
 kwk_status kwk_fired_keep(kwk_engine* e, uint32_t depth) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   if (!e) return fail(KWK_EINVAL, "null engine");
   if (depth > kHbMax) return fail(KWK_EINVAL, "kwk_fired_keep: depth 0.." + std::to_string(kHbMax));
   if (kwk_status st = set_dev(e)) return st;
@@ -6497,7 +6496,7 @@ static kwk_status fired_prologue(kwk_engine* e, uint32_t format, HbFmt* f) {
 }
 
 kwk_status kwk_fired_compact(kwk_engine* e, uint32_t format) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   if (!e) return fail(KWK_EINVAL, "null engine");
   HbFmt f;
   if (kwk_status st = fired_prologue(e, format, &f)) return st;
@@ -6505,7 +6504,7 @@ kwk_status kwk_fired_compact(kwk_engine* e, uint32_t format) {
 }
 
 kwk_status kwk_fired_device(kwk_engine* e, uint32_t format, const void** list, const uint32_t** count) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   if (!e || !list || !count) return fail(KWK_EINVAL, "null argument");
   HbFmt f;
   if (!hb_fmt_of(format, &f)) return fail(KWK_EINVAL, "format: KWK_COMPACT_REC, _PACKED, _PACKED16 or _BITS");
@@ -6518,7 +6517,7 @@ kwk_status kwk_fired_device(kwk_engine* e, uint32_t format, const void** list, c
 
 kwk_status kwk_fired_read(kwk_engine* e, uint32_t format, void* out, uint64_t cap_bytes, uint32_t* seg_counts,
                           uint32_t seg_cap, kwk_fetch_info* info) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   if (!e || !info) return fail(KWK_EINVAL, "null argument");
   HbFmt f;
   if (kwk_status st = fired_prologue(e, format, &f)) return st;
@@ -6561,7 +6560,7 @@ kwk_status kwk_fired_read(kwk_engine* e, uint32_t format, void* out, uint64_t ca
 
 kwk_status kwk_fired_fetch(kwk_engine* e, uint64_t step, void* out, uint64_t cap_bytes, uint32_t* seg_counts,
                            uint32_t seg_cap, kwk_fetch_info* info) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   if (!e || !info) return fail(KWK_EINVAL, "null argument");
   if (kwk_status st = set_dev(e)) return st;
   memset(info, 0, sizeof(*info));
@@ -6594,7 +6593,7 @@ static kwk_status hb_view(const kwk_engine* e, uint32_t i, kwk_fired_view* out) 
 }
 
 kwk_status kwk_ring_view(kwk_engine* e, uint64_t step, kwk_fired_view* out) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   if (!e || !out) return fail(KWK_EINVAL, "null argument");
   memset(out, 0, sizeof(*out));
   const uint32_t n = (uint32_t)e->hb.size();
@@ -6611,7 +6610,7 @@ kwk_status kwk_ring_view(kwk_engine* e, uint64_t step, kwk_fired_view* out) {
 }
 
 kwk_status kwk_fired_fetch_wait(kwk_engine* e) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   if (!e) return fail(KWK_EINVAL, "null engine");
   if (kwk_status st = set_dev(e)) return st;
   if (e->copy_recorded) HIP_TRY(hipStreamSynchronize(e->copy_stream));  // every slot's copies
@@ -6632,7 +6631,7 @@ kwk_status kwk_free_host(void* p) {
 }
 
 kwk_status kwk_stats(kwk_engine* e, kwk_step_stats* out) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   if (!e || !out) return fail(KWK_EINVAL, "null argument");
   if (kwk_status st = set_dev(e)) return st;
   hipLaunchKernelGGL(reduce_stats_kernel, dim3(kStatWords), dim3(kBlock), 0, e->stream, e->d_cum, e->cum_rows,
@@ -6653,7 +6652,7 @@ kwk_status kwk_stats(kwk_engine* e, kwk_step_stats* out) {
 }
 
 kwk_status kwk_read(kwk_engine* e, uint32_t first, uint32_t n, kwk_hot* hot, int64_t* del) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   if (!e) return fail(KWK_EINVAL, "null engine");
   if ((uint64_t)first + n > e->capacity) return fail(KWK_EINVAL, "range beyond capacity");
   if (kwk_status st = set_dev(e)) return st;
@@ -6679,7 +6678,7 @@ kwk_status kwk_read(kwk_engine* e, uint32_t first, uint32_t n, kwk_hot* hot, int
 
 kwk_status kwk_usage_config(kwk_engine* e, uint32_t n_nodes, const uint32_t* node_ptr, const uint32_t* ukey,
                             uint32_t n_cpu, const double* cpu_values, uint32_t n_mem, const double* mem_values) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   if (!e || !node_ptr || !ukey || !cpu_values || !mem_values) return fail(KWK_EINVAL, "null argument");
   if (n_cpu == 0 || n_mem == 0 || n_cpu > 0x4000 || n_mem > 0x4000) return fail(KWK_EINVAL, "dictionary size");
   if (node_ptr[0] != 0) return fail(KWK_EINVAL, "node_ptr[0] must be 0");
@@ -6816,7 +6815,7 @@ kwk_status kwk_usage_config(kwk_engine* e, uint32_t n_nodes, const uint32_t* nod
 }
 
 kwk_status kwk_usage_mixed(kwk_engine* e, uint32_t n_mixed, const uint32_t* mixed, uint32_t n_ckeys, const uint32_t* ckeys) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   if (!e || (n_mixed && !mixed) || (n_ckeys && !ckeys)) return fail(KWK_EINVAL, "null argument");
   if (!e->d_node_ptr) return fail(KWK_ESTATE, "kwk_usage_config must be called first");
   if (n_mixed > kUKeyMixedIndex) return fail(KWK_ECAP, "too many mixed pods");
@@ -6879,7 +6878,7 @@ static kwk_status ensure_cptr(kwk_engine* e) {
 }
 
 kwk_status kwk_usage_read_containers(kwk_engine* e, uint32_t first, uint32_t n, double* out, uint32_t cap, uint32_t* n_out) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   if (!e || !n_out || (n && cap && !out)) return fail(KWK_EINVAL, "null argument");
   if (!e->d_pod_out) return fail(KWK_ESTATE, "kwk_usage_pods(eng, 1) must be called first");
   if ((uint64_t)first + n > e->n_usage_pods) return fail(KWK_EINVAL, "pods beyond the usage configuration");
@@ -7000,7 +6999,7 @@ static kwk_status check_metric_program(const kwk_metric_op* ops, uint32_t first,
 
 kwk_status kwk_metrics_load(kwk_engine* e, uint32_t n_metrics, const kwk_metric_desc* metrics, uint32_t n_ops,
                             const kwk_metric_op* ops) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   if (!e || (n_metrics && !metrics) || (n_ops && !ops)) return fail(KWK_EINVAL, "null argument");
   uint32_t needs = 0;
   for (uint32_t m = 0; m < n_metrics; ++m)
@@ -7019,7 +7018,7 @@ kwk_status kwk_metrics_load(kwk_engine* e, uint32_t n_metrics, const kwk_metric_
 
 kwk_status kwk_metrics_inputs(kwk_engine* e, const int64_t* pod_created, const int64_t* node_created, const double* started,
                               double zero_time_unix_s) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   if (!e || !pod_created || !node_created || !started) return fail(KWK_EINVAL, "null argument");
   if (!e->d_node_ptr) return fail(KWK_ESTATE, "kwk_usage_config must be called first");
   if (kwk_status st = set_dev(e)) return st;
@@ -7091,7 +7090,7 @@ static kwk_status enqueue_metrics(kwk_engine* e, int64_t now_ns, uint32_t node_f
 
 kwk_status kwk_metrics_eval(kwk_engine* e, int64_t now_ns, uint32_t node_first, uint32_t n_nodes, double* out, uint64_t cap,
                             uint64_t* n_out) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   if (!e || !n_out) return fail(KWK_EINVAL, "null argument");
   uint64_t total = 0;
   if (kwk_status st = enqueue_metrics(e, now_ns, node_first, n_nodes, false, &total)) return st;
@@ -7106,7 +7105,7 @@ kwk_status kwk_metrics_eval(kwk_engine* e, int64_t now_ns, uint32_t node_first, 
 
 kwk_status kwk_metrics_eval_device(kwk_engine* e, int64_t now_ns, uint32_t node_first, uint32_t n_nodes,
                                    const double** out, uint64_t* n_out) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   if (!e || !out || !n_out) return fail(KWK_EINVAL, "null argument");
   *out = nullptr;
   if (kwk_status st = enqueue_metrics(e, now_ns, node_first, n_nodes, true, n_out)) return st;
@@ -7128,7 +7127,7 @@ __global__ __launch_bounds__(kBlock) void alive_bits_kernel(const void* __restri
 
 kwk_status kwk_metrics_series_device(kwk_engine* e, uint32_t node_first, uint32_t n_nodes, const uint32_t** node_ptr,
                                      const uint32_t** cptr, const uint32_t** alive_bits) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   if (!e || !node_ptr || !cptr || !alive_bits) return fail(KWK_EINVAL, "null argument");
   if (!e->d_node_ptr) return fail(KWK_ESTATE, "kwk_usage_config must be called first");
   if (e->has_mixed_keys && !e->d_mixed) return fail(KWK_ESTATE, "kwk_usage_mixed must be called first");
@@ -7161,7 +7160,7 @@ static bool go_float_less(double x, double y) { return x < y || (std::isnan(x) &
 
 kwk_status kwk_histograms_load(kwk_engine* e, uint32_t n_hist, const kwk_histogram_desc* hists, uint32_t n_buckets,
                                const kwk_metric_bucket* buckets, uint32_t n_ops, const kwk_metric_op* ops) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   if (!e || (n_hist && !hists) || (n_buckets && !buckets) || (n_ops && !ops)) return fail(KWK_EINVAL, "null argument");
   uint32_t needs = 0;
   std::vector<HistDesc> hd(n_hist);
@@ -7265,7 +7264,7 @@ static kwk_status enqueue_histograms(kwk_engine* e, int64_t now_ns, uint32_t nod
 
 kwk_status kwk_histograms_eval(kwk_engine* e, int64_t now_ns, uint32_t node_first, uint32_t n_nodes, uint64_t* out,
                                uint64_t cap, uint64_t* n_out) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   if (!e || !n_out) return fail(KWK_EINVAL, "null argument");
   uint64_t total = 0;
   if (kwk_status st = enqueue_histograms(e, now_ns, node_first, n_nodes, false, &total)) return st;
@@ -7280,7 +7279,7 @@ kwk_status kwk_histograms_eval(kwk_engine* e, int64_t now_ns, uint32_t node_firs
 
 kwk_status kwk_histograms_eval_device(kwk_engine* e, int64_t now_ns, uint32_t node_first, uint32_t n_nodes,
                                       const uint64_t** out, uint64_t* n_out) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   if (!e || !out || !n_out) return fail(KWK_EINVAL, "null argument");
   *out = nullptr;
   if (kwk_status st = enqueue_histograms(e, now_ns, node_first, n_nodes, true, n_out)) return st;
@@ -7337,7 +7336,7 @@ static kwk_status enqueue_usage(kwk_engine* e, int64_t now_ns, uint32_t* n_block
 }
 
 kwk_status kwk_usage(kwk_engine* e, int64_t now_ns) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   if (!e) return fail(KWK_EINVAL, "null engine");
   if (!e->d_node_ptr) return fail(KWK_ESTATE, "kwk_usage_config must be called first");
   if (e->n_nodes == 0) return KWK_OK;
@@ -7350,7 +7349,7 @@ kwk_status kwk_usage(kwk_engine* e, int64_t now_ns) {
 }
 
 kwk_status kwk_usage_pods(kwk_engine* e, uint32_t enable) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   if (!e) return fail(KWK_EINVAL, "null engine");
   if (kwk_status st = set_dev(e)) return st;
   HIP_TRY(hipStreamSynchronize(e->stream));
@@ -7372,7 +7371,7 @@ kwk_status kwk_usage_pods(kwk_engine* e, uint32_t enable) {
 }
 
 kwk_status kwk_usage_read_pods(kwk_engine* e, uint32_t first, uint32_t n, double* pod_out) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   if (!e || (n && !pod_out)) return fail(KWK_EINVAL, "null argument");
   if (!e->d_pod_out) return fail(KWK_ESTATE, "kwk_usage_pods(eng, 1) must be called first");
   if ((uint64_t)first + n > e->capacity) return fail(KWK_EINVAL, "range beyond capacity");
@@ -7383,7 +7382,7 @@ kwk_status kwk_usage_read_pods(kwk_engine* e, uint32_t first, uint32_t n, double
 }
 
 kwk_status kwk_usage_read(kwk_engine* e, double* node_out, double* cluster_out) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   if (!e) return fail(KWK_EINVAL, "null engine");
   if (!e->d_node_ptr) return fail(KWK_ESTATE, "kwk_usage_config must be called first");
   if (kwk_status st = set_dev(e)) return st;
@@ -7401,7 +7400,7 @@ static kwk_status ensure_count_part(kwk_engine* e) {
 }
 
 kwk_status kwk_count(kwk_engine* e, uint32_t n_masks, const uint32_t* masks, uint64_t* counts) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   if (!e || (n_masks && (!masks || !counts))) return fail(KWK_EINVAL, "null argument");
   if (n_masks > kMaxCountMasks) return fail(KWK_EINVAL, "at most 16 masks");
   if (n_masks == 0) return KWK_OK;
@@ -7436,7 +7435,7 @@ kwk_status kwk_count(kwk_engine* e, uint32_t n_masks, const uint32_t* masks, uin
 
 kwk_status kwk_aggregate(kwk_engine* e, uint32_t n_masks, const uint32_t* masks, int64_t now_ns, uint32_t flags,
                          double* out, uint32_t* n_out) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   if (!e || !n_out || (n_masks && !masks)) return fail(KWK_EINVAL, "null argument");
   if (n_masks > kMaxCountMasks) return fail(KWK_EINVAL, "at most 16 masks");
   const bool usage = (flags & KWK_AGG_USAGE) != 0;
@@ -7506,7 +7505,7 @@ kwk_status kwk_aggregate(kwk_engine* e, uint32_t n_masks, const uint32_t* masks,
 }
 
 kwk_status kwk_aggregate_read(kwk_engine* e, double* host_out, uint32_t n) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   if (!e || (n && !host_out)) return fail(KWK_EINVAL, "null argument");
   if (n > KWK_MAX_STAGES + kMaxCountMasks + 2) return fail(KWK_EINVAL, "more doubles than kwk_aggregate writes");
   if (!e->d_agg) return fail(KWK_ESTATE, "kwk_aggregate must be called first");
@@ -7518,7 +7517,7 @@ kwk_status kwk_aggregate_read(kwk_engine* e, double* host_out, uint32_t n) {
 
 // ---- node leases
 kwk_status kwk_lease_config(kwk_engine* e, const kwk_lease_params* cfg) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   if (!e || !cfg) return fail(KWK_EINVAL, "null argument");
   if (cfg->renew_interval_ns <= 0) return fail(KWK_EINVAL, "renew_interval_ns must be > 0");
   if (kwk_status st = set_dev(e)) return st;
@@ -7540,7 +7539,7 @@ kwk_status kwk_lease_config(kwk_engine* e, const kwk_lease_params* cfg) {
 }
 
 kwk_status kwk_lease_set(kwk_engine* e, uint32_t first, uint32_t n, const kwk_lease* leases) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   if (!e || (n && !leases)) return fail(KWK_EINVAL, "null argument");
   if (!e->lease_on) return fail(KWK_ESTATE, "kwk_lease_config must be called first");
   if ((uint64_t)first + n > e->capacity) return fail(KWK_ECAP, "lease range beyond capacity");
@@ -7584,7 +7583,7 @@ static kwk_status enqueue_lease_step(kwk_engine* e, int64_t now_ns, uint64_t see
 }
 
 kwk_status kwk_lease_step(kwk_engine* e, int64_t now_ns, uint64_t seed, uint64_t step) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   if (!e) return fail(KWK_EINVAL, "null engine");
   if (!e->lease_on) return fail(KWK_ESTATE, "kwk_lease_config must be called first");
   if (kwk_status st = set_dev(e)) return st;
@@ -7593,7 +7592,7 @@ kwk_status kwk_lease_step(kwk_engine* e, int64_t now_ns, uint64_t seed, uint64_t
 
 kwk_status kwk_lease_fail(kwk_engine* e, int64_t now_ns, uint64_t seed, uint64_t step, uint32_t n, const uint32_t* slots,
                           const kwk_lease* old) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   if (!e || (n && (!slots || !old))) return fail(KWK_EINVAL, "null argument");
   if (!e->lease_on) return fail(KWK_ESTATE, "kwk_lease_config must be called first");
   if (n == 0) return KWK_OK;
@@ -7628,7 +7627,7 @@ kwk_status kwk_lease_fail(kwk_engine* e, int64_t now_ns, uint64_t seed, uint64_t
 }
 
 kwk_status kwk_lease_ops(kwk_engine* e, kwk_fired_rec* out, uint32_t cap, uint32_t* n_out) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   if (!e || !n_out) return fail(KWK_EINVAL, "null argument");
   if (!e->lease_on) return fail(KWK_ESTATE, "kwk_lease_config must be called first");
   if (kwk_status st = set_dev(e)) return st;
@@ -7643,7 +7642,7 @@ kwk_status kwk_lease_ops(kwk_engine* e, kwk_fired_rec* out, uint32_t cap, uint32
 }
 
 kwk_status kwk_lease_read(kwk_engine* e, uint32_t first, uint32_t n, kwk_lease* out) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   if (!e || (n && !out)) return fail(KWK_EINVAL, "null argument");
   if (!e->lease_on) return fail(KWK_ESTATE, "kwk_lease_config must be called first");
   if ((uint64_t)first + n > e->capacity) return fail(KWK_EINVAL, "range beyond capacity");
@@ -7654,7 +7653,7 @@ kwk_status kwk_lease_read(kwk_engine* e, uint32_t first, uint32_t n, kwk_lease* 
 }
 
 kwk_status kwk_lease_stats(kwk_engine* e, kwk_lease_counters* out) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   if (!e || !out) return fail(KWK_EINVAL, "null argument");
   if (!e->lease_on) return fail(KWK_ESTATE, "kwk_lease_config must be called first");
   if (kwk_status st = set_dev(e)) return st;
@@ -7670,7 +7669,7 @@ kwk_status kwk_lease_stats(kwk_engine* e, kwk_lease_counters* out) {
 }
 
 kwk_status kwk_lease_sync_pods(kwk_engine* pods, const kwk_engine* nodes, uint32_t n_nodes, const uint32_t* node_ptr) {
-  ErrScope es_(pods);
+  ErrScope es_(pods ? &pods->err : nullptr);
   if (!pods || !nodes || !node_ptr) return fail(KWK_EINVAL, "null argument");
   if (!nodes->lease_on) return fail(KWK_ESTATE, "node engine has no lease configuration");
   if (n_nodes > nodes->n_active) return fail(KWK_EINVAL, "n_nodes beyond the node engine's objects");
@@ -7694,7 +7693,7 @@ kwk_status kwk_lease_sync_pods(kwk_engine* pods, const kwk_engine* nodes, uint32
 
 // ---- the fused reconciliation tick (C3): lease step -> pod sync -> node step -> pod step
 kwk_status kwk_tick_bind(kwk_engine* pods, const kwk_engine* nodes, uint32_t n_nodes, const uint32_t* node_ptr) {
-  ErrScope es_(pods);
+  ErrScope es_(pods ? &pods->err : nullptr);
   if (!pods || !nodes || !node_ptr) return fail(KWK_EINVAL, "null argument");
   if (pods == nodes) return fail(KWK_EINVAL, "pod and node engines must differ");
   if (!nodes->lease_on) return fail(KWK_ESTATE, "node engine has no lease configuration");
@@ -7750,14 +7749,14 @@ static kwk_status tick_check(kwk_engine* nodes, kwk_engine* pods) {
 }
 
 kwk_status kwk_tick(kwk_engine* nodes, kwk_engine* pods, int64_t now_ns, uint64_t seed, uint64_t step, uint32_t flags) {
-  ErrScope es_(nodes);
+  ErrScope es_(nodes ? &nodes->err : nullptr);
   if (kwk_status st = tick_check(nodes, pods)) return st;
   return enqueue_tick(nodes, pods, now_ns, seed, step, flags);
 }
 
 kwk_status kwk_tick_n(kwk_engine* nodes, kwk_engine* pods, uint32_t n, int64_t now0_ns, int64_t dt_ns, uint64_t seed,
                       uint64_t step0, uint32_t flags) {
-  ErrScope es_(nodes);
+  ErrScope es_(nodes ? &nodes->err : nullptr);
   if (kwk_status st = tick_check(nodes, pods)) return st;
   for (uint32_t k = 0; k < n; ++k)
     if (kwk_status st = enqueue_tick(nodes, pods, now0_ns + (int64_t)k * dt_ns, seed, step0 + k, flags)) return st;
@@ -7765,7 +7764,7 @@ kwk_status kwk_tick_n(kwk_engine* nodes, kwk_engine* pods, uint32_t n, int64_t n
 }
 
 kwk_status kwk_device_ptrs(kwk_engine* e, void** hot, void** fired, void** wave_counts) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   if (!e) return fail(KWK_EINVAL, "null engine");
   if (hot) *hot = e->d_st;
   if (fired) *fired = e->d_fired;
@@ -7775,21 +7774,21 @@ kwk_status kwk_device_ptrs(kwk_engine* e, void** hot, void** fired, void** wave_
 
 // ---- timing helpers (HIP events on the engine's own stream; bench.py)
 kwk_status kwk_last_sweep(kwk_engine* e, kwk_sweep_info* out) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   if (!e || !out) return fail(KWK_EINVAL, "null argument");
   *out = e->last_sweep;
   return KWK_OK;
 }
 
 kwk_status kwk_stream(kwk_engine* e, void** stream) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   if (!e || !stream) return fail(KWK_EINVAL, "null argument");
   *stream = (void*)e->stream;
   return KWK_OK;
 }
 
 kwk_status kwk_event_record(kwk_engine* e, uint32_t idx) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   if (!e) return fail(KWK_EINVAL, "null engine");
   if (kwk_status st = set_dev(e)) return st;
   while (e->events.size() <= idx) {
@@ -7803,7 +7802,7 @@ kwk_status kwk_event_record(kwk_engine* e, uint32_t idx) {
 }
 
 kwk_status kwk_event_elapsed(kwk_engine* e, uint32_t a, uint32_t b, float* ms) {
-  ErrScope es_(e);
+  ErrScope es_(e ? &e->err : nullptr);
   if (!e || !ms || a >= e->events.size() || b >= e->events.size()) return fail(KWK_EINVAL, "bad event index");
   if (kwk_status st = set_dev(e)) return st;
   HIP_TRY(hipEventSynchronize(e->events[b]));

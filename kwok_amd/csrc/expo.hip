@@ -56,28 +56,11 @@
 #include <vector>
 
 #include "../../include/kwok_expo.h"
+#include "errscope.hpp"
 #include "f64fmt.hpp"
 #include "keycmp.hpp"
 
 namespace {
-
-thread_local std::string g_err;
-thread_local std::string* tl_err = nullptr;
-struct ErrScope {
-  std::string* prev;
-  explicit ErrScope(std::string* target) : prev(tl_err) { tl_err = target; }
-  ~ErrScope() { tl_err = prev; }
-};
-kwk_status fail(kwk_status code, const std::string& msg) {
-  g_err = msg;
-  if (tl_err) *tl_err = msg;
-  return code;
-}
-#define HIP_TRY(x)                                                                                \
-  do {                                                                                            \
-    hipError_t e_ = (x);                                                                          \
-    if (e_ != hipSuccess) return fail(KWK_EHIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
-  } while (0)
 
 constexpr uint32_t kScanBlock = 1024;
 constexpr uint32_t kFmtBlock = 256;

@@ -26,6 +26,7 @@
 
 #include "../../include/kwok_engine.h"
 #include "../../include/kwok_patch.h"
+#include "errscope.hpp"
 #include "json_dom.hpp"
 #include "timefmt.hpp"
 
@@ -33,21 +34,6 @@ namespace {
 
 using kwkjson::JV;
 using kwkjson::Parser;
-
-// the failing call's message: per handle (the call's own object, see ErrScope) and per thread
-// (calls without a handle: create)
-thread_local std::string g_err;
-thread_local std::string* tl_err = nullptr;
-struct ErrScope {
-  std::string* prev;
-  explicit ErrScope(std::string* target) : prev(tl_err) { tl_err = target; }
-  ~ErrScope() { tl_err = prev; }
-};
-kwk_status fail(kwk_status code, const std::string& msg) {
-  g_err = msg;
-  if (tl_err) *tl_err = msg;
-  return code;
-}
 
 struct NeedsRender {};  // thrown while rendering one object: fall back to the host renderer
 // skeleton mode: the template's bytes depend on more than the object's class, Now and the values

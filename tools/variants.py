@@ -6,6 +6,7 @@ removed work costs on the C2-mix HBM working set.
     python tools/variants.py build [names...]      # -> tools/build/libkwok_engine_<name>.so ("a+b": b applied to a)
     python tools/variants.py run [names...]        # one child process per variant, JSON lines
     python tools/variants.py snap                  # HEAD's engine.hip -> tools/ab/ (the "head" variant on the box)
+    python tools/variants.py check                 # every variant's patterns still match (nothing is compiled)
 """
 from __future__ import annotations
 
@@ -19,6 +20,32 @@ from concurrent.futures import ThreadPoolExecutor
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "kwok_amd", "csrc", "engine.hip")
 OUT = os.path.join(ROOT, "tools", "build")
+SNAP = os.path.join(ROOT, "tools", "ab", "engine_head.hip")
+
+
+def tree_source():
+    return open(SRC).read()
+
+
+def head_source():
+    """The committed engine: same-box A/B against the working tree ("base").  The GPU box has no
+    .git: `variants.py snap` leaves HEAD's source in tools/ab/ first."""
+    if os.path.exists(SNAP):
+        return open(SNAP).read()
+    return subprocess.run(["git", "show", "HEAD:kwok_amd/csrc/engine.hip"], cwd=ROOT, check=True, capture_output=True,
+                          text=True).stdout
+
+
+def apply(name, src):
+    """Variant `name` ("a+b": b's replacements applied to a's source) of the engine's source."""
+    parts = name.split("+")
+    s = head_source() if parts[0] == "head" else src
+    for part in parts:
+        for old, new in VARIANTS[part]:
+            if old not in s:
+                raise SystemExit(f"variant {name}: pattern not found: {old[:60]!r}")
+            s = s.replace(old, new)
+    return s
 
 _P2 = ("const uint2 nv = process_object<kHarness, kWB, false, kDW>(a, T, deltas, n_stages, fin_group, i, s.x, s.y, due,\n"
        "                                                                   f, n_matched, lutp, lut_n, due_set, due_w);")
@@ -27,11 +54,7 @@ _PF_EARLY = ("  if (tile + gridDim.x < n_tiles) load_tile(tile + gridDim.x);  //
 _PF_LATE = ("  const bool rebase = kDW && a.dw_rebase;",
             "  if (tile + gridDim.x < n_tiles) load_tile(tile + gridDim.x);\n  const bool rebase = kDW && a.dw_rebase;")
 
-_S8_INV = [("  __shared__ uint32_t s_inv[kWavesPerBlock][64];", "  __shared__ uint32_t s_inv[64];"),
-           ("  s_inv[wave][lane] = 0xFFFFFFFFu;", "  s_inv[lane] = 0xFFFFFFFFu;"),
-           ("lds_addr(&s_inv[wave][lane])", "lds_addr(&s_inv[lane])")]
-
-_FORCE = ("const bool lean = a.fsm && e->fsm_kernel;", "const bool lean = a.fsm && e->fsm_kernel;")
+_FORCE = ("    lean = a.fsm && e->fsm_kernel;", "    lean = a.fsm && e->fsm_kernel;")
 
 _NOCALL = ("          const uint2 r = general16<kHarness>(wbase + w, (uint32_t)tw[w]);",
            "          const uint2 r = make_uint2(0u, 0u);")
@@ -46,8 +69,6 @@ VARIANTS = {
                   "delay = (int64_t)((uint64_t)delay + (uint64_t)(jit >> 1));")],
     # the word sweep's fired records / per-stage counts are not written
     "w_noemit": [("      emit_fired<true>(f, off, lane, seg, seg_n, s_stat, n_bytes);\n", "      (void)f;\n")],
-    # scheduled stages do not store their due time (the due column is only read)
-    "nodue_w": [("    else a.due[i] = due;\n", "    else (void)due;\n")],
     # table-only 2-byte sweep (sweep16_fsm_kernel) even when some table entry is general (pod-fast at
     # C5 reaches none of them: results stay correct there, not in general)
     "f_force": [_FORCE],
@@ -80,32 +101,13 @@ VARIANTS = {
     # no deletion-column loads (pod-delete's jitterDurationFrom)
     "w_nodel": [("    const int64_t dels = need_del ? a.del_s[i] : KWK_DEL_ABSENT;",
                  "    const int64_t dels = KWK_DEL_ABSENT;")],
-    # 1-byte sweep (run with --c5): no phase 2, every line of the column rewritten — the kernel's
-    # own read + rewrite stream (wrong results: the ids never change)
-    "s8_stream": [("    if (n_work) {  // wave-uniform\n      // ---- phase 2: the ids to the LDS tile",
-                   "    if (false) {  // wave-uniform\n      // ---- phase 2: the ids to the LDS tile"),
-                  ("      const bool st = (ballot(ch) >> (lane & ~(kStoreLanes - 1u))) & ((1ull << kStoreLanes) - 1ull);",
-                   "      const bool st = real || ch;")],
-    # ... and no line stores: the read stream alone
-    "s8_read": [("    if (n_work) {  // wave-uniform\n      // ---- phase 2: the ids to the LDS tile",
-                 "    if (false) {  // wave-uniform\n      // ---- phase 2: the ids to the LDS tile"),
-                ("      const bool st = (ballot(ch) >> (lane & ~(kStoreLanes - 1u))) & ((1ull << kStoreLanes) - 1ull);",
-                 "      const bool st = !real && ch;")],
-    # sweep8: one kIdInvalid row shared by the block's waves (LDS 27.8 -> 27.0 KB: 6 workgroups per CU
-    # fit) / and a VGPR cap for 6 waves per SIMD (run with --c5; r3x: 52.5-53.6 / 53.6-53.9 vs
-    # 52.7-52.8 us, not kept)
-    "s8_inv": _S8_INV,
-    "s8_lb6": _S8_INV + [("__global__ __launch_bounds__(kBlock) void sweep8_kernel(SweepArgs a) {",
-                          "__global__ __launch_bounds__(kBlock, 6) void sweep8_kernel(SweepArgs a) {")],
     # sweep8: 1 / 2 id passes per loop step instead of 4 (run with --c5)
     "id8b1": [("constexpr uint32_t kId8Batch = 4;", "constexpr uint32_t kId8Batch = 1;")],
     "id8b2": [("constexpr uint32_t kId8Batch = 4;", "constexpr uint32_t kId8Batch = 2;")],
     # fused word sweep capped at 6 waves per SIMD instead of 5 (the round-4 default)
     "lb6": [("constexpr int kDwMinBlocks = 5;", "constexpr int kDwMinBlocks = 6;")],
-    # sweep8 cost isolation (the shard-size step, --c5 --c5-nodes 125000): no phase 2 (no LDS passes,
-    # no fires) / no statistics atomics at the end / no phase-3 line stores / an empty kernel
-    "s8_nop2": [("    if (n_work) {  // wave-uniform\n      // ---- phase 2: the ids to the LDS tile",
-                 "    if (n_work && a.n == 0u) {  // wave-uniform\n      // ---- phase 2: the ids to the LDS tile")],
+    # sweep8 cost isolation (the shard-size step, --c5 --c5-nodes 125000): no statistics atomics at the
+    # end / no phase-3 line stores / an empty kernel
     "s8_nostat": [("    if (val) atomicAdd(&a.cum[(uint64_t)blockIdx.x * kStatWords + threadIdx.x], (unsigned long long)val);\n"
                    "  }\n}\n\n// ------------------------------------------------------------------ 4- and 8-byte state sweep",
                    "    if (val && a.n == 0u) atomicAdd(&a.cum[(uint64_t)blockIdx.x * kStatWords + threadIdx.x], "
@@ -134,8 +136,6 @@ VARIANTS = {
     # the matcher's Philox block replaced by a few multiplies (the pick and jitter draws)
     "w_nophilox": [("    philox10(c0, c1, c2, c3, (uint32_t)a.key, (uint32_t)(a.key >> 32));",
                     "    c0 ^= c1 * 0x9E3779B9u; c1 ^= c0 * 0x85EBCA6Bu; c2 ^= c1 * 0xC2B2AE35u; c3 ^= c2 * 0x27D4EB2Fu;")],
-    # fused: fired records stored per phase-2 pass (not staged in LDS)
-    "w_nolds": [("constexpr bool kDwLdsRecs = true;", "constexpr bool kDwLdsRecs = false;")],
     # fused word sweep: each wave touches the 32 lines of its region of the tile after next (one dword
     # load per line, into L2), so the next tile's prefetch issued before phase 2 — which phase 2's
     # loads wait behind in the in-order vmcnt queue — hits L2
@@ -176,26 +176,11 @@ VARIANTS = {
 
 def build(names):
     os.makedirs(OUT, exist_ok=True)
-    src = open(SRC).read()
+    src = tree_source()
 
     def one(name):
-        s = src
-        parts = name.split("+")  # "a+b": variant b's replacements applied to variant a's source
-        if parts[0] == "head":  # the committed engine.hip: same-box A/B against the working tree ("base");
-            # the GPU box has no .git: `variants.py snap` leaves HEAD's source in tools/ab/ first
-            snap = os.path.join(ROOT, "tools", "ab", "engine_head.hip")
-            if os.path.exists(snap):
-                s = open(snap).read()
-            else:
-                s = subprocess.run(["git", "show", "HEAD:kwok_amd/csrc/engine.hip"], cwd=ROOT, check=True,
-                                   capture_output=True, text=True).stdout
-        for part in parts:
-            for old, new in VARIANTS[part]:
-                if old not in s:
-                    raise SystemExit(f"variant {name}: pattern not found: {old[:60]!r}")
-                s = s.replace(old, new)
         path = os.path.join(OUT, f"engine_{name}.hip")
-        open(path, "w").write(s)
+        open(path, "w").write(apply(name, src))
         so = os.path.join(OUT, f"libkwok_engine_{name}.so")
         cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wno-unused-result",
                "-Wno-unused-value", "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "kwok_amd", "csrc"),
@@ -233,7 +218,7 @@ def child_c5(name, steps, nodes=0):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("cmd", choices=("build", "run", "child", "snap"))
+    ap.add_argument("cmd", choices=("build", "run", "child", "snap", "check"))
     ap.add_argument("names", nargs="*")
     ap.add_argument("--hbm-nodes", type=int, default=1_000_000)
     ap.add_argument("--steps", type=int, default=10)
@@ -243,10 +228,17 @@ def main():
     a = ap.parse_args()
     names = a.names or list(VARIANTS)
     if a.cmd == "snap":
-        os.makedirs(os.path.join(ROOT, "tools", "ab"), exist_ok=True)
-        src = subprocess.run(["git", "show", "HEAD:kwok_amd/csrc/engine.hip"], cwd=ROOT, check=True,
-                             capture_output=True, text=True).stdout
-        open(os.path.join(ROOT, "tools", "ab", "engine_head.hip"), "w").write(src)
+        if os.path.exists(SNAP):
+            os.remove(SNAP)  # head_source() would return the old snapshot
+        os.makedirs(os.path.dirname(SNAP), exist_ok=True)
+        src = head_source()
+        open(SNAP, "w").write(src)
+    elif a.cmd == "check":
+        src = tree_source()
+        for n in names:
+            if n != "head":
+                apply(n, src)
+        print(f"{len(names)} variants: every pattern found")
     elif a.cmd == "build":
         build(names)
     elif a.cmd == "child":
