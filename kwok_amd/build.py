@@ -12,7 +12,8 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 SRC = [os.path.join(PKG, "csrc", "engine.hip")]
 ERR_HDR = os.path.join(PKG, "csrc", "errscope.hpp")  # the error scope every library includes
-HDR = [os.path.join(ROOT, "include", "kwok_engine.h"), os.path.join(PKG, "csrc", "id8_compose.hpp"), ERR_HDR]
+MEM_HDR = os.path.join(PKG, "csrc", "devmem.hpp")    # the owners of device memory and events of the HIP libraries
+HDR = [os.path.join(ROOT, "include", "kwok_engine.h"), os.path.join(PKG, "csrc", "id8_compose.hpp"), ERR_HDR, MEM_HDR]
 OUT = os.path.join(PKG, "lib", "libkwok_engine.so")
 DOM_HDR = os.path.join(PKG, "csrc", "json_dom.hpp")
 ENC_SRC = [os.path.join(PKG, "csrc", "encoder.cpp")]
@@ -31,16 +32,16 @@ COMPILER_HDR = [os.path.join(ROOT, "include", "kwok_compiler.h"), os.path.join(R
                                             "celc.hpp", "f64fmt.hpp", "f64fmt_tables.hpp", "errscope.hpp")]
 COMPILER_OUT = os.path.join(PKG, "lib", "libkwok_compiler.so")
 COMM_SRC = [os.path.join(PKG, "csrc", "comm.cpp")]
-COMM_HDR = [os.path.join(ROOT, "include", "kwok_comm.h"), os.path.join(ROOT, "include", "kwok_engine.h"), ERR_HDR]
+COMM_HDR = [os.path.join(ROOT, "include", "kwok_comm.h"), os.path.join(ROOT, "include", "kwok_engine.h"), ERR_HDR, MEM_HDR]
 COMM_OUT = os.path.join(PKG, "lib", "libkwok_comm.so")
 EMIT_SRC = [os.path.join(PKG, "csrc", "emit.hip")]
 EMIT_HDR = [os.path.join(ROOT, "include", "kwok_emit.h"), os.path.join(ROOT, "include", "kwok_engine.h"),
-            os.path.join(PKG, "csrc", "timefmt.hpp"), ERR_HDR]
+            os.path.join(PKG, "csrc", "timefmt.hpp"), ERR_HDR, MEM_HDR]
 EMIT_OUT = os.path.join(PKG, "lib", "libkwok_emit.so")
 EXPO_SRC = [os.path.join(PKG, "csrc", "expo.hip")]
 EXPO_HDR = [os.path.join(ROOT, "include", "kwok_expo.h"), os.path.join(ROOT, "include", "kwok_metrics.h"),
             os.path.join(ROOT, "include", "kwok_engine.h"), os.path.join(PKG, "csrc", "f64fmt.hpp"),
-            os.path.join(PKG, "csrc", "f64fmt_tables.hpp"), os.path.join(PKG, "csrc", "keycmp.hpp"), ERR_HDR]
+            os.path.join(PKG, "csrc", "f64fmt_tables.hpp"), os.path.join(PKG, "csrc", "keycmp.hpp"), ERR_HDR, MEM_HDR]
 EXPO_OUT = os.path.join(PKG, "lib", "libkwok_expo.so")
 ARCH = "gfx950"  # MI355X only
 

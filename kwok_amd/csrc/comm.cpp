@@ -11,16 +11,16 @@
 #include "../../include/kwok_comm.h"
 #include "../../include/kwok_engine.h"
 #include "errscope.hpp"
+#include "devmem.hpp"
 
 struct kwk_comm {
   int device = 0;
   int rank = 0, world = 1;
   ncclComm_t nccl = nullptr;
   hipStream_t stream = nullptr;
-  hipEvent_t done = nullptr;              // the last all-reduce on `stream`
-  std::vector<hipEvent_t> joins;          // one per engine stream joined
-  double* buf = nullptr;
-  uint64_t cap = 0;
+  Event done;                             // the last all-reduce on `stream`
+  std::vector<Event> joins;               // one per engine stream joined
+  DevBuf<double> buf;
   std::string err;
 };
 
@@ -72,7 +72,7 @@ kwk_status kwk_comm_init(const uint8_t id[KWK_COMM_ID_BYTES], int32_t rank, int3
     return fail(KWK_EHIP, std::string("ncclCommInitRank: ") + ncclGetErrorString(r));
   }
   if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(&c->done, hipEventDisableTiming) != hipSuccess) {
+      c->done.create(hipEventDisableTiming) != hipSuccess) {
     kwk_comm_destroy(c);
     return fail(KWK_EHIP, "stream / event creation");
   }
@@ -85,11 +85,8 @@ kwk_status kwk_comm_destroy(kwk_comm* c) {
   hipSetDevice(c->device);
   if (c->stream) hipStreamSynchronize(c->stream);
   if (c->nccl) ncclCommDestroy(c->nccl);
-  if (c->buf) hipFree(c->buf);
-  for (hipEvent_t e : c->joins) hipEventDestroy(e);
-  if (c->done) hipEventDestroy(c->done);
   if (c->stream) hipStreamDestroy(c->stream);
-  delete c;
+  delete c;  // the device is set and the stream idle: the buffer and the events go with the handle
   return KWK_OK;
 }
 
@@ -97,16 +94,16 @@ kwk_status kwk_comm_buffer(kwk_comm* c, uint64_t n, double** dev) {
   ErrScope es_(c ? &c->err : nullptr);
   if (!c || !dev) return fail(KWK_EINVAL, "null argument");
   HIP_OK(hipSetDevice(c->device));
-  if (n > c->cap) {
+  if (n > c->buf.size()) {
     HIP_OK(hipStreamSynchronize(c->stream));
-    if (c->buf) HIP_OK(hipFree(c->buf));
-    c->buf = nullptr;
-    HIP_OK(hipMalloc(&c->buf, 8 * n));
+    c->buf.reset();
+    DevBuf<double> buf;  // the communicator's once it is zeroed
+    HIP_OK(buf.alloc(n));
     // zeroed on the communicator's stream and complete on return: the engines write into the
     // buffer from their own non-blocking streams, which would not wait for a null-stream memset
-    HIP_OK(hipMemsetAsync(c->buf, 0, 8 * n, c->stream));
+    HIP_OK(hipMemsetAsync(buf, 0, 8 * n, c->stream));
     HIP_OK(hipStreamSynchronize(c->stream));
-    c->cap = n;
+    c->buf = std::move(buf);
   }
   *dev = c->buf;
   return KWK_OK;
@@ -115,12 +112,12 @@ kwk_status kwk_comm_buffer(kwk_comm* c, uint64_t n, double** dev) {
 kwk_status kwk_comm_allreduce(kwk_comm* c, uint64_t n, kwk_engine* const* engines, uint32_t n_engines) {
   ErrScope es_(c ? &c->err : nullptr);
   if (!c || (n_engines && !engines)) return fail(KWK_EINVAL, "null argument");
-  if (n > c->cap) return fail(KWK_EINVAL, "n beyond the communicator's buffer (kwk_comm_buffer)");
+  if (n > c->buf.size()) return fail(KWK_EINVAL, "n beyond the communicator's buffer (kwk_comm_buffer)");
   HIP_OK(hipSetDevice(c->device));
   while (c->joins.size() < n_engines) {
-    hipEvent_t e;
-    HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    c->joins.push_back(e);
+    Event e;
+    HIP_OK(e.create(hipEventDisableTiming));
+    c->joins.push_back(std::move(e));
   }
   std::vector<hipStream_t> streams(n_engines);
   for (uint32_t i = 0; i < n_engines; ++i) {  // the collective waits for every engine's queued work
@@ -130,7 +127,7 @@ kwk_status kwk_comm_allreduce(kwk_comm* c, uint64_t n, kwk_engine* const* engine
     HIP_OK(hipEventRecord(c->joins[i], streams[i]));
     HIP_OK(hipStreamWaitEvent(c->stream, c->joins[i], 0));
   }
-  if (n) NCCL_OK(ncclAllReduce(c->buf, c->buf, (size_t)n, ncclFloat64, ncclSum, c->nccl, c->stream));
+  if (n) NCCL_OK(ncclAllReduce(c->buf.get(), c->buf.get(), (size_t)n, ncclFloat64, ncclSum, c->nccl, c->stream));
   HIP_OK(hipEventRecord(c->done, c->stream));
   for (uint32_t i = 0; i < n_engines; ++i) HIP_OK(hipStreamWaitEvent(streams[i], c->done, 0));
   return KWK_OK;
@@ -139,7 +136,7 @@ kwk_status kwk_comm_allreduce(kwk_comm* c, uint64_t n, kwk_engine* const* engine
 kwk_status kwk_comm_read(kwk_comm* c, double* host_out, uint64_t n) {
   ErrScope es_(c ? &c->err : nullptr);
   if (!c || (n && !host_out)) return fail(KWK_EINVAL, "null argument");
-  if (n > c->cap) return fail(KWK_EINVAL, "n beyond the communicator's buffer");
+  if (n > c->buf.size()) return fail(KWK_EINVAL, "n beyond the communicator's buffer");
   HIP_OK(hipSetDevice(c->device));
   if (n) HIP_OK(hipMemcpyAsync(host_out, c->buf, 8 * n, hipMemcpyDeviceToHost, c->stream));
   HIP_OK(hipStreamSynchronize(c->stream));

@@ -35,6 +35,7 @@
 
 #include "../../include/kwok_emit.h"
 #include "errscope.hpp"
+#include "devmem.hpp"
 #include "timefmt.hpp"
 
 namespace {
@@ -1333,71 +1334,71 @@ struct kwk_emitter {
   int device = 0;
   uint32_t capacity = 0, n_columns = 0, max_tiles = 0, grid = 0, cus = 1;
   int write_occ[6] = {0, 0, 0, 0, 0, 0};  // resident blocks per CU of each write kernel variant (0: not asked yet)
-  Prog p{};
-  std::vector<void*> allocs;
+  Prog p{};  // the kernels' view of the program: its pointers alias the tables of `pm`
+  struct ProgMem {
+    DevBuf<uint32_t> stage_tpl_ptr, stride;
+    DevBuf<uint16_t> stage_tpl;
+    DevBuf<uint8_t> stage_delete, fresh;
+    DevBuf<int32_t> skel_of;
+    DevBuf<kwk_emit_skel> skels;
+    DevBuf<kwk_emit_piece> pieces;
+    DevBuf<char> lits;
+    DevBuf<uint8_t*> cols;
+  } pm;
   std::vector<uint32_t> stride;
-  std::vector<uint8_t*> cols;
-  uint64_t* d_words = nullptr;
-  uint32_t* d_tile_items = nullptr;
-  unsigned long long* d_tile_bytes = nullptr;
+  std::vector<DevBuf<uint8_t>> cols;
+  DevBuf<uint64_t> d_words;
+  DevBuf<uint32_t> d_tile_items;
+  DevBuf<unsigned long long> d_tile_bytes;
   // The output sets (kwk_emit_reserve_sets; one by default): emissions rotate through them, so
   // that the emissions of a fused group are enqueued back to back and all read afterwards
   struct OutSet {
-    unsigned long long* d_totals = nullptr;  // 8 words of d_totals_all
-    kwk_emit_item* d_items = nullptr;
-    uint64_t* d_offsets = nullptr;
-    char* d_out = nullptr;
+    unsigned long long* d_totals = nullptr;  // 8 words of d_totals_all (an alias, not owned)
+    DevBuf<kwk_emit_item> d_items;
+    DevBuf<uint64_t> d_offsets;
+    DevBuf<char> d_out;
     uint64_t cap_items = 0, cap_bytes = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    Event ev0, ev1;
     bool emitted = false;
     // the finalizer stream (kwk_emit_finalizers_load)
-    unsigned long long* d_fin_totals = nullptr;  // 8 words of d_fin_totals_all
-    kwk_emit_fin_item* d_fin_items = nullptr;
-    uint64_t* d_fin_offsets = nullptr;
-    char* d_fin_out = nullptr;
+    unsigned long long* d_fin_totals = nullptr;  // 8 words of d_fin_totals_all (an alias, not owned)
+    DevBuf<kwk_emit_fin_item> d_fin_items;
+    DevBuf<uint64_t> d_fin_offsets;
+    DevBuf<char> d_fin_out;
     uint64_t fin_cap_items = 0, fin_cap_bytes = 0;
   };
   std::vector<OutSet> sets;
   uint32_t cur = 0;               // the set of the last emission
   uint32_t n_emitted = 0;         // emissions since the sets were made (kwk_emit_select's range)
   uint32_t sel = 0;               // the readers' emission: `sel` before the last
-  unsigned long long* d_totals_all = nullptr;
-  uint32_t* d_sticky = nullptr;   // device flag: an emission in flight exceeded its set
-  uint32_t* d_zero = nullptr;     // a zero length word (a ring list of no segments is empty)
+  DevBuf<unsigned long long> d_totals_all;
+  DevBuf<uint32_t> d_sticky;      // device flag: an emission in flight exceeded its set; two words:
+  uint32_t* d_zero = nullptr;     // its second, a zero length word (a ring list of no segments is empty; an alias)
   bool sticky_armed = false;      // an emission that may set d_sticky was enqueued since it was cleared
   bool saw_cap = false;           // the host has read KWK_ECAP: the next emission clears d_sticky
-  uint32_t* d_seg_base = nullptr; // the 2-byte source's segment bases (n_segs + 1) ...
-  uint32_t seg_cap = 0;
-  uint32_t* d_tile_seg = nullptr; // ... and every tile's first segment (max_tiles + 1)
+  DevBuf<uint32_t> d_seg_base;    // the 2-byte source's segment bases (n_segs + 1) ...
+  DevBuf<uint32_t> d_tile_seg;    // ... and every tile's first segment (max_tiles + 1)
   OutSet& selected() { return sets[(cur + (uint32_t)sets.size() - sel) % (uint32_t)sets.size()]; }
   bool chunk_ok = false;          // skeletons own consecutive, disjoint piece ranges (the chunk writer's templates)
   bool lencache = false;          // words' bits 24-31 cache the value lengths (emit_lens_kernel)
   bool fin = false;               // a finalizer program is loaded: every emission also emits its stream
   bool fin_any = false;           // ... and some stage of it has KWK_NEXT_FIN (else its launches are skipped)
-  FinArgs f{};                    // its device tables, order words and tile arrays
-  unsigned long long* d_fin_totals_all = nullptr;
+  FinArgs f{};                    // the kernels' view of it: its pointers alias `fm`
+  struct FinMem {                 // its device tables, order words and tile arrays
+    DevBuf<uint4> stages;
+    DevBuf<uint32_t> lit, lits, words, tile_items;
+    DevBuf<unsigned long long> tile_bytes;
+  } fm;
+  DevBuf<unsigned long long> d_fin_totals_all;
   uint64_t fin_req_items = 0, fin_req_bytes = 0;  // kwk_emit_reserve_fin's room, given to every set
   uint64_t tpl_lits = 0;          // literal bytes of every skeleton's pieces
   uint32_t tpl_now_slots = 0;     // Now slots of every skeleton's pieces
 
+  // the device is set and the stream idle before the members free themselves
   ~kwk_emitter() {
     hipSetDevice(device);
     void* s = nullptr;
     if (eng && kwk_stream(eng, &s) == KWK_OK && s) hipStreamSynchronize(static_cast<hipStream_t>(s));
-    for (void* x : allocs) hipFree(x);
-    if (d_seg_base) hipFree(d_seg_base);
-    for (OutSet& o : sets) free_set(o);
-  }
-  static void free_set(OutSet& o) {
-    if (o.d_items) hipFree(o.d_items);
-    if (o.d_offsets) hipFree(o.d_offsets);
-    if (o.d_out) hipFree(o.d_out);
-    if (o.d_fin_items) hipFree(o.d_fin_items);
-    if (o.d_fin_offsets) hipFree(o.d_fin_offsets);
-    if (o.d_fin_out) hipFree(o.d_fin_out);
-    if (o.ev0) hipEventDestroy(o.ev0);
-    if (o.ev1) hipEventDestroy(o.ev1);
-    o = OutSet{};
   }
 };
 
@@ -1416,16 +1417,12 @@ kwk_status bind(kwk_emitter* em) {
 // host -> device copy ordered on the engine's stream (a pageable hipMemcpy on the null stream can
 // return with its DMA in flight, and the engine's non-blocking stream would not wait for it)
 kwk_status copy_in(kwk_emitter* em, void* dst, const void* src, size_t bytes) {
-  if (!bytes) return KWK_OK;
-  HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, em->stream));
-  HIP_TRY(hipStreamSynchronize(em->stream));
+  HIP_TRY(copy_in(em->stream, dst, src, bytes));
   return KWK_OK;
 }
 
 kwk_status copy_out(kwk_emitter* em, void* dst, const void* src, size_t bytes) {
-  if (!bytes) return KWK_OK;
-  HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, em->stream));
-  HIP_TRY(hipStreamSynchronize(em->stream));
+  HIP_TRY(copy_out(em->stream, dst, src, bytes));
   return KWK_OK;
 }
 
@@ -1435,13 +1432,12 @@ kwk_status fill(kwk_emitter* em, void* dst, int v, size_t bytes) {
   return KWK_OK;
 }
 
-template <typename T>
-kwk_status upload(kwk_emitter* em, T** dst, const T* src, size_t n) {
-  void* d = nullptr;
-  HIP_TRY(hipMalloc(&d, std::max<size_t>(1, n) * sizeof(T)));
-  em->allocs.push_back(d);
-  if (kwk_status st = copy_in(em, d, src, n * sizeof(T))) return st;
-  *dst = static_cast<T*>(d);
+// makes `own` a device copy of n items, and *view (a kernel-argument alias) its address
+template <typename T, typename V>
+kwk_status upload(kwk_emitter* em, DevBuf<T>& own, V* view, const T* src, size_t n) {
+  HIP_TRY(own.alloc(std::max<size_t>(1, n)));
+  if (kwk_status st = copy_in(em, own, src, n * sizeof(T))) return st;
+  *view = own.get();
   return KWK_OK;
 }
 
@@ -1449,13 +1445,13 @@ constexpr uint32_t kMaxSets = 8;
 
 // n fresh output sets (the stream idle): the rotation starts over
 kwk_status make_sets(kwk_emitter* em, uint32_t n) {
-  for (kwk_emitter::OutSet& o : em->sets) kwk_emitter::free_set(o);
-  em->sets.assign(n, kwk_emitter::OutSet{});
+  em->sets.clear();
+  em->sets.resize(n);
   for (uint32_t i = 0; i < n; ++i) {
     em->sets[i].d_totals = em->d_totals_all + 8u * i;
     em->sets[i].d_fin_totals = em->d_fin_totals_all ? em->d_fin_totals_all + 8u * i : nullptr;
-    HIP_TRY(hipEventCreate(&em->sets[i].ev0));
-    HIP_TRY(hipEventCreate(&em->sets[i].ev1));
+    HIP_TRY(em->sets[i].ev0.create(hipEventDefault));
+    HIP_TRY(em->sets[i].ev1.create(hipEventDefault));
   }
   em->cur = n - 1u;
   em->n_emitted = 0;
@@ -1532,56 +1528,43 @@ kwk_status emitter_init(kwk_emitter* em, const kwk_emit_program* g) {
     em->chunk_ok = ok;
   }
   const uint32_t n_st = g->stage_tpl_ptr[g->n_stages];
-  if (kwk_status st = upload(em, const_cast<uint32_t**>(&em->p.stage_tpl_ptr), g->stage_tpl_ptr, g->n_stages + 1)) return st;
-  if (kwk_status st = upload(em, const_cast<uint16_t**>(&em->p.stage_tpl), g->stage_tpl, n_st)) return st;
-  if (kwk_status st = upload(em, const_cast<uint8_t**>(&em->p.stage_delete), g->stage_delete, g->n_stages)) return st;
-  if (kwk_status st = upload(em, const_cast<int32_t**>(&em->p.skel_of), g->skel_of, (size_t)g->n_classes * g->n_templates))
+  if (kwk_status st = upload(em, em->pm.stage_tpl_ptr, &em->p.stage_tpl_ptr, g->stage_tpl_ptr, g->n_stages + 1)) return st;
+  if (kwk_status st = upload(em, em->pm.stage_tpl, &em->p.stage_tpl, g->stage_tpl, n_st)) return st;
+  if (kwk_status st = upload(em, em->pm.stage_delete, &em->p.stage_delete, g->stage_delete, g->n_stages)) return st;
+  if (kwk_status st = upload(em, em->pm.skel_of, &em->p.skel_of, g->skel_of, (size_t)g->n_classes * g->n_templates))
     return st;
-  if (kwk_status st = upload(em, const_cast<kwk_emit_skel**>(&em->p.skels), g->skels, g->n_skels)) return st;
-  if (kwk_status st = upload(em, const_cast<kwk_emit_piece**>(&em->p.pieces), g->pieces, g->n_pieces)) return st;
+  if (kwk_status st = upload(em, em->pm.skels, &em->p.skels, g->skels, g->n_skels)) return st;
+  if (kwk_status st = upload(em, em->pm.pieces, &em->p.pieces, g->pieces, g->n_pieces)) return st;
   {  // the literal runs with 16 bytes of zero padding (the writers read aligned dword pairs)
     std::vector<char> lits(g->lits, g->lits + g->n_lit_bytes);
     lits.resize(lits.size() + 16, 0);
-    if (kwk_status st = upload(em, const_cast<char**>(&em->p.lits), lits.data(), lits.size())) return st;
+    if (kwk_status st = upload(em, em->pm.lits, &em->p.lits, lits.data(), lits.size())) return st;
   }
-  if (kwk_status st = upload(em, const_cast<uint8_t**>(&em->p.fresh), g->fresh_guards, g->n_classes)) return st;
+  if (kwk_status st = upload(em, em->pm.fresh, &em->p.fresh, g->fresh_guards, g->n_classes)) return st;
   em->n_columns = g->n_columns;
   em->stride.assign(g->column_stride, g->column_stride + g->n_columns);
   for (uint32_t c = 0; c < g->n_columns; ++c) {
-    void* d = nullptr;
-    HIP_TRY(hipMalloc(&d, (size_t)em->capacity * em->stride[c] + 16));  // + the dword a row's last read may touch
-    em->allocs.push_back(d);
-    if (kwk_status st = fill(em, d, 0xFF, (size_t)em->capacity * em->stride[c] + 16)) return st;  // unusable until set
-    em->cols.push_back(static_cast<uint8_t*>(d));
+    DevBuf<uint8_t> d;
+    HIP_TRY(d.alloc((size_t)em->capacity * em->stride[c] + 16));  // + the dword a row's last read may touch
+    if (kwk_status st = fill(em, d, 0xFF, d.size())) return st;  // unusable until set
+    em->cols.push_back(std::move(d));
   }
-  if (kwk_status st = upload(em, const_cast<uint8_t***>(&em->p.cols), em->cols.data(), em->cols.size())) return st;
-  if (kwk_status st = upload(em, const_cast<uint32_t**>(&em->p.stride), em->stride.data(), em->stride.size())) return st;
-  void* d = nullptr;
-  HIP_TRY(hipMalloc(&d, (size_t)std::max(1u, em->capacity) * 8));
-  em->allocs.push_back(d);
-  if (kwk_status st = fill(em, d, 0, (size_t)std::max(1u, em->capacity) * 8)) return st;  // class 0, nothing accepted: all to the host
-  em->d_words = static_cast<uint64_t*>(d);
+  const std::vector<uint8_t*> cols(em->cols.begin(), em->cols.end());
+  if (kwk_status st = upload(em, em->pm.cols, &em->p.cols, cols.data(), cols.size())) return st;
+  if (kwk_status st = upload(em, em->pm.stride, &em->p.stride, em->stride.data(), em->stride.size())) return st;
+  HIP_TRY(em->d_words.alloc(std::max(1u, em->capacity)));
+  if (kwk_status st = fill(em, em->d_words, 0, em->d_words.size() * 8)) return st;  // class 0, nothing accepted: all to the host
   em->lencache = g->n_columns <= 2;
   for (uint32_t c = 0; c < g->n_columns; ++c) em->lencache = em->lencache && g->column_stride[c] == 16u;
   em->max_tiles = (em->capacity + kTile - 1) / kTile + 1;
-  HIP_TRY(hipMalloc(&d, (size_t)em->max_tiles * 4));
-  em->allocs.push_back(d);
-  em->d_tile_items = static_cast<uint32_t*>(d);
-  HIP_TRY(hipMalloc(&d, (size_t)em->max_tiles * 8));
-  em->allocs.push_back(d);
-  em->d_tile_bytes = static_cast<unsigned long long*>(d);
-  HIP_TRY(hipMalloc(&d, kMaxSets * 8 * 8));
-  em->allocs.push_back(d);
-  em->d_totals_all = static_cast<unsigned long long*>(d);
-  if (kwk_status st = fill(em, d, 0, kMaxSets * 8 * 8)) return st;
-  HIP_TRY(hipMalloc(&d, 2 * 4));
-  em->allocs.push_back(d);
-  em->d_sticky = static_cast<uint32_t*>(d);
+  HIP_TRY(em->d_tile_items.alloc(em->max_tiles));
+  HIP_TRY(em->d_tile_bytes.alloc(em->max_tiles));
+  HIP_TRY(em->d_totals_all.alloc(kMaxSets * 8));
+  if (kwk_status st = fill(em, em->d_totals_all, 0, kMaxSets * 8 * 8)) return st;
+  HIP_TRY(em->d_sticky.alloc(2));
   em->d_zero = em->d_sticky + 1;
-  if (kwk_status st = fill(em, d, 0, 2 * 4)) return st;
-  HIP_TRY(hipMalloc(&d, ((size_t)em->max_tiles + 1) * 4));
-  em->allocs.push_back(d);
-  em->d_tile_seg = static_cast<uint32_t*>(d);
+  if (kwk_status st = fill(em, em->d_sticky, 0, 2 * 4)) return st;
+  HIP_TRY(em->d_tile_seg.alloc((size_t)em->max_tiles + 1));
   if (kwk_status st = make_sets(em, 1)) return st;
   int cus = 0;
   HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, em->device));
@@ -1670,42 +1653,30 @@ kwk_status reserve_sets(kwk_emitter* em, uint32_t n_sets, uint32_t max_items, ui
     if (kwk_status st = make_sets(em, n_sets)) return st;
   for (kwk_emitter::OutSet& o : em->sets) {
     if (max_items > o.cap_items) {
-      if (o.d_items) HIP_TRY(hipFree(o.d_items));
-      if (o.d_offsets) HIP_TRY(hipFree(o.d_offsets));
-      o.d_items = nullptr;
-      o.d_offsets = nullptr;
       o.cap_items = 0;
-      HIP_TRY(hipMalloc(&o.d_items, (size_t)max_items * sizeof(kwk_emit_item)));
-      HIP_TRY(hipMalloc(&o.d_offsets, ((size_t)max_items + 1) * 8));
+      HIP_TRY(o.d_items.alloc(max_items));
+      HIP_TRY(o.d_offsets.alloc((size_t)max_items + 1));
       o.cap_items = max_items;
     }
     if (max_bytes > o.cap_bytes) {
-      if (o.d_out) HIP_TRY(hipFree(o.d_out));
-      o.d_out = nullptr;
       o.cap_bytes = 0;
-      HIP_TRY(hipMalloc(&o.d_out, (size_t)max_bytes));
+      HIP_TRY(o.d_out.alloc((size_t)max_bytes));
       o.cap_bytes = max_bytes;
     }
   }
   if (em->fin) {  // the finalizer stream's room, in every set
     for (kwk_emitter::OutSet& o : em->sets) {
       if (em->fin_req_items > o.fin_cap_items || !o.d_fin_offsets) {
-        if (o.d_fin_items) HIP_TRY(hipFree(o.d_fin_items));
-        if (o.d_fin_offsets) HIP_TRY(hipFree(o.d_fin_offsets));
-        o.d_fin_items = nullptr;
-        o.d_fin_offsets = nullptr;
         o.fin_cap_items = 0;
         const size_t ni = (size_t)std::max<uint64_t>(1, em->fin_req_items);
-        HIP_TRY(hipMalloc(&o.d_fin_items, ni * sizeof(kwk_emit_fin_item)));
-        HIP_TRY(hipMalloc(&o.d_fin_offsets, (ni + 1) * 8));
+        HIP_TRY(o.d_fin_items.alloc(ni));
+        HIP_TRY(o.d_fin_offsets.alloc(ni + 1));
         o.fin_cap_items = ni;
       }
       if (em->fin_req_bytes > o.fin_cap_bytes || !o.d_fin_out) {
-        if (o.d_fin_out) HIP_TRY(hipFree(o.d_fin_out));
-        o.d_fin_out = nullptr;
         o.fin_cap_bytes = 0;
         const size_t nb = (size_t)std::max<uint64_t>(1, em->fin_req_bytes);
-        HIP_TRY(hipMalloc(&o.d_fin_out, nb + 16));
+        HIP_TRY(o.d_fin_out.alloc(nb + 16));
         o.fin_cap_bytes = nb;
       }
     }
@@ -1727,13 +1698,7 @@ kwk_status enqueue_emission(kwk_emitter* em, EmitArgs& a, int64_t now_ns) {
   if (em->fin && !em->sets[0].d_fin_offsets)
     if (kwk_status st = reserve_sets(em, (uint32_t)em->sets.size(), 0, 0)) return st;
   const bool src16 = a.p16 != nullptr;
-  if (src16 && a.n_segs + 1u > em->seg_cap) {
-    if (em->d_seg_base) HIP_TRY(hipFree(em->d_seg_base));  // (synchronises the device: no kernel still reads it)
-    em->d_seg_base = nullptr;
-    em->seg_cap = 0;
-    HIP_TRY(hipMalloc((void**)&em->d_seg_base, ((size_t)a.n_segs + 1u) * 4));
-    em->seg_cap = a.n_segs + 1u;
-  }
+  if (src16) HIP_TRY(em->d_seg_base.grow((size_t)a.n_segs + 1u));  // (its free synchronises the device: no kernel still reads it)
   const uint32_t n_sets = (uint32_t)em->sets.size();
   kwk_emitter::OutSet& o = em->sets[(em->cur + 1u) % n_sets];
   a.p = em->p;
@@ -2069,27 +2034,24 @@ kwk_status kwk_emit_finalizers_load(kwk_emitter* em, const kwk_emit_fin_program*
   memcpy(words.data(), bytes.data(), bytes.size());
   if (kwk_status st = bind(em)) return st;
   HIP_TRY(hipStreamSynchronize(em->stream));
+  em->fm = kwk_emitter::FinMem{};  // (what an earlier, failed load left: the stream is idle)
   FinArgs f{};
-  if (kwk_status st = upload(em, const_cast<uint4**>(&f.stages), stages.data(), stages.size())) return st;
-  if (kwk_status st = upload(em, const_cast<uint32_t**>(&f.lit), ent.data(), ent.size())) return st;
-  if (kwk_status st = upload(em, const_cast<uint32_t**>(&f.lits), words.data(), words.size())) return st;
+  if (kwk_status st = upload(em, em->fm.stages, &f.stages, stages.data(), stages.size())) return st;
+  if (kwk_status st = upload(em, em->fm.lit, &f.lit, ent.data(), ent.size())) return st;
+  if (kwk_status st = upload(em, em->fm.lits, &f.lits, words.data(), words.size())) return st;
   f.n_stages = g->n_stages;
   f.n_lit_words = (uint32_t)(bytes.size() / 4);
-  void* d = nullptr;
-  HIP_TRY(hipMalloc(&d, (size_t)std::max(1u, em->capacity) * 4));
-  em->allocs.push_back(d);
-  if (kwk_status st = fill(em, d, 0, (size_t)std::max(1u, em->capacity) * 4)) return st;
-  f.words = static_cast<uint32_t*>(d);
-  HIP_TRY(hipMalloc(&d, (size_t)em->max_tiles * 4));
-  em->allocs.push_back(d);
-  f.tile_items = static_cast<uint32_t*>(d);
-  HIP_TRY(hipMalloc(&d, (size_t)em->max_tiles * 8));
-  em->allocs.push_back(d);
-  f.tile_bytes = static_cast<unsigned long long*>(d);
-  HIP_TRY(hipMalloc(&d, kMaxSets * 8 * 8));
-  em->allocs.push_back(d);
-  if (kwk_status st = fill(em, d, 0, kMaxSets * 8 * 8)) return st;
-  em->d_fin_totals_all = static_cast<unsigned long long*>(d);
+  HIP_TRY(em->fm.words.alloc(std::max(1u, em->capacity)));
+  if (kwk_status st = fill(em, em->fm.words, 0, em->fm.words.size() * 4)) return st;
+  f.words = em->fm.words;
+  HIP_TRY(em->fm.tile_items.alloc(em->max_tiles));
+  f.tile_items = em->fm.tile_items;
+  HIP_TRY(em->fm.tile_bytes.alloc(em->max_tiles));
+  f.tile_bytes = em->fm.tile_bytes;
+  DevBuf<unsigned long long> totals;  // the emitter's once it is zeroed (make_sets looks at d_fin_totals_all)
+  HIP_TRY(totals.alloc(kMaxSets * 8));
+  if (kwk_status st = fill(em, totals, 0, kMaxSets * 8 * 8)) return st;
+  em->d_fin_totals_all = std::move(totals);
   for (size_t i = 0; i < em->sets.size(); ++i) em->sets[i].d_fin_totals = em->d_fin_totals_all + 8u * i;
   em->f = f;
   em->fin = true;

@@ -35,6 +35,7 @@
 #include "../../include/kwok_engine.h"
 #include "id8_compose.hpp"
 #include "errscope.hpp"
+#include "devmem.hpp"
 
 namespace {
 
@@ -4674,14 +4675,13 @@ struct kwk_engine {
   // kwk_step_n call, fused or not), hb[hb_cur] is the engine's last list (kwk_fired_read / _device), and a
   // compaction waits on the device only for the copy of the slot it rewrites.
   struct HbSlot {
-    void* list = nullptr;
-    size_t list_bytes = 0;
-    uint32_t* offsets = nullptr;
-    uint32_t* groups = nullptr;
-    uint32_t* tot = nullptr;
-    uint32_t* counts = nullptr;
-    hipEvent_t ev_copied = nullptr;  // the copy stream's last copy out of this slot
-    hipEvent_t ev_done = nullptr;    // kwk_fired_keep: recorded after the compaction that wrote the slot
+    DevBuf<void> list;
+    DevBuf<uint32_t> offsets;
+    DevBuf<uint32_t> groups;
+    DevBuf<uint32_t> tot;
+    DevBuf<uint32_t> counts;
+    Event ev_copied;                 // the copy stream's last copy out of this slot
+    Event ev_done;                   // kwk_fired_keep: recorded after the compaction that wrote the slot
     int done_slot = -1;              // ... the slot whose ev_done marks it (a fused group's last step)
     bool copy_pending = false;       // ev_copied recorded and not yet waited for by a compaction
     bool valid = false;
@@ -4692,19 +4692,19 @@ struct kwk_engine {
   std::vector<HbSlot> hb = std::vector<HbSlot>(kHbMin);
   uint32_t hb_cur = 0;
   bool hb_track = false;       // kwk_fired_keep: compactions record ev_done and write their length to h_len
-  uint32_t* h_len = nullptr;   // pinned, 2 words per slot (the kernels write them: host_len)
-  uint32_t* h_len_dev = nullptr;
+  HostBuf<uint32_t> h_len;     // pinned, 2 words per slot (the kernels write them: host_len)
+  uint32_t* h_len_dev = nullptr;  // h_len as the device sees it (an alias, not owned)
   uint64_t last_step_no = 0;   // the step number of the last sweep's (last) step
   hipStream_t copy_stream = nullptr;
-  hipEvent_t ev_count = nullptr;  // kwk_fired_fetch(KWK_STEP_LAST) without kwk_fired_keep: the length's copy
-  uint32_t* h_count = nullptr;
+  Event ev_count;                 // kwk_fired_fetch(KWK_STEP_LAST) without kwk_fired_keep: the length's copy
+  HostBuf<uint32_t> h_count;
   bool copy_recorded = false;  // a copy was enqueued (kwk_fired_fetch_wait)
   kwk_sweep_info last_sweep{};  // kwk_last_sweep
   bool loaded_table = false;
   uint32_t n_stages = 0, n_classes = 0;
   kwk_harness harness{};
 
-  void* d_st = nullptr;       // state word per slot (8-byte capacity; format in fmt)
+  DevBuf<void> d_st;          // state word per slot (8-byte capacity; format in fmt)
   StateFmt fmt{};             // current state format (wide until a table allows narrow)
   bool force_wide = false;
   bool allow_half = true;     // KWK_ENGINE_STATE32: never the 2-byte format
@@ -4716,8 +4716,8 @@ struct kwk_engine {
   bool agg_fused = true;      // KWK_TUNE_USAGE & KWK_USAGE_AGG_FUSED: kwk_aggregate's mask counts inside the usage kernel
   int n_cus = 256;
   std::vector<std::pair<const void*, int>> occupancy;  // blocks per CU per kernel (this engine's device)
-  uint32_t* d_fsm = nullptr;  // transition table of the 2-byte format (fsm_build_kernel)
-  int64_t* d_fsm_due = nullptr;
+  DevBuf<uint32_t> d_fsm;     // transition table of the 2-byte format (fsm_build_kernel)
+  DevBuf<int64_t> d_fsm_due;
   uint32_t fsm_bits = 0;
   int fsm_harness = -1;       // harness enable the table was built for (-1: no table)
   uint32_t fsm_kernel = kFsmKernelDefault;  // KWK_TUNE_SWEEP16 kernel: 0 never, else its prefetch depth
@@ -4732,123 +4732,120 @@ struct kwk_engine {
   std::vector<uint16_t> h_id2w;   // [256] word of each id
   std::vector<uint8_t> h_w2id;    // [65536] id of each half word (kIdInvalid: none)
   uint32_t id_fill[8] = {};       // ids used per class (need, pend, alive)
-  uint16_t* d_id2w = nullptr;
-  uint8_t* d_w2id = nullptr;
-  uint32_t* d_fsm8 = nullptr;     // [2][256] id transition table of sweep8_kernel
-  int64_t* d_fsm8_due = nullptr;
+  DevBuf<uint16_t> d_id2w;
+  DevBuf<uint8_t> d_w2id;
+  DevBuf<uint32_t> d_fsm8;        // [2][256] id transition table of sweep8_kernel
+  DevBuf<int64_t> d_fsm8_due;
   bool fsm8_due_any = false;      // some d_fsm8 entry schedules a delayed stage (kId8Due)
-  uint4* d_comp8 = nullptr;       // [2][256] composite rows of d_fsm8 for launches of 2 and of 4 fused steps
-  int64_t* d_due = nullptr;   // due time per slot
-  int64_t* d_del = nullptr;
-  uint32_t* d_rec = nullptr;
-  kwk_value* d_values = nullptr;
-  kwk_stage_table* d_table = nullptr;
-  uint32_t* d_lut = nullptr;  // kLutTables match masks (valid for lut_n entries)
+  DevBuf<uint4> d_comp8;          // [2][256] composite rows of d_fsm8 for launches of 2 and of 4 fused steps
+  DevBuf<int64_t> d_due;      // due time per slot
+  DevBuf<int64_t> d_del;
+  DevBuf<uint32_t> d_rec;
+  DevBuf<kwk_value> d_values;
+  DevBuf<kwk_stage_table> d_table;
+  DevBuf<uint32_t> d_lut;     // kLutTables match masks (valid for lut_n entries)
   uint32_t lut_n = 0, lut_bytes = 0, lut_rest = 0;
-  kwk_delta* d_deltas = nullptr;
-  kwk_fired_rec* d_fired = nullptr;
+  DevBuf<kwk_delta> d_deltas;
+  DevBuf<kwk_fired_rec> d_fired;
   // up to fuse_steps steps per 1-byte sweep launch (KWK_TUNE_FUSE_STEPS, sweep8_kernel<..., kSteps>):
   // steps 1.. segments and counts, rotated with d_fired / d_wave_counts by the steps' hand-backs
   uint32_t fuse_steps = kMaxFuseSteps;
-  kwk_fired_rec* d_firedx[kMaxFuseSteps - 1] = {};
-  uint32_t* d_countsx[kMaxFuseSteps - 1] = {};
-  uint32_t* d_wave_counts = nullptr;
+  DevBuf<kwk_fired_rec> d_firedx[kMaxFuseSteps - 1];
+  DevBuf<uint32_t> d_countsx[kMaxFuseSteps - 1];
+  DevBuf<uint32_t> d_wave_counts;
   // the hand-back inside one-tile-per-block 2-byte sweeps (tail_handback, KWK_TUNE_TAIL_HANDBACK):
   // per block the launch's tag and fired count; the tag of the last such launch
-  unsigned long long* d_tail_status = nullptr;
+  DevBuf<unsigned long long> d_tail_status;
   uint32_t tail_seq = 0;
   bool tail_hb = true;
-  uint32_t* d_bits_wc = nullptr;      // ... its words per segment
-  uint32_t* d_bits_bsum = nullptr;    // ... its records per workgroup of bits_size_kernel
-  unsigned long long* d_cum = nullptr;
-  unsigned long long* d_stats = nullptr;
+  DevBuf<uint32_t> d_bits_wc;         // ... its words per segment
+  DevBuf<uint32_t> d_bits_bsum;       // ... its records per workgroup of bits_size_kernel
+  DevBuf<unsigned long long> d_cum;
+  DevBuf<unsigned long long> d_stats;
   uint64_t steps = 0;
 
   // usage
   uint32_t n_nodes = 0, n_usage_pods = 0;
-  uint32_t* d_node_ptr = nullptr;
-  uint32_t* d_ukey = nullptr;
-  uint8_t* d_ukey8 = nullptr;   // usage_fast_kernel<WB, true>: 1-byte key column (<= kUKeyDict distinct keys)
-  double2* d_kv = nullptr;      // {cpu, mem} per distinct key
+  DevBuf<uint32_t> d_node_ptr;
+  DevBuf<uint32_t> d_ukey;
+  DevBuf<uint8_t> d_ukey8;      // usage_fast_kernel<WB, true>: 1-byte key column (<= kUKeyDict distinct keys)
+  DevBuf<double2> d_kv;         // {cpu, mem} per distinct key
   uint32_t kv_n = 0;
-  double* d_cpu = nullptr;
-  double* d_mem = nullptr;
-  double* d_node_out = nullptr;
-  double* d_node_cum = nullptr;
-  int64_t* d_node_last = nullptr;
-  double* d_pod_out = nullptr;   // per pod {cpu, mem, cpu_cumulative, mem_cumulative} (kwk_usage_pods)
-  double* d_pod_cum = nullptr;
-  int64_t* d_pod_last = nullptr;
-  double* d_usage_part = nullptr;
-  double* d_cluster = nullptr;
-  double* d_agg = nullptr;        // kwk_aggregate's own output buffer
-  uint32_t* d_count_part = nullptr;  // count_kernel's per-block partial counts
-  unsigned long long* d_agg_counts = nullptr;
+  DevBuf<double> d_cpu;
+  DevBuf<double> d_mem;
+  DevBuf<double> d_node_out;
+  DevBuf<double> d_node_cum;
+  DevBuf<int64_t> d_node_last;
+  DevBuf<double> d_pod_out;      // per pod {cpu, mem, cpu_cumulative, mem_cumulative} (kwk_usage_pods)
+  DevBuf<double> d_pod_cum;
+  DevBuf<int64_t> d_pod_last;
+  DevBuf<double> d_usage_part;
+  DevBuf<double> d_cluster;
+  DevBuf<double> d_agg;           // kwk_aggregate's own output buffer
+  DevBuf<uint32_t> d_count_part;     // count_kernel's per-block partial counts
+  DevBuf<unsigned long long> d_agg_counts;
   uint32_t agg_masks[16] = {};    // the masks last copied to d_agg_masks (kMaxCountMasks)
   uint32_t agg_n_masks = 0;
-  uint32_t* d_agg_masks = nullptr;
-  double* d_podv = nullptr;       // usage_fast_kernel's pod values per (containers, value id)
+  DevBuf<uint32_t> d_agg_masks;
+  DevBuf<double> d_podv;          // usage_fast_kernel's pod values per (containers, value id)
   uint32_t podv_n = 0;
   uint32_t compact_small = 8192;  // KWK_TUNE_COMPACT_SMALL (kSmallSegs)
-  uint4* d_uchunk = nullptr;      // usage_kernel's chunks of whole nodes {first pod, end pod, first node, end node}
+  DevBuf<uint4> d_uchunk;         // usage_kernel's chunks of whole nodes {first pod, end pod, first node, end node}
   uint32_t n_uchunks = 0;
   // host copies of the usage configuration (per-container reads, metric scrapes)
   std::vector<uint32_t> h_node_ptr, h_ukey, h_mixed, h_ckeys, h_cptr;
   std::vector<double> h_cpu, h_mem;
   bool has_mixed_keys = false;
-  uint2* d_mixed = nullptr;       // {first, count} per mixed pod
-  uint32_t* d_ckeys = nullptr;
-  double* d_ccum = nullptr;       // per container of a mixed pod: {cpu, mem} integrators
-  uint32_t* d_mbase = nullptr;    // per pod: first integrator of its containers in d_ccum (mixed pods)
+  DevBuf<uint2> d_mixed;          // {first, count} per mixed pod
+  DevBuf<uint32_t> d_ckeys;
+  DevBuf<double> d_ccum;          // per container of a mixed pod: {cpu, mem} integrators
+  DevBuf<uint32_t> d_mbase;       // per pod: first integrator of its containers in d_ccum (mixed pods)
   std::vector<uint32_t> h_mbase;
-  uint32_t* d_cptr = nullptr;     // per pod: first container (metric scrapes)
+  DevBuf<uint32_t> d_cptr;        // per pod: first container (metric scrapes)
   // Metric CRD programs
-  kwk_metric_op* d_mops = nullptr;
+  DevBuf<kwk_metric_op> d_mops;
   std::vector<kwk_metric_desc> metrics;
   uint32_t metric_inputs_needed = 0;  // 1: some program reads creation times / started containers
-  int64_t* d_pod_created = nullptr;
-  int64_t* d_node_created = nullptr;
-  double* d_node_started = nullptr;
+  DevBuf<int64_t> d_pod_created;
+  DevBuf<int64_t> d_node_created;
+  DevBuf<double> d_node_started;
   double zero_time_unix_s = 0.0;
-  double* d_mout = nullptr;
-  size_t mout_cap = 0;
-  uint32_t* d_alive_bits = nullptr;  // kwk_metrics_series_device: a bit per pod slot of the last range
-  size_t alive_words = 0;
+  DevBuf<double> d_mout;
+  DevBuf<uint32_t> d_alive_bits;     // kwk_metrics_series_device: a bit per pod slot of the last range
   // histogram Metric programs (kwk_histograms_load)
-  kwk_metric_op* d_hops = nullptr;
-  kwk_metric_bucket* d_hbuckets = nullptr;
-  uint32_t* d_hkeys = nullptr;
-  double* d_hbounds = nullptr;
+  DevBuf<kwk_metric_op> d_hops;
+  DevBuf<kwk_metric_bucket> d_hbuckets;
+  DevBuf<uint32_t> d_hkeys;
+  DevBuf<double> d_hbounds;
   std::vector<HistDesc> hists;
   uint32_t hist_inputs_needed = 0;
-  uint64_t* d_hout = nullptr;
-  size_t hout_cap = 0;
+  DevBuf<uint64_t> d_hout;
 
   // staging for upserts
-  void* d_stage_buf = nullptr;
+  DevBuf<void> d_stage_buf;
   size_t stage_bytes = 0;
 
   // node leases (node engines only)
   bool lease_on = false;
   kwk_lease_params lease_cfg{};
-  kwk_lease* d_lease = nullptr;
-  uint8_t* d_lease_op = nullptr;
-  kwk_fired_rec* d_lease_ops = nullptr;
-  uint32_t* d_lease_nops = nullptr;   // [2]: API writes of the last lease step / zeroed for the next one
+  DevBuf<kwk_lease> d_lease;
+  DevBuf<uint8_t> d_lease_op;
+  DevBuf<kwk_fired_rec> d_lease_ops;
+  DevBuf<uint32_t> d_lease_nops;      // [2]: API writes of the last lease step / zeroed for the next one
   uint32_t lease_par = 0;               // d_lease_nops entry the next lease step counts into
   uint32_t lease_last = 0;              // entry of the last lease step (kwk_lease_ops)
   // kwk_tick_bind (pod engines): the node engine whose lease results the fused tick applies
   const kwk_engine* tick_nodes = nullptr;
   uint32_t tick_n_nodes = 0;
-  uint32_t* d_tick_ptr = nullptr;       // node_ptr on the device
-  hipEvent_t ev_lease = nullptr;        // node stream: the tick's lease step is done
-  hipEvent_t ev_podsync = nullptr;      // pod stream: the tick's pod sync has read the lease results
+  DevBuf<uint32_t> d_tick_ptr;          // node_ptr on the device
+  Event ev_lease;                       // node stream: the tick's lease step is done
+  Event ev_podsync;                     // pod stream: the tick's pod sync has read the lease results
   bool tick_pending = false;            // ev_podsync recorded by an earlier tick
   kwk_engine* tick_pods = nullptr;      // node engines: the pod engine of the last fused tick
-  unsigned long long* d_lease_stats = nullptr;
+  DevBuf<unsigned long long> d_lease_stats;
   uint64_t lease_steps = 0;
 
-  std::vector<hipEvent_t> events;
+  std::vector<Event> events;
   std::string err;            // message of the last failing call on this engine (kwk_last_error)
 };
 
@@ -4957,11 +4954,7 @@ static hipError_t upload(const kwk_engine* e, void* dst, const void* src, size_t
 }
 
 static kwk_status ensure_stage_buf(kwk_engine* e, size_t bytes) {
-  if (bytes <= e->stage_bytes) return KWK_OK;
-  if (e->d_stage_buf) HIP_TRY(hipFree(e->d_stage_buf));
-  e->d_stage_buf = nullptr;
-  HIP_TRY(hipMalloc(&e->d_stage_buf, bytes));
-  e->stage_bytes = bytes;
+  HIP_TRY(e->d_stage_buf.grow(bytes));
   return KWK_OK;
 }
 
@@ -5111,7 +5104,7 @@ static kwk_status dw_fold(kwk_engine* e, uint32_t first, uint32_t n) {
   if (!e->fmt.dw || n == 0) return KWK_OK;
   const uint32_t g = std::min((n + kBlock - 1) / kBlock, (uint32_t)e->n_cus * 32u);
   hipLaunchKernelGGL(dw_fold_kernel, dim3(g), dim3(kBlock), 0, e->stream,
-                     reinterpret_cast<uint2*>(e->d_st), e->d_due, first, n, e->fmt.epoch);
+                     reinterpret_cast<uint2*>(e->d_st.get()), e->d_due, first, n, e->fmt.epoch);
   HIP_TRY(hipGetLastError());
   return KWK_OK;
 }
@@ -5119,7 +5112,7 @@ static kwk_status dw_unfold(kwk_engine* e, uint32_t first, uint32_t n) {
   if (!e->fmt.dw || n == 0) return KWK_OK;
   const uint32_t g = std::min((n + kBlock - 1) / kBlock, (uint32_t)e->n_cus * 32u);
   hipLaunchKernelGGL(dw_unfold_kernel, dim3(g), dim3(kBlock), 0, e->stream,
-                     reinterpret_cast<const uint2*>(e->d_st), e->d_due, first, n, e->fmt.epoch);
+                     reinterpret_cast<const uint2*>(e->d_st.get()), e->d_due, first, n, e->fmt.epoch);
   HIP_TRY(hipGetLastError());
   return KWK_OK;
 }
@@ -5219,15 +5212,6 @@ extern "C" {
 
 const char* kwk_last_error(const kwk_engine* e) { return e ? e->err.c_str() : g_err.c_str(); }
 
-// ------------------------------------------------------------------ hand-back ring
-static void hb_free(kwk_engine::HbSlot& h) {
-  for (void* p : {h.list, (void*)h.offsets, (void*)h.groups, (void*)h.tot, (void*)h.counts})
-    if (p) hipFree(p);
-  for (hipEvent_t ev : {h.ev_copied, h.ev_done})
-    if (ev) hipEventDestroy(ev);
-  h = kwk_engine::HbSlot{};
-}
-
 kwk_status kwk_engine_create(const kwk_engine_desc* d, kwk_engine** out) {
   if (!d || !out) return fail(KWK_EINVAL, "null argument");
   if (d->capacity == 0) return fail(KWK_EINVAL, "capacity must be > 0");
@@ -5253,48 +5237,44 @@ kwk_status kwk_engine_create(const kwk_engine_desc* d, kwk_engine** out) {
   if (hipDeviceGetAttribute(&e->n_cus, hipDeviceAttributeMultiprocessorCount, e->device) != hipSuccess || e->n_cus <= 0)
     e->n_cus = 256;
   const size_t n_waves = (size_t)e->n_blocks_cap * kWavesPerBlock;
-#define ALLOC(p, bytes)                                                          \
-  do {                                                                           \
-    hipError_t er = hipMalloc((void**)&(p), (bytes));                            \
-    if (er != hipSuccess) {                                                      \
-      kwk_engine_destroy(e);                                                     \
-      return fail(KWK_EHIP, std::string("hipMalloc: ") + hipGetErrorString(er)); \
-    }                                                                            \
-  } while (0)
   // state words: 8 bytes per slot (wide), slots padded to the largest sweep tile so that whole
   // chunks / lines of the last tile stay inside the allocation
   const size_t st_slots = ((size_t)e->capacity + kBlock * kMaxObjPerThread - 1) / (kBlock * kMaxObjPerThread) *
                           (kBlock * kMaxObjPerThread);
-  ALLOC(e->d_st, sizeof(uint2) * st_slots);
-  ALLOC(e->d_due, sizeof(int64_t) * (size_t)e->capacity);
-  ALLOC(e->d_del, sizeof(int64_t) * (size_t)e->capacity);
-  ALLOC(e->d_rec, sizeof(uint32_t) * (size_t)e->capacity);
-  ALLOC(e->d_values, sizeof(kwk_value) * (size_t)e->max_records * e->value_slots);
-  ALLOC(e->d_table, sizeof(kwk_stage_table));
-  ALLOC(e->d_lut, sizeof(uint32_t) * kLutTables);
-  ALLOC(e->d_fired, sizeof(kwk_fired_rec) * ((size_t)e->n_blocks_cap * kBlock * kMinObjPerThread +
-                                              (size_t)kBlock * kMaxObjPerThread));
-  ALLOC(e->d_wave_counts, sizeof(uint32_t) * (n_waves + 1));
-  ALLOC(e->d_tail_status, sizeof(unsigned long long) * ((size_t)e->n_blocks_cap + 1));
-  ALLOC(e->d_bits_wc, sizeof(uint32_t) * (n_waves + 4));
-  ALLOC(e->d_bits_bsum, sizeof(uint32_t) * (n_waves / kSegsPerBlock + 4));
-  ALLOC(e->d_cum, sizeof(unsigned long long) * (size_t)e->n_blocks_cap * kStatWords);
-  ALLOC(e->d_stats, sizeof(unsigned long long) * kStatWords);
-  ALLOC(e->d_id2w, sizeof(uint16_t) * 256);
-  ALLOC(e->d_w2id, 65536);
-  ALLOC(e->d_fsm8, sizeof(uint32_t) * 512);
-  ALLOC(e->d_fsm8_due, sizeof(int64_t) * 512);
-  ALLOC(e->d_comp8, sizeof(uint4) * 512);
-  hipError_t er = hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking);
-  if (er != hipSuccess) { kwk_engine_destroy(e); return fail(KWK_EHIP, "hipStreamCreate"); }
-  hipMemsetAsync(e->d_st, 0, sizeof(uint2) * st_slots, e->stream);
-  hipMemsetAsync(e->d_due, 0, sizeof(int64_t) * (size_t)e->capacity, e->stream);
-  hipMemsetAsync(e->d_cum, 0, sizeof(unsigned long long) * (size_t)e->n_blocks_cap * kStatWords, e->stream);
-  hipMemsetAsync(e->d_wave_counts, 0, sizeof(uint32_t) * (n_waves + 1), e->stream);
-  hipMemsetAsync(e->d_tail_status, 0, sizeof(unsigned long long) * ((size_t)e->n_blocks_cap + 1), e->stream);
-#undef ALLOC
-  er = hipStreamSynchronize(e->stream);
-  if (er != hipSuccess) { kwk_engine_destroy(e); return fail(KWK_EHIP, hipGetErrorString(er)); }
+  auto init = [&]() -> kwk_status {
+    HIP_TRY(e->d_st.alloc(sizeof(uint2) * st_slots));
+    HIP_TRY(e->d_due.alloc(e->capacity));
+    HIP_TRY(e->d_del.alloc(e->capacity));
+    HIP_TRY(e->d_rec.alloc(e->capacity));
+    HIP_TRY(e->d_values.alloc((size_t)e->max_records * e->value_slots));
+    HIP_TRY(e->d_table.alloc(1));
+    HIP_TRY(e->d_lut.alloc(kLutTables));
+    HIP_TRY(e->d_fired.alloc((size_t)e->n_blocks_cap * kBlock * kMinObjPerThread + (size_t)kBlock * kMaxObjPerThread));
+    HIP_TRY(e->d_wave_counts.alloc(n_waves + 1));
+    HIP_TRY(e->d_tail_status.alloc((size_t)e->n_blocks_cap + 1));
+    HIP_TRY(e->d_bits_wc.alloc(n_waves + 4));
+    HIP_TRY(e->d_bits_bsum.alloc(n_waves / kSegsPerBlock + 4));
+    HIP_TRY(e->d_cum.alloc((size_t)e->n_blocks_cap * kStatWords));
+    HIP_TRY(e->d_stats.alloc(kStatWords));
+    HIP_TRY(e->d_id2w.alloc(256));
+    HIP_TRY(e->d_w2id.alloc(65536));
+    HIP_TRY(e->d_fsm8.alloc(512));
+    HIP_TRY(e->d_fsm8_due.alloc(512));
+    HIP_TRY(e->d_comp8.alloc(512));
+    if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) return fail(KWK_EHIP, "hipStreamCreate");
+    HIP_TRY(hipMemsetAsync(e->d_st, 0, sizeof(uint2) * st_slots, e->stream));
+    HIP_TRY(hipMemsetAsync(e->d_due, 0, sizeof(int64_t) * (size_t)e->capacity, e->stream));
+    HIP_TRY(hipMemsetAsync(e->d_cum, 0, sizeof(unsigned long long) * (size_t)e->n_blocks_cap * kStatWords, e->stream));
+    HIP_TRY(hipMemsetAsync(e->d_wave_counts, 0, sizeof(uint32_t) * (n_waves + 1), e->stream));
+    HIP_TRY(hipMemsetAsync(e->d_tail_status, 0, sizeof(unsigned long long) * ((size_t)e->n_blocks_cap + 1), e->stream));
+    const hipError_t er = hipStreamSynchronize(e->stream);
+    return er != hipSuccess ? fail(KWK_EHIP, hipGetErrorString(er)) : KWK_OK;
+  };
+  st = init();
+  if (st) {
+    kwk_engine_destroy(e);
+    return st;
+  }
   {
     std::lock_guard<std::mutex> lk(g_live_mu);
     g_live.insert(e);
@@ -5318,29 +5298,10 @@ kwk_status kwk_engine_destroy(kwk_engine* e) {
   hipSetDevice(e->device);
   if (e->stream) hipStreamSynchronize(e->stream);
   if (e->copy_stream) hipStreamSynchronize(e->copy_stream);
-  for (kwk_engine::HbSlot& h : e->hb) hb_free(h);
-  for (uint32_t i = 0; i + 1 < kMaxFuseSteps; ++i) {
-    if (e->d_firedx[i]) hipFree(e->d_firedx[i]);
-    if (e->d_countsx[i]) hipFree(e->d_countsx[i]);
-  }
-  void* ptrs[] = {                  e->d_bits_wc, e->d_bits_bsum, e->d_st, e->d_due, e->d_del, e->d_rec, e->d_values, e->d_table, e->d_lut, e->d_deltas, e->d_fired,
-                  e->d_wave_counts, e->d_tail_status, e->d_cum, e->d_stats,
-                  e->d_node_ptr, e->d_ukey, e->d_cpu, e->d_mem, e->d_node_out, e->d_node_cum, e->d_node_last,
-                  e->d_usage_part, e->d_cluster, e->d_uchunk, e->d_podv, e->d_agg, e->d_agg_counts, e->d_agg_masks, e->d_count_part, e->d_stage_buf, e->d_pod_out, e->d_pod_cum, e->d_pod_last,
-                  e->d_lease, e->d_lease_op, e->d_lease_ops, e->d_fsm, e->d_fsm_due, e->d_mixed, e->d_ckeys, e->d_ccum,
-                  e->d_mbase, e->d_cptr, e->d_mops, e->d_pod_created, e->d_node_created, e->d_node_started, e->d_mout, e->d_alive_bits,
-                  e->d_lease_nops, e->d_lease_stats, e->d_ukey8, e->d_kv, e->d_hops, e->d_hbuckets, e->d_hkeys,
-                  e->d_hbounds, e->d_hout, e->d_id2w, e->d_w2id, e->d_fsm8, e->d_fsm8_due, e->d_comp8};
-  for (void* p : ptrs) if (p) hipFree(p);
-  if (e->d_tick_ptr) hipFree(e->d_tick_ptr);
-  if (e->ev_lease) hipEventDestroy(e->ev_lease);
-  if (e->ev_podsync) hipEventDestroy(e->ev_podsync);
-  if (e->ev_count) hipEventDestroy(e->ev_count);
-  if (e->h_count) hipHostFree(e->h_count);
-  if (e->h_len) hipHostFree(e->h_len);
   if (e->copy_stream) hipStreamDestroy(e->copy_stream);
-  for (auto ev : e->events) hipEventDestroy(ev);
   if (e->stream) hipStreamDestroy(e->stream);
+  // last, with the device set and both streams idle: the members' destructors free every buffer,
+  // pinned buffer and event the engine owns
   delete e;
   return KWK_OK;
 }
@@ -5432,10 +5393,8 @@ kwk_status kwk_load_stages(kwk_engine* e, const kwk_stage_table* t, const kwk_de
     }
     HIP_TRY(upload(e, e->d_lut, lut.data(), sizeof(uint32_t) * e->lut_n));
   }
-  if (e->d_deltas) HIP_TRY(hipFree(e->d_deltas));
-  e->d_deltas = nullptr;
   const size_t nd = (size_t)(t->n_classes ? t->n_classes : 1) * (t->n_stages ? t->n_stages : 1);
-  HIP_TRY(hipMalloc(&e->d_deltas, sizeof(kwk_delta) * nd));
+  HIP_TRY(e->d_deltas.alloc(nd));
   if (deltas && t->n_stages) HIP_TRY(upload(e, e->d_deltas, deltas, sizeof(kwk_delta) * nd));
   else HIP_TRY(hipMemsetAsync(e->d_deltas, 0xFF, sizeof(kwk_delta) * nd, e->stream));
   e->n_stages = t->n_stages;
@@ -5565,7 +5524,7 @@ kwk_status kwk_load(kwk_engine* e, uint32_t n, const kwk_hot* hot, const int64_t
   if (n_records)
     HIP_TRY(upload(e, e->d_values, records, sizeof(kwk_value) * (size_t)n_records * e->value_slots));
   if (n < e->n_active)
-    HIP_TRY(hipMemsetAsync((char*)e->d_st + word_bytes(e->fmt) * n, 0, word_bytes(e->fmt) * (size_t)(e->n_active - n), e->stream));
+    HIP_TRY(hipMemsetAsync((char*)e->d_st.get() + word_bytes(e->fmt) * n, 0, word_bytes(e->fmt) * (size_t)(e->n_active - n), e->stream));
   e->n_active = n;
   return KWK_OK;
 }
@@ -5620,7 +5579,7 @@ static kwk_status scatter_rows(kwk_engine* e, uint32_t n, const uint32_t* slots,
   const size_t bytes = (size_t)n * (4 + sizeof(kwk_hot) + 8 + 4 + 2) + 64;
   if (kwk_status st = ensure_stage_buf(e, bytes)) return st;
   HIP_TRY(hipStreamSynchronize(e->stream));
-  char* p = (char*)e->d_stage_buf;
+  char* p = (char*)e->d_stage_buf.get();
   kwk_hot* s_hot = (kwk_hot*)p; p += sizeof(kwk_hot) * n;
   int64_t* s_del = (int64_t*)p; p += 8 * (size_t)n;
   uint32_t* s_slots = (uint32_t*)p; p += 4 * (size_t)n;
@@ -5632,7 +5591,7 @@ static kwk_status scatter_rows(kwk_engine* e, uint32_t n, const uint32_t* slots,
   HIP_TRY(upload(e, s_rec, rec, 4 * (size_t)n));
   HIP_TRY(upload(e, s_cls, cls, 2 * (size_t)n));
   if (max_slot + 1 > e->n_active) {
-    HIP_TRY(hipMemsetAsync((char*)e->d_st + word_bytes(e->fmt) * e->n_active, 0,
+    HIP_TRY(hipMemsetAsync((char*)e->d_st.get() + word_bytes(e->fmt) * e->n_active, 0,
                            word_bytes(e->fmt) * (size_t)(max_slot + 1 - e->n_active), e->stream));
     e->n_active = max_slot + 1;
   }
@@ -5654,7 +5613,7 @@ kwk_status kwk_delete(kwk_engine* e, uint32_t n, const uint32_t* slots) {
   HIP_TRY(hipStreamSynchronize(e->stream));
   HIP_TRY(upload(e, e->d_stage_buf, slots, 4 * (size_t)n));
   hipLaunchKernelGGL(delete_kernel, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, e->stream, e->d_st,
-                     e->fmt, (const uint32_t*)e->d_stage_buf, n);
+                     e->fmt, (const uint32_t*)e->d_stage_buf.get(), n);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(e->stream));
   return KWK_OK;
@@ -5685,7 +5644,7 @@ kwk_status kwk_retry(kwk_engine* e, int64_t now_ns, uint64_t seed, uint64_t step
   const size_t bytes = (size_t)n * (4 + sizeof(kwk_hot) + 2 + 2 + 4) + 64;
   if (kwk_status st = ensure_stage_buf(e, bytes)) return st;
   HIP_TRY(hipStreamSynchronize(e->stream));
-  char* p = (char*)e->d_stage_buf;
+  char* p = (char*)e->d_stage_buf.get();
   kwk_hot* s_hot = (kwk_hot*)p; p += sizeof(kwk_hot) * n;
   uint32_t* s_slots = (uint32_t*)p; p += 4 * (size_t)n;
   uint32_t* s_rc = (uint32_t*)p; p += 4 * (size_t)n;
@@ -5771,12 +5730,9 @@ static kwk_status build_fsm(kwk_engine* e) {
   const uint32_t bits = e->fmt.fshift + 5;
   if (bits > 16) return KWK_OK;
   if (e->fsm_bits != bits || !e->d_fsm) {
-    if (e->d_fsm) HIP_TRY(hipFree(e->d_fsm));
-    if (e->d_fsm_due) HIP_TRY(hipFree(e->d_fsm_due));
-    e->d_fsm = nullptr;
-    e->d_fsm_due = nullptr;
-    HIP_TRY(hipMalloc(&e->d_fsm, sizeof(uint32_t) * (2u << bits)));
-    HIP_TRY(hipMalloc(&e->d_fsm_due, sizeof(int64_t) * (2u << bits)));
+    e->d_fsm.reset();
+    HIP_TRY(e->d_fsm_due.alloc(2u << bits));
+    HIP_TRY(e->d_fsm.alloc(2u << bits));  // (the last: the test above looks at it)
     e->fsm_bits = bits;
   }
   SweepArgs a = sweep_args(e, 0, 0, 0, true);
@@ -6065,21 +6021,15 @@ static kwk_status hb_prepare(kwk_engine* e, uint32_t i, HbFmt mode, hipStream_t 
     h.copy_pending = false;
   }
   const size_t need = hb_list_bytes(e, mode);
-  if (h.list_bytes < need) {
-    if (h.list) HIP_TRY(hipFree(h.list));  // (synchronises the device: no copy or kernel still reads it)
-    h.list = nullptr;
-    h.list_bytes = 0;
-    HIP_TRY(hipMalloc(&h.list, need));
-    h.list_bytes = need;
-  }
+  HIP_TRY(h.list.grow(need));  // (its free synchronises the device: no copy or kernel still reads it)
   if (!h.offsets) {
     const size_t n_waves = (size_t)e->n_blocks_cap * kWavesPerBlock;
-    HIP_TRY(hipMalloc((void**)&h.offsets, sizeof(uint32_t) * (n_waves + 4)));
-    HIP_TRY(hipMalloc((void**)&h.groups, sizeof(uint32_t) * (n_waves / kScanGroup + 4)));
-    HIP_TRY(hipMalloc((void**)&h.tot, 64));
-    HIP_TRY(hipMalloc((void**)&h.counts, sizeof(uint32_t) * (n_waves + 4)));
+    HIP_TRY(h.offsets.alloc(n_waves + 4));
+    HIP_TRY(h.groups.alloc(n_waves / kScanGroup + 4));
+    HIP_TRY(h.tot.alloc(16));
+    HIP_TRY(h.counts.alloc(n_waves + 4));
   }
-  if (e->hb_track && !h.ev_done) HIP_TRY(hipEventCreateWithFlags(&h.ev_done, hipEventDisableTiming));
+  if (e->hb_track) HIP_TRY(h.ev_done.create(hipEventDisableTiming));
   return KWK_OK;
 }
 
@@ -6102,7 +6052,7 @@ static kwk_status hb_commit(kwk_engine* e, uint32_t i, uint64_t step, HbFmt mode
 
 static void hb_args(const kwk_engine* e, uint32_t i, HbFmt mode, CompactArgs& a) {
   const kwk_engine::HbSlot& h = e->hb[i];
-  a.out = reinterpret_cast<kwk_fired_rec*>(h.list);
+  a.out = reinterpret_cast<kwk_fired_rec*>(h.list.get());
   a.offsets = h.offsets;
   a.group_tot = h.groups;
   a.counts_out = mode == HbFmt::Packed16 ? h.counts : nullptr;
@@ -6192,7 +6142,7 @@ static kwk_status enqueue_compact(kwk_engine* e, HbFmt mode) {
   }
   CompactArgs4 c4;
   CompactArgs& a = c4.a[0];
-  a.fired32 = reinterpret_cast<const uint32_t*>(e->d_fired);
+  a.fired32 = reinterpret_cast<const uint32_t*>(e->d_fired.get());
   a.counts = e->d_wave_counts;
   hb_args(e, i, mode, a);
   if (mode == HbFmt::Packed16) {
@@ -6283,9 +6233,8 @@ static kwk_status step_group(kwk_engine* e, uint32_t m, int64_t now, int64_t dt,
   for (uint32_t i = 0; i + 1 < m; ++i) {
     if (e->d_firedx[i]) continue;
     const size_t n_waves = (size_t)e->n_blocks_cap * kWavesPerBlock;
-    HIP_TRY(hipMalloc((void**)&e->d_firedx[i], sizeof(kwk_fired_rec) * ((size_t)e->n_blocks_cap * kBlock * kMinObjPerThread +
-                                                                         (size_t)kBlock * kMaxObjPerThread)));
-    HIP_TRY(hipMalloc((void**)&e->d_countsx[i], sizeof(uint32_t) * (n_waves + 4)));
+    HIP_TRY(e->d_firedx[i].alloc((size_t)e->n_blocks_cap * kBlock * kMinObjPerThread + (size_t)kBlock * kMaxObjPerThread));
+    HIP_TRY(e->d_countsx[i].alloc(n_waves + 4));
   }
   if (ev_a >= 0)
     if (kwk_status st = kwk_event_record(e, (uint32_t)ev_a)) return st;
@@ -6301,7 +6250,7 @@ static kwk_status step_group(kwk_engine* e, uint32_t m, int64_t now, int64_t dt,
       if (kwk_status st = hb_prepare(e, hb_next(e, i + 1), HbFmt::Packed16, e->stream)) return st;
     for (uint32_t i = 0; i < m; ++i) {
       CompactArgs& a = c4.a[i];
-      a.fired32 = reinterpret_cast<const uint32_t*>(i ? e->d_firedx[i - 1] : e->d_fired);
+      a.fired32 = reinterpret_cast<const uint32_t*>((i ? e->d_firedx[i - 1] : e->d_fired).get());
       a.counts = i ? e->d_countsx[i - 1] : e->d_wave_counts;
       hb_args(e, hb_next(e, i + 1), HbFmt::Packed16, a);
     }
@@ -6405,22 +6354,23 @@ kwk_status kwk_fired_keep(kwk_engine* e, uint32_t depth) {
   if (e->copy_stream) HIP_TRY(hipStreamSynchronize(e->copy_stream));
   const uint32_t slots = depth > kHbMin ? depth : kHbMin;
   // the engine's last list stays the last (moved to slot 0 of the new ring)
-  kwk_engine::HbSlot cur = e->hb[e->hb_cur];
-  e->hb[e->hb_cur] = kwk_engine::HbSlot{};
-  for (kwk_engine::HbSlot& h : e->hb) hb_free(h);
-  e->hb.assign(slots, kwk_engine::HbSlot{});
+  kwk_engine::HbSlot cur = std::move(e->hb[e->hb_cur]);
+  e->hb.clear();  // (both streams are idle)
+  e->hb.resize(slots);
   cur.copy_pending = false;
-  e->hb[0] = cur;
+  e->hb[0] = std::move(cur);
   e->hb_cur = 0;
   e->hb_track = depth > 0;
   if (e->hb_track && !e->h_len) {
-    HIP_TRY(hipHostMalloc((void**)&e->h_len, 2 * sizeof(uint32_t) * kHbMax, hipHostMallocDefault));
+    HIP_TRY(e->h_len.alloc(2 * kHbMax));
     memset(e->h_len, 0, 2 * sizeof(uint32_t) * kHbMax);
-    HIP_TRY(hipHostGetDevicePointer((void**)&e->h_len_dev, e->h_len, 0));
+    void* dev = nullptr;
+    HIP_TRY(hipHostGetDevicePointer(&dev, e->h_len, 0));
+    e->h_len_dev = static_cast<uint32_t*>(dev);
   }
   e->hb[0].done_slot = 0;
   if (e->hb_track && e->hb[0].offsets) {  // the current list's length where a fetch reads it
-    if (!e->hb[0].ev_done) HIP_TRY(hipEventCreateWithFlags(&e->hb[0].ev_done, hipEventDisableTiming));
+    HIP_TRY(e->hb[0].ev_done.create(hipEventDisableTiming));
     const bool bits = e->hb[0].mode == HbFmt::Bits;
     e->h_len[1] = 0u;
     HIP_TRY(hipMemcpy(e->h_len, bits ? e->hb[0].tot : e->hb[0].offsets, (bits ? 2 : 1) * sizeof(uint32_t),
@@ -6438,10 +6388,10 @@ static kwk_status hb_fetch(kwk_engine* e, uint32_t i, void* out, uint64_t cap_by
     int prio = 0;
     HIP_TRY(hipStreamGetPriority(e->stream, &prio));
     HIP_TRY(hipStreamCreateWithPriority(&e->copy_stream, hipStreamNonBlocking, prio));
-    HIP_TRY(hipEventCreateWithFlags(&e->ev_count, hipEventDisableTiming));
-    HIP_TRY(hipHostMalloc((void**)&e->h_count, 64, hipHostMallocDefault));
+    HIP_TRY(e->ev_count.create(hipEventDisableTiming));
+    HIP_TRY(e->h_count.alloc(16));
   }
-  if (!h.ev_copied) HIP_TRY(hipEventCreateWithFlags(&h.ev_copied, hipEventDisableTiming));
+  HIP_TRY(h.ev_copied.create(hipEventDisableTiming));
   const bool bits = h.mode == HbFmt::Bits, b16 = h.mode == HbFmt::Packed16;
   const uint32_t rb = hb_record_bytes(h.mode);
   const bool segs = b16 && seg_counts && h.n_segs;
@@ -6660,7 +6610,7 @@ kwk_status kwk_read(kwk_engine* e, uint32_t first, uint32_t n, kwk_hot* hot, int
   if (hot) {  // device SoA -> AoS interchange rows
     std::vector<uint8_t> raw(word_bytes(e->fmt) * (size_t)n);
     std::vector<int64_t> due(n);
-    HIP_TRY(hipMemcpy(raw.data(), (const char*)e->d_st + word_bytes(e->fmt) * first, raw.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(raw.data(), (const char*)e->d_st.get() + word_bytes(e->fmt) * first, raw.size(), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(due.data(), e->d_due + first, sizeof(int64_t) * n, hipMemcpyDeviceToHost));
     const std::vector<uint2> st = unpack_words(e, raw, e->fmt, n);
     if (e->fmt.dw) {  // D in the window, else the due column's value
@@ -6697,9 +6647,10 @@ kwk_status kwk_usage_config(kwk_engine* e, uint32_t n_nodes, const uint32_t* nod
   }
   if (kwk_status st = set_dev(e)) return st;
   HIP_TRY(hipStreamSynchronize(e->stream));
-  void* olds[] = {e->d_node_ptr, e->d_ukey, e->d_cpu, e->d_mem, e->d_node_out, e->d_node_cum, e->d_node_last,
-                  e->d_usage_part, e->d_cluster, e->d_uchunk};
-  for (void* p : olds) if (p) hipFree(p);
+  // the old configuration goes first; the engine has none until d_node_ptr is set again, at the end
+  // (the KWK_ESTATE guard of the usage calls, should a call below fail)
+  e->d_node_ptr.reset(), e->d_ukey.reset(), e->d_cpu.reset(), e->d_mem.reset(), e->d_node_out.reset();
+  e->d_node_cum.reset(), e->d_node_last.reset(), e->d_usage_part.reset(), e->d_cluster.reset(), e->d_uchunk.reset();
   // the usage kernels' chunks: whole nodes, at most kUChunkRows wave rows of pods (less the 8 of the
   // rounded start) and kUChunkNodes nodes each; a node with more pods than that gets a chunk of its
   // own (the wave carries its sum from row to row)
@@ -6713,7 +6664,7 @@ kwk_status kwk_usage_config(kwk_engine* e, uint32_t n_nodes, const uint32_t* nod
     n = nb;
   }
   const uint32_t ublocks = ((uint32_t)chunks.size() + kWavesPerBlock - 1) / kWavesPerBlock;
-  HIP_TRY(hipMalloc(&e->d_uchunk, sizeof(uint4) * (chunks.size() + 1)));
+  HIP_TRY(e->d_uchunk.alloc(chunks.size() + 1));
   if (!chunks.empty())
     HIP_TRY(upload(e, e->d_uchunk, chunks.data(), sizeof(uint4) * chunks.size()));
   e->n_uchunks = (uint32_t)chunks.size();
@@ -6721,12 +6672,7 @@ kwk_status kwk_usage_config(kwk_engine* e, uint32_t n_nodes, const uint32_t* nod
   // container by container (podResourceUsage's order, :170-193) — what usage_kernel's loop adds
   uint32_t max_nc = 0;
   for (uint32_t p = 0; p < n_pods; ++p) max_nc = (ukey[p] >> 28) > max_nc ? (ukey[p] >> 28) : max_nc;
-  if (e->d_podv) HIP_TRY(hipFree(e->d_podv));
-  if (e->d_ukey8) HIP_TRY(hipFree(e->d_ukey8));
-  if (e->d_kv) HIP_TRY(hipFree(e->d_kv));
-  e->d_podv = nullptr;
-  e->d_ukey8 = nullptr;
-  e->d_kv = nullptr;
+  e->d_podv.reset(), e->d_ukey8.reset(), e->d_kv.reset();
   e->podv_n = 0;
   e->kv_n = 0;
   const size_t nv = (size_t)n_cpu + n_mem;
@@ -6744,7 +6690,7 @@ kwk_status kwk_usage_config(kwk_engine* e, uint32_t n_nodes, const uint32_t* nod
         podv[nc * nv + n_cpu + i] = v;
       }
     }
-    HIP_TRY(hipMalloc(&e->d_podv, sizeof(double) * podv.size()));
+    HIP_TRY(e->d_podv.alloc(podv.size()));
     HIP_TRY(upload(e, e->d_podv, podv.data(), sizeof(double) * podv.size()));
     e->podv_n = (uint32_t)podv.size();
     // distinct keys -> 1-byte column + {cpu, mem} values (the same podv entries, so the sums are
@@ -6767,23 +6713,24 @@ kwk_status kwk_usage_config(kwk_engine* e, uint32_t n_nodes, const uint32_t* nod
         const uint32_t k = dict[d], row = (k >> 28) * (uint32_t)nv;
         kv[d] = make_double2(podv[row + (k & 0x3FFFu)], podv[row + n_cpu + ((k >> 14) & 0x3FFFu)]);
       }
-      HIP_TRY(hipMalloc(&e->d_ukey8, (size_t)n_pods + 16));
-      HIP_TRY(hipMalloc(&e->d_kv, sizeof(double2) * kv.size()));
+      HIP_TRY(e->d_ukey8.alloc((size_t)n_pods + 16));
+      HIP_TRY(e->d_kv.alloc(kv.size()));
       HIP_TRY(upload(e, e->d_ukey8, k8.data(), n_pods));
       HIP_TRY(upload(e, e->d_kv, kv.data(), sizeof(double2) * kv.size()));
       e->kv_n = (uint32_t)kv.size();
     }
   }
-  HIP_TRY(hipMalloc(&e->d_node_ptr, 4 * ((size_t)n_nodes + 1)));
-  HIP_TRY(hipMalloc(&e->d_ukey, 4 * ((size_t)n_pods + 1)));
-  HIP_TRY(hipMalloc(&e->d_cpu, 8 * (size_t)n_cpu));
-  HIP_TRY(hipMalloc(&e->d_mem, 8 * (size_t)n_mem));
-  HIP_TRY(hipMalloc(&e->d_node_out, 32 * ((size_t)n_nodes + 1)));
-  HIP_TRY(hipMalloc(&e->d_node_cum, 16 * ((size_t)n_nodes + 1)));
-  HIP_TRY(hipMalloc(&e->d_node_last, 8 * ((size_t)n_nodes + 1)));
-  HIP_TRY(hipMalloc(&e->d_usage_part, 16 * ((size_t)ublocks + 1)));
-  HIP_TRY(hipMalloc(&e->d_cluster, 16));
-  HIP_TRY(upload(e, e->d_node_ptr, node_ptr, 4 * ((size_t)n_nodes + 1)));
+  DevBuf<uint32_t> d_node_ptr;
+  HIP_TRY(d_node_ptr.alloc((size_t)n_nodes + 1));
+  HIP_TRY(e->d_ukey.alloc((size_t)n_pods + 1));
+  HIP_TRY(e->d_cpu.alloc(n_cpu));
+  HIP_TRY(e->d_mem.alloc(n_mem));
+  HIP_TRY(e->d_node_out.alloc(4 * ((size_t)n_nodes + 1)));
+  HIP_TRY(e->d_node_cum.alloc(2 * ((size_t)n_nodes + 1)));
+  HIP_TRY(e->d_node_last.alloc((size_t)n_nodes + 1));
+  HIP_TRY(e->d_usage_part.alloc(2 * ((size_t)ublocks + 1)));
+  HIP_TRY(e->d_cluster.alloc(2));
+  HIP_TRY(upload(e, d_node_ptr, node_ptr, 4 * ((size_t)n_nodes + 1)));
   HIP_TRY(upload(e, e->d_ukey, ukey, 4 * (size_t)n_pods));
   HIP_TRY(upload(e, e->d_cpu, cpu_values, 8 * (size_t)n_cpu));
   HIP_TRY(upload(e, e->d_mem, mem_values, 8 * (size_t)n_mem));
@@ -6802,15 +6749,10 @@ kwk_status kwk_usage_config(kwk_engine* e, uint32_t n_nodes, const uint32_t* nod
   e->h_mixed.clear();
   e->h_ckeys.clear();
   e->h_cptr.clear();
-  for (void* q : {(void*)e->d_mixed, (void*)e->d_ckeys, (void*)e->d_ccum, (void*)e->d_cptr, (void*)e->d_mbase})
-    if (q) HIP_TRY(hipFree(q));
-  e->d_mixed = nullptr;
-  e->d_ckeys = nullptr;
-  e->d_ccum = nullptr;
-  e->d_cptr = nullptr;
-  e->d_mbase = nullptr;
+  e->d_mixed.reset(), e->d_ckeys.reset(), e->d_ccum.reset(), e->d_cptr.reset(), e->d_mbase.reset();
   e->h_mbase.clear();
   if (e->d_pod_cum) HIP_TRY(hipMemsetAsync(e->d_pod_cum, 0, 16 * (size_t)e->capacity, e->stream));
+  e->d_node_ptr = std::move(d_node_ptr);
   return KWK_OK;
 }
 
@@ -6829,9 +6771,8 @@ kwk_status kwk_usage_mixed(kwk_engine* e, uint32_t n_mixed, const uint32_t* mixe
       return fail(KWK_EINVAL, "usage_key mixed index out of range");
   if (kwk_status st = set_dev(e)) return st;
   HIP_TRY(hipStreamSynchronize(e->stream));
-  for (void* q : {(void*)e->d_mixed, (void*)e->d_ckeys, (void*)e->d_ccum, (void*)e->d_cptr, (void*)e->d_mbase})
-    if (q) HIP_TRY(hipFree(q));
-  e->d_cptr = nullptr;
+  // (the engine has no mixed table until d_mixed is set again, at the end: the KWK_ESTATE guard)
+  e->d_mixed.reset(), e->d_ckeys.reset(), e->d_ccum.reset(), e->d_cptr.reset(), e->d_mbase.reset();
   e->h_cptr.clear();
   // integrators are per pod and container (mixed entries may be shared by pods whose containers
   // evaluate alike): each mixed pod's containers get their own range of ccum
@@ -6843,16 +6784,18 @@ kwk_status kwk_usage_mixed(kwk_engine* e, uint32_t n_mixed, const uint32_t* mixe
       nint += mixed[2 * (size_t)(e->h_ukey[p] & kUKeyMixedIndex) + 1];
       if (nint > 0xFFFFFFFFull) return fail(KWK_ECAP, "more than 2^32 containers of mixed pods");
     }
-  HIP_TRY(hipMalloc(&e->d_mixed, 8 * ((size_t)n_mixed + 1)));
-  HIP_TRY(hipMalloc(&e->d_ckeys, 4 * ((size_t)n_ckeys + 1)));
-  HIP_TRY(hipMalloc(&e->d_ccum, 16 * ((size_t)nint + 1)));
-  HIP_TRY(hipMalloc(&e->d_mbase, 4 * ((size_t)e->n_usage_pods + 1)));
-  if (n_mixed) HIP_TRY(upload(e, e->d_mixed, mixed, 8 * (size_t)n_mixed));
+  DevBuf<uint2> d_mixed;
+  HIP_TRY(d_mixed.alloc((size_t)n_mixed + 1));
+  HIP_TRY(e->d_ckeys.alloc((size_t)n_ckeys + 1));
+  HIP_TRY(e->d_ccum.alloc(2 * ((size_t)nint + 1)));
+  HIP_TRY(e->d_mbase.alloc((size_t)e->n_usage_pods + 1));
+  if (n_mixed) HIP_TRY(upload(e, d_mixed, mixed, 8 * (size_t)n_mixed));
   if (n_ckeys) HIP_TRY(upload(e, e->d_ckeys, ckeys, 4 * (size_t)n_ckeys));
   if (e->n_usage_pods) HIP_TRY(upload(e, e->d_mbase, e->h_mbase.data(), 4 * (size_t)e->n_usage_pods));
   HIP_TRY(hipMemsetAsync(e->d_ccum, 0, 16 * ((size_t)nint + 1), e->stream));
   e->h_mixed.assign(mixed, mixed + 2 * (size_t)n_mixed);
   e->h_ckeys.assign(ckeys, ckeys + n_ckeys);
+  e->d_mixed = std::move(d_mixed);
   return KWK_OK;
 }
 
@@ -6872,7 +6815,7 @@ static kwk_status ensure_cptr(kwk_engine* e) {
     if (c > 0xFFFFFFFFull) return fail(KWK_ECAP, "more than 2^32 containers");
   }
   e->h_cptr[e->n_usage_pods] = (uint32_t)c;
-  HIP_TRY(hipMalloc(&e->d_cptr, 4 * e->h_cptr.size()));
+  HIP_TRY(e->d_cptr.alloc(e->h_cptr.size()));
   HIP_TRY(upload(e, e->d_cptr, e->h_cptr.data(), 4 * e->h_cptr.size()));
   return KWK_OK;
 }
@@ -6899,7 +6842,7 @@ kwk_status kwk_usage_read_containers(kwk_engine* e, uint32_t first, uint32_t n, 
   if (kwk_status st = set_dev(e)) return st;
   HIP_TRY(hipStreamSynchronize(e->stream));
   std::vector<uint8_t> raw(word_bytes(e->fmt) * (size_t)n);
-  HIP_TRY(hipMemcpy(raw.data(), (const char*)e->d_st + word_bytes(e->fmt) * first, raw.size(), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(raw.data(), (const char*)e->d_st.get() + word_bytes(e->fmt) * first, raw.size(), hipMemcpyDeviceToHost));
   const std::vector<uint2> st = unpack_words(e, raw, e->fmt, n);
   std::vector<double> unit(2 * (size_t)n);
   HIP_TRY(hipMemcpy(unit.data(), e->d_pod_cum + 2 * (size_t)first, 16 * (size_t)n, hipMemcpyDeviceToHost));
@@ -7007,9 +6950,7 @@ kwk_status kwk_metrics_load(kwk_engine* e, uint32_t n_metrics, const kwk_metric_
       return st;
   if (kwk_status st = set_dev(e)) return st;
   HIP_TRY(hipStreamSynchronize(e->stream));
-  if (e->d_mops) HIP_TRY(hipFree(e->d_mops));
-  e->d_mops = nullptr;
-  HIP_TRY(hipMalloc(&e->d_mops, sizeof(kwk_metric_op) * ((size_t)n_ops + 1)));
+  HIP_TRY(e->d_mops.alloc((size_t)n_ops + 1));
   if (n_ops) HIP_TRY(upload(e, e->d_mops, ops, sizeof(kwk_metric_op) * n_ops));
   e->metrics.assign(metrics, metrics + n_metrics);
   e->metric_inputs_needed = needs;
@@ -7023,18 +6964,20 @@ kwk_status kwk_metrics_inputs(kwk_engine* e, const int64_t* pod_created, const i
   if (!e->d_node_ptr) return fail(KWK_ESTATE, "kwk_usage_config must be called first");
   if (kwk_status st = set_dev(e)) return st;
   HIP_TRY(hipStreamSynchronize(e->stream));
-  for (void* q : {(void*)e->d_pod_created, (void*)e->d_node_created, (void*)e->d_node_started})
-    if (q) HIP_TRY(hipFree(q));
-  HIP_TRY(hipMalloc(&e->d_pod_created, 8 * ((size_t)e->n_usage_pods + 1)));
-  HIP_TRY(hipMalloc(&e->d_node_created, 8 * ((size_t)e->n_nodes + 1)));
-  HIP_TRY(hipMalloc(&e->d_node_started, 8 * ((size_t)e->n_nodes + 1)));
+  // (the engine has no inputs until d_pod_created is set again, at the end: the KWK_ESTATE guard)
+  e->d_pod_created.reset(), e->d_node_created.reset(), e->d_node_started.reset();
+  DevBuf<int64_t> d_pod_created;
+  HIP_TRY(d_pod_created.alloc((size_t)e->n_usage_pods + 1));
+  HIP_TRY(e->d_node_created.alloc((size_t)e->n_nodes + 1));
+  HIP_TRY(e->d_node_started.alloc((size_t)e->n_nodes + 1));
   if (e->n_usage_pods)
-    HIP_TRY(upload(e, e->d_pod_created, pod_created, 8 * (size_t)e->n_usage_pods));
+    HIP_TRY(upload(e, d_pod_created, pod_created, 8 * (size_t)e->n_usage_pods));
   if (e->n_nodes) {
     HIP_TRY(upload(e, e->d_node_created, node_created, 8 * (size_t)e->n_nodes));
     HIP_TRY(upload(e, e->d_node_started, started, 8 * (size_t)e->n_nodes));
   }
   e->zero_time_unix_s = zero_time_unix_s;
+  e->d_pod_created = std::move(d_pod_created);
   return KWK_OK;
 }
 
@@ -7056,12 +6999,7 @@ static kwk_status enqueue_metrics(kwk_engine* e, int64_t now_ns, uint32_t node_f
     total += m.dimension == KWK_METRIC_DIM_NODE ? n_nodes : m.dimension == KWK_METRIC_DIM_POD ? (p1 - p0) : (c1 - c0);
   *n_out = total;
   if (!run || total == 0) return KWK_OK;
-  if (total > e->mout_cap) {
-    if (e->d_mout) HIP_TRY(hipFree(e->d_mout));
-    e->d_mout = nullptr;
-    HIP_TRY(hipMalloc(&e->d_mout, 8 * total));
-    e->mout_cap = total;
-  }
+  HIP_TRY(e->d_mout.grow(total));
   uint64_t off = 0;
   PodMetricList pl{};
   for (const auto& m : e->metrics) {
@@ -7136,13 +7074,9 @@ kwk_status kwk_metrics_series_device(kwk_engine* e, uint32_t node_first, uint32_
   if (kwk_status st = ensure_cptr(e)) return st;
   const uint32_t p0 = e->h_node_ptr[node_first], p1 = e->h_node_ptr[node_first + n_nodes];
   const size_t words = 2 * (((size_t)(p1 - p0) + 63) / 64) + 2;
-  if (words > e->alive_words) {
+  if (words > e->d_alive_bits.size()) {
     HIP_TRY(hipStreamSynchronize(e->stream));
-    if (e->d_alive_bits) HIP_TRY(hipFree(e->d_alive_bits));
-    e->d_alive_bits = nullptr;
-    e->alive_words = 0;
-    HIP_TRY(hipMalloc(&e->d_alive_bits, 4 * words));
-    e->alive_words = words;
+    HIP_TRY(e->d_alive_bits.alloc(words));
   }
   if (p1 > p0) {
     hipLaunchKernelGGL(alive_bits_kernel, dim3((p1 - p0 + kBlock - 1) / kBlock), dim3(kBlock), 0, e->stream, e->d_st, e->fmt,
@@ -7207,14 +7141,11 @@ kwk_status kwk_histograms_load(kwk_engine* e, uint32_t n_hist, const kwk_histogr
   }
   if (kwk_status st = set_dev(e)) return st;
   HIP_TRY(hipStreamSynchronize(e->stream));
-  for (void** q : {(void**)&e->d_hops, (void**)&e->d_hbuckets, (void**)&e->d_hkeys, (void**)&e->d_hbounds}) {
-    if (*q) HIP_TRY(hipFree(*q));
-    *q = nullptr;
-  }
-  HIP_TRY(hipMalloc(&e->d_hops, sizeof(kwk_metric_op) * ((size_t)n_ops + 1)));
-  HIP_TRY(hipMalloc(&e->d_hbuckets, sizeof(kwk_metric_bucket) * ((size_t)n_buckets + 1)));
-  HIP_TRY(hipMalloc(&e->d_hkeys, sizeof(uint32_t) * (keys.size() + 1)));
-  HIP_TRY(hipMalloc(&e->d_hbounds, sizeof(double) * (bounds.size() + 1)));
+  e->d_hops.reset(), e->d_hbuckets.reset(), e->d_hkeys.reset(), e->d_hbounds.reset();
+  HIP_TRY(e->d_hops.alloc((size_t)n_ops + 1));
+  HIP_TRY(e->d_hbuckets.alloc((size_t)n_buckets + 1));
+  HIP_TRY(e->d_hkeys.alloc(keys.size() + 1));
+  HIP_TRY(e->d_hbounds.alloc(bounds.size() + 1));
   if (n_ops) HIP_TRY(upload(e, e->d_hops, ops, sizeof(kwk_metric_op) * n_ops));
   if (n_buckets) HIP_TRY(upload(e, e->d_hbuckets, buckets, sizeof(kwk_metric_bucket) * n_buckets));
   if (!keys.empty()) HIP_TRY(upload(e, e->d_hkeys, keys.data(), sizeof(uint32_t) * keys.size()));
@@ -7242,12 +7173,7 @@ static kwk_status enqueue_histograms(kwk_engine* e, int64_t now_ns, uint32_t nod
     total += (uint64_t)metric_args(e, h.dim, now_ns, n0, n1, p0, p1, c0, n_nodes).n_series * h.out_words;
   *n_out = total;
   if (!run || total == 0) return KWK_OK;
-  if (total > e->hout_cap) {
-    if (e->d_hout) HIP_TRY(hipFree(e->d_hout));
-    e->d_hout = nullptr;
-    HIP_TRY(hipMalloc(&e->d_hout, 8 * total));
-    e->hout_cap = total;
-  }
+  HIP_TRY(e->d_hout.grow(total));
   uint64_t off = 0;
   for (const auto& h : e->hists) {
     MetricArgs a = metric_args(e, h.dim, now_ns, n0, n1, p0, p1, c0, n_nodes);
@@ -7353,20 +7279,18 @@ kwk_status kwk_usage_pods(kwk_engine* e, uint32_t enable) {
   if (!e) return fail(KWK_EINVAL, "null engine");
   if (kwk_status st = set_dev(e)) return st;
   HIP_TRY(hipStreamSynchronize(e->stream));
-  void* olds[] = {e->d_pod_out, e->d_pod_cum, e->d_pod_last};
-  for (void* p : olds) if (p) HIP_TRY(hipFree(p));
-  e->d_pod_out = nullptr;
-  e->d_pod_cum = nullptr;
-  e->d_pod_last = nullptr;
+  e->d_pod_out.reset(), e->d_pod_cum.reset(), e->d_pod_last.reset();
   if (!enable) return KWK_OK;
   const size_t n = e->capacity;
-  HIP_TRY(hipMalloc(&e->d_pod_out, 32 * n));
-  HIP_TRY(hipMalloc(&e->d_pod_cum, 16 * n));
-  HIP_TRY(hipMalloc(&e->d_pod_last, 8 * n));
-  HIP_TRY(hipMemsetAsync(e->d_pod_out, 0, 32 * n, e->stream));
+  DevBuf<double> d_pod_out;  // the engine's at the end: its presence turns the per-pod outputs on
+  HIP_TRY(d_pod_out.alloc(4 * n));
+  HIP_TRY(e->d_pod_cum.alloc(2 * n));
+  HIP_TRY(e->d_pod_last.alloc(n));
+  HIP_TRY(hipMemsetAsync(d_pod_out, 0, 32 * n, e->stream));
   HIP_TRY(hipMemsetAsync(e->d_pod_cum, 0, 16 * n, e->stream));
   std::vector<int64_t> lasts(n, INT64_MIN);
   HIP_TRY(upload(e, e->d_pod_last, lasts.data(), 8 * n));
+  e->d_pod_out = std::move(d_pod_out);
   return KWK_OK;
 }
 
@@ -7395,7 +7319,7 @@ kwk_status kwk_usage_read(kwk_engine* e, double* node_out, double* cluster_out) 
 // count_kernel's partial rows: at most n_cus * 32 blocks
 static kwk_status ensure_count_part(kwk_engine* e) {
   if (!e->d_count_part)
-    HIP_TRY(hipMalloc(&e->d_count_part, sizeof(uint32_t) * kMaxCountMasks * ((size_t)e->n_cus * 32u + 1)));
+    HIP_TRY(e->d_count_part.alloc(kMaxCountMasks * ((size_t)e->n_cus * 32u + 1)));
   return KWK_OK;
 }
 
@@ -7406,8 +7330,8 @@ kwk_status kwk_count(kwk_engine* e, uint32_t n_masks, const uint32_t* masks, uin
   if (n_masks == 0) return KWK_OK;
   if (kwk_status st = set_dev(e)) return st;
   if (kwk_status st = ensure_stage_buf(e, 4 * kMaxCountMasks + 8 * kMaxCountMasks)) return st;
-  uint32_t* d_masks = (uint32_t*)e->d_stage_buf;
-  unsigned long long* d_out = (unsigned long long*)((char*)e->d_stage_buf + 4 * kMaxCountMasks);
+  uint32_t* d_masks = (uint32_t*)e->d_stage_buf.get();
+  unsigned long long* d_out = (unsigned long long*)((char*)e->d_stage_buf.get() + 4 * kMaxCountMasks);
   HIP_TRY(hipMemcpyAsync(d_masks, masks, 4 * (size_t)n_masks, hipMemcpyHostToDevice, e->stream));
   HIP_TRY(hipMemsetAsync(d_out, 0, 8 * kMaxCountMasks, e->stream));
   if (e->n_active) {
@@ -7443,9 +7367,9 @@ kwk_status kwk_aggregate(kwk_engine* e, uint32_t n_masks, const uint32_t* masks,
   if (kwk_status st = set_dev(e)) return st;
   const uint32_t n_stages = e->loaded_table ? e->n_stages : 0u;
   if (!e->d_agg) {
-    HIP_TRY(hipMalloc(&e->d_agg, sizeof(double) * (KWK_MAX_STAGES + kMaxCountMasks + 2)));
-    HIP_TRY(hipMalloc(&e->d_agg_counts, sizeof(unsigned long long) * kMaxCountMasks));
-    HIP_TRY(hipMalloc(&e->d_agg_masks, sizeof(uint32_t) * kMaxCountMasks));
+    HIP_TRY(e->d_agg_counts.alloc(kMaxCountMasks));
+    HIP_TRY(e->d_agg_masks.alloc(kMaxCountMasks));
+    HIP_TRY(e->d_agg.alloc(KWK_MAX_STAGES + kMaxCountMasks + 2));  // (the last: the test above looks at it)
   }
   double* dst = out ? out : e->d_agg;
   // count_total_kernel overwrites the counts it produces: zeroed only when no count runs.  The
@@ -7523,15 +7447,17 @@ kwk_status kwk_lease_config(kwk_engine* e, const kwk_lease_params* cfg) {
   if (kwk_status st = set_dev(e)) return st;
   HIP_TRY(hipStreamSynchronize(e->stream));
   if (!e->d_lease) {
-    HIP_TRY(hipMalloc(&e->d_lease, sizeof(kwk_lease) * (size_t)e->capacity));
-    HIP_TRY(hipMalloc(&e->d_lease_op, (size_t)e->capacity));
-    HIP_TRY(hipMalloc(&e->d_lease_ops, sizeof(kwk_fired_rec) * (size_t)e->capacity));
-    HIP_TRY(hipMalloc(&e->d_lease_nops, 2 * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc(&e->d_lease_stats, sizeof(unsigned long long) * 5));
-    HIP_TRY(hipMemsetAsync(e->d_lease, 0, sizeof(kwk_lease) * (size_t)e->capacity, e->stream));
+    DevBuf<kwk_lease> d_lease;  // the engine's at the end: the test above looks at it
+    HIP_TRY(d_lease.alloc(e->capacity));
+    HIP_TRY(e->d_lease_op.alloc(e->capacity));
+    HIP_TRY(e->d_lease_ops.alloc(e->capacity));
+    HIP_TRY(e->d_lease_nops.alloc(2));
+    HIP_TRY(e->d_lease_stats.alloc(5));
+    HIP_TRY(hipMemsetAsync(d_lease, 0, sizeof(kwk_lease) * (size_t)e->capacity, e->stream));
     HIP_TRY(hipMemsetAsync(e->d_lease_op, 0, (size_t)e->capacity, e->stream));
     HIP_TRY(hipMemsetAsync(e->d_lease_nops, 0, 2 * sizeof(uint32_t), e->stream));
     HIP_TRY(hipMemsetAsync(e->d_lease_stats, 0, sizeof(unsigned long long) * 5, e->stream));
+    e->d_lease = std::move(d_lease);
   }
   e->lease_cfg = *cfg;
   e->lease_on = true;
@@ -7601,8 +7527,8 @@ kwk_status kwk_lease_fail(kwk_engine* e, int64_t now_ns, uint64_t seed, uint64_t
   if (kwk_status st = set_dev(e)) return st;
   if (kwk_status st = ensure_stage_buf(e, (size_t)n * (4 + sizeof(kwk_lease)) + 64)) return st;
   HIP_TRY(hipStreamSynchronize(e->stream));
-  kwk_lease* s_old = (kwk_lease*)e->d_stage_buf;
-  uint32_t* s_slots = (uint32_t*)((char*)e->d_stage_buf + sizeof(kwk_lease) * n);
+  kwk_lease* s_old = (kwk_lease*)e->d_stage_buf.get();
+  uint32_t* s_slots = (uint32_t*)((char*)e->d_stage_buf.get() + sizeof(kwk_lease) * n);
   HIP_TRY(upload(e, s_old, old, sizeof(kwk_lease) * n));
   HIP_TRY(upload(e, s_slots, slots, 4 * (size_t)n));
   LeaseArgs a;
@@ -7684,7 +7610,7 @@ kwk_status kwk_lease_sync_pods(kwk_engine* pods, const kwk_engine* nodes, uint32
   HIP_TRY(hipStreamSynchronize(nodes->stream));
   HIP_TRY(hipMemcpyAsync(pods->d_stage_buf, node_ptr, 4 * ((size_t)n_nodes + 1), hipMemcpyHostToDevice, pods->stream));
   hipLaunchKernelGGL(lease_pods_kernel, dim3((n_nodes + kWavesPerBlock - 1) / kWavesPerBlock), dim3(kBlock), 0,
-                     pods->stream, pods->d_st, pods->fmt, (const uint32_t*)pods->d_stage_buf, nodes->d_lease_op,
+                     pods->stream, pods->d_st, pods->fmt, (const uint32_t*)pods->d_stage_buf.get(), nodes->d_lease_op,
                      nodes->d_lease, nodes->lease_cfg.holder_id, n_nodes);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(pods->stream));
@@ -7704,12 +7630,10 @@ kwk_status kwk_tick_bind(kwk_engine* pods, const kwk_engine* nodes, uint32_t n_n
     if (node_ptr[j + 1] < node_ptr[j]) return fail(KWK_EINVAL, "node_ptr must be non-decreasing");
   if (kwk_status st = set_dev(pods)) return st;
   HIP_TRY(hipStreamSynchronize(pods->stream));
-  if (pods->d_tick_ptr) HIP_TRY(hipFree(pods->d_tick_ptr));
-  pods->d_tick_ptr = nullptr;
-  HIP_TRY(hipMalloc(&pods->d_tick_ptr, 4 * ((size_t)n_nodes + 1)));
+  HIP_TRY(pods->d_tick_ptr.alloc((size_t)n_nodes + 1));
   HIP_TRY(upload(pods, pods->d_tick_ptr, node_ptr, 4 * ((size_t)n_nodes + 1)));
-  if (!pods->ev_lease) HIP_TRY(hipEventCreateWithFlags(&pods->ev_lease, hipEventDisableTiming));
-  if (!pods->ev_podsync) HIP_TRY(hipEventCreateWithFlags(&pods->ev_podsync, hipEventDisableTiming));
+  HIP_TRY(pods->ev_lease.create(hipEventDisableTiming));
+  HIP_TRY(pods->ev_podsync.create(hipEventDisableTiming));
   pods->tick_nodes = nodes;
   pods->tick_n_nodes = n_nodes;
   pods->tick_pending = false;
@@ -7792,10 +7716,10 @@ kwk_status kwk_event_record(kwk_engine* e, uint32_t idx) {
   if (!e) return fail(KWK_EINVAL, "null engine");
   if (kwk_status st = set_dev(e)) return st;
   while (e->events.size() <= idx) {
-    hipEvent_t ev;
+    Event ev;
     // timing only: no system-scope release (its L2 write-back idled the stream ~5 us per marker)
-    HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableSystemFence));
-    e->events.push_back(ev);
+    HIP_TRY(ev.create(hipEventDisableSystemFence));
+    e->events.push_back(std::move(ev));
   }
   HIP_TRY(hipEventRecord(e->events[idx], e->stream));
   return KWK_OK;

@@ -57,6 +57,7 @@
 
 #include "../../include/kwok_expo.h"
 #include "errscope.hpp"
+#include "devmem.hpp"
 #include "f64fmt.hpp"
 #include "keycmp.hpp"
 
@@ -507,8 +508,8 @@ __global__ __launch_bounds__(kSortBlock) void expo_sort_kernel(const ArenaDev* _
 
 // a group's blocks or keys on the device: rows at any offset of one buffer, and what the host knows of it
 struct Arena {
-  char* d = nullptr;
-  uint2* d_ref = nullptr;
+  DevBuf<char> d;
+  DevBuf<uint2> d_ref;
   uint64_t size = 0, tail = 0;     // bytes allocated; the first free byte (tail + 8 <= size, both multiples of 8)
   std::vector<uint32_t> off, cap;  // per row: its slot
 };
@@ -519,12 +520,12 @@ struct Group {
   std::vector<uint32_t> dirty;            // rows set since the last commit of either kind
   std::vector<uint8_t> is_dirty;          // per row
   Arena blk, key;                         // key: groups with a permutation only
-  uint32_t* d_perm = nullptr;
+  DevBuf<uint32_t> d_perm;
 };
 
 struct Pending {  // device buffers replaced by an incremental commit: freed once the stream has passed `ev`
-  hipEvent_t ev;
-  std::vector<void*> ptrs;
+  Event ev;
+  std::vector<DevBuf<char>> bufs;
 };
 
 constexpr uint64_t kArenaMax = 0xFFFFFFF8ull;  // 32-bit offsets
@@ -538,41 +539,39 @@ struct kwk_expo {
   hipStream_t stream = nullptr;  // the engine's stream as of the current call (it may be re-created)
   int device = 0;
   uint32_t n_nodes = 0, n_pods = 0, n_cont = 0, width = 0;
-  uint4* d_stash = nullptr;
-  uint64_t stash_cap = 0;
+  DevBuf<uint4> d_stash;
   std::vector<DevFamily> fam;
   std::vector<DevHist> hist;  // of the histogram families' histograms (empty: a scalar-only program)
   uint32_t max_lines = 1;     // most lines of a series
   std::vector<Group> groups;
   std::vector<uint32_t> h_node_ptr, h_cptr;
-  DevFamily* d_fam = nullptr;
-  DevHist* d_hist = nullptr;
-  kwk_expo_hist_line* d_hlines = nullptr;
-  DevGroup* d_grp = nullptr;
-  char* d_lits = nullptr;
-  uint32_t* d_pod_of = nullptr;
-  unsigned long long* d_node_bytes = nullptr;
-  unsigned long long* d_offsets = nullptr;
-  unsigned long long* d_total = nullptr;
-  uint32_t cap_nodes = 0;
-  char* d_out = nullptr;
+  DevBuf<DevFamily> d_fam;
+  DevBuf<DevHist> d_hist;
+  DevBuf<kwk_expo_hist_line> d_hlines;
+  DevBuf<DevGroup> d_grp;
+  DevBuf<char> d_lits;
+  DevBuf<uint32_t> d_pod_of;
+  DevBuf<unsigned long long> d_node_bytes;
+  DevBuf<unsigned long long> d_offsets;
+  DevBuf<unsigned long long> d_total;
+  DevBuf<char> d_out;
   uint64_t cap_bytes = 0;
-  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  Event ev[5];
   bool committed = false, scraped = false;
   uint32_t last_nodes = 0;
   // incremental commits
   bool full = false;               // a full commit has laid the arenas out (and no later call left them half written)
   hipStream_t aux = nullptr;       // the layout totals are read here, beside the engine's stream
-  uint32_t* h_totals = nullptr;    // pinned: the device's node_ptr[n_nodes], cptr[n_pods]
-  char* h_stage = nullptr;         // pinned staging and its device copy
-  char* d_stage = nullptr;
-  uint64_t h_stage_cap = 0, d_stage_cap = 0;
-  hipEvent_t ev_stage = nullptr;   // the last copy out of h_stage
+  HostBuf<uint32_t> h_totals;     // pinned: the device's node_ptr[n_nodes], cptr[n_pods]
+  HostBuf<char> h_stage;           // pinned staging and its device copy
+  DevBuf<char> d_stage;
+  Event ev_stage;                  // the last copy out of h_stage
   bool stage_busy = false;
-  hipEvent_t ev_rows[3] = {nullptr, nullptr, nullptr};  // around the last commit's scatter and sort kernels
+  Event ev_rows[3];                // around the last commit's scatter and sort kernels
   bool rows_timed = false;
   std::vector<Pending> pending;
 
+  // the device is set and both streams are idle before the members free themselves
   ~kwk_expo() {
     hipSetDevice(device);
     void* s = nullptr;
@@ -581,24 +580,7 @@ struct kwk_expo {
       hipStreamSynchronize(aux);
       hipStreamDestroy(aux);
     }
-    for (Pending& p : pending) {
-      hipEventDestroy(p.ev);
-      for (void* q : p.ptrs) hipFree(q);
-    }
-    if (h_totals) hipHostFree(h_totals);
-    if (h_stage) hipHostFree(h_stage);
-    if (d_stage) hipFree(d_stage);
-    if (ev_stage) hipEventDestroy(ev_stage);
-    for (hipEvent_t e : ev_rows)
-      if (e) hipEventDestroy(e);
-    for (Group& g : groups)
-      for (void* p : {(void*)g.blk.d, (void*)g.blk.d_ref, (void*)g.key.d, (void*)g.key.d_ref, (void*)g.d_perm})
-        if (p) hipFree(p);
-    for (void* p : {(void*)d_fam, (void*)d_grp, (void*)d_lits, (void*)d_pod_of, (void*)d_node_bytes, (void*)d_offsets,
-                    (void*)d_total, (void*)d_out, (void*)d_stash, (void*)d_hist, (void*)d_hlines})
-      if (p) hipFree(p);
-    for (hipEvent_t e : ev)
-      if (e) hipEventDestroy(e);
+    pending.clear();  // the streams are idle
   }
 };
 
@@ -614,28 +596,20 @@ kwk_status bind(kwk_expo* ex) {
 
 // copies ordered on the engine's (non-blocking) stream
 kwk_status copy_in(kwk_expo* ex, void* dst, const void* src, size_t bytes) {
-  if (!bytes) return KWK_OK;
-  HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ex->stream));
-  HIP_TRY(hipStreamSynchronize(ex->stream));
+  HIP_TRY(copy_in(ex->stream, dst, src, bytes));
   return KWK_OK;
 }
 
 kwk_status copy_out(kwk_expo* ex, void* dst, const void* src, size_t bytes) {
-  if (!bytes) return KWK_OK;
-  HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ex->stream));
-  HIP_TRY(hipStreamSynchronize(ex->stream));
+  HIP_TRY(copy_out(ex->stream, dst, src, bytes));
   return KWK_OK;
 }
 
-// replaces *dst by a device copy of n items (the stream is idle: callers synchronise first)
+// makes dst a device copy of n items (the stream is idle: callers synchronise first)
 template <typename T>
-kwk_status replace(kwk_expo* ex, T** dst, const T* src, size_t n) {
-  if (*dst) HIP_TRY(hipFree(*dst));
-  *dst = nullptr;
-  void* d = nullptr;
-  HIP_TRY(hipMalloc(&d, std::max<size_t>(1, n) * sizeof(T)));
-  *dst = static_cast<T*>(d);
-  return copy_in(ex, d, src, n * sizeof(T));
+kwk_status upload(kwk_expo* ex, DevBuf<T>& dst, const T* src, size_t n) {
+  HIP_TRY(dst.alloc(std::max<size_t>(1, n)));
+  return copy_in(ex, dst, src, n * sizeof(T));
 }
 
 uint32_t group_rows(const kwk_expo* ex, uint32_t dim) {
@@ -664,17 +638,8 @@ kwk_status refresh_layout(kwk_expo* ex) {
 // frees what earlier incremental commits replaced, where the stream has passed their event
 // (all = true: the stream is idle)
 void drain_pending(kwk_expo* ex, bool all) {
-  size_t kept = 0;
-  for (Pending& p : ex->pending) {
-    if (all || hipEventQuery(p.ev) == hipSuccess) {
-      for (void* q : p.ptrs) hipFree(q);
-      hipEventDestroy(p.ev);
-    } else {
-      if (&ex->pending[kept] != &p) ex->pending[kept] = std::move(p);
-      ++kept;
-    }
-  }
-  ex->pending.resize(kept);
+  auto passed = [all](const Pending& p) { return all || hipEventQuery(p.ev) == hipSuccess; };
+  ex->pending.erase(std::remove_if(ex->pending.begin(), ex->pending.end(), passed), ex->pending.end());
 }
 
 // a full commit's layout of one arena: the set rows packed in row order, slack at the tail
@@ -698,15 +663,10 @@ kwk_status pack_arena(kwk_expo* ex, Arena& a, const std::vector<std::string>& it
   blob.reserve(a.tail + 8);
   for (const std::string& b : items) blob += b;
   blob.append(a.tail + 8 - total, '\0');  // read as 8-byte words
-  for (void* p : {(void*)a.d, (void*)a.d_ref})
-    if (p) HIP_TRY(hipFree(p));
-  a.d = nullptr;
-  a.d_ref = nullptr;
-  void* d = nullptr;
-  HIP_TRY(hipMalloc(&d, (size_t)a.size));
-  a.d = static_cast<char*>(d);
+  a.d_ref.reset();
+  HIP_TRY(a.d.alloc((size_t)a.size));
   if (kwk_status st = copy_in(ex, a.d, blob.data(), blob.size())) return st;
-  return replace(ex, &a.d_ref, ref.data(), ref.size());
+  return upload(ex, a.d_ref, ref.data(), ref.size());
 }
 
 }  // namespace
@@ -798,20 +758,20 @@ kwk_status create(kwk_engine* pods, uint32_t n_nodes, const kwk_expo_program* pr
     HIP_TRY(hipStreamGetDevice(ex->stream, &ex->device));
     if (kwk_status st = bind(ex)) return st;
     if (kwk_status st = refresh_layout(ex)) return st;
-    if (kwk_status st = replace(ex, &ex->d_fam, ex->fam.data(), ex->fam.size())) return st;
+    if (kwk_status st = upload(ex, ex->d_fam, ex->fam.data(), ex->fam.size())) return st;
     const std::string lits = std::string(prog->lits, prog->n_lit_bytes) + std::string(8, '\0');  // read as 8-byte words
-    if (kwk_status st = replace(ex, &ex->d_lits, lits.data(), lits.size())) return st;
+    if (kwk_status st = upload(ex, ex->d_lits, lits.data(), lits.size())) return st;
     if (!ex->hist.empty()) {
-      if (kwk_status st = replace(ex, &ex->d_hist, ex->hist.data(), ex->hist.size())) return st;
-      if (kwk_status st = replace(ex, &ex->d_hlines, hp->lines, (size_t)hp->n_lines)) return st;
+      if (kwk_status st = upload(ex, ex->d_hist, ex->hist.data(), ex->hist.size())) return st;
+      if (kwk_status st = upload(ex, ex->d_hlines, hp->lines, (size_t)hp->n_lines)) return st;
     }
-    HIP_TRY(hipMalloc(&ex->d_total, 16));
+    HIP_TRY(ex->d_total.alloc(2));
     HIP_TRY(hipMemsetAsync(ex->d_total, 0, 16, ex->stream));
-    for (hipEvent_t& e : ex->ev) HIP_TRY(hipEventCreate(&e));
-    for (hipEvent_t& e : ex->ev_rows) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipEventCreateWithFlags(&ex->ev_stage, hipEventDisableTiming));
+    for (Event& e : ex->ev) HIP_TRY(e.create(hipEventDefault));
+    for (Event& e : ex->ev_rows) HIP_TRY(e.create(hipEventDefault));
+    HIP_TRY(ex->ev_stage.create(hipEventDisableTiming));
     HIP_TRY(hipStreamCreateWithFlags(&ex->aux, hipStreamNonBlocking));
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&ex->h_totals), 8, hipHostMallocDefault));
+    HIP_TRY(ex->h_totals.alloc(2));
     return KWK_OK;
   };
   if (kwk_status st = init()) {
@@ -885,7 +845,7 @@ kwk_status kwk_expo_commit(kwk_expo* ex) {
   std::vector<uint32_t> pod_of(ex->n_cont);
   for (uint32_t p = 0; p < ex->n_pods; ++p)
     for (uint32_t c = ex->h_cptr[p]; c < ex->h_cptr[p + 1]; ++c) pod_of[c] = p;
-  if (kwk_status st = replace(ex, &ex->d_pod_of, pod_of.data(), pod_of.size())) return st;
+  if (kwk_status st = upload(ex, ex->d_pod_of, pod_of.data(), pod_of.size())) return st;
   std::vector<DevGroup> dg(ex->groups.size());
   for (size_t gi = 0; gi < ex->groups.size(); ++gi) {
     Group& g = ex->groups[gi];
@@ -903,13 +863,13 @@ kwk_status kwk_expo_commit(kwk_expo* ex) {
         std::stable_sort(perm.begin() + lo, perm.begin() + hi,
                          [&](uint32_t x, uint32_t y) { return g.keys[x] < g.keys[y]; });  // std::string: unsigned bytes
       }
-      if (kwk_status st = replace(ex, &g.d_perm, perm.data(), perm.size())) return st;
+      if (kwk_status st = upload(ex, g.d_perm, perm.data(), perm.size())) return st;
     }
     dg[gi] = DevGroup{g.blk.d_ref, g.blk.d, g.d_perm};
     g.is_dirty.assign(rows, 0);
     g.dirty.clear();
   }
-  if (kwk_status st = replace(ex, &ex->d_grp, dg.data(), dg.size())) return st;
+  if (kwk_status st = upload(ex, ex->d_grp, dg.data(), dg.size())) return st;
   ex->committed = true;
   ex->full = true;
   return KWK_OK;
@@ -1007,32 +967,23 @@ kwk_status kwk_expo_commit_rows(kwk_expo* ex) {
   const uint64_t rows_at = up8(grp_at + sizeof(DevGroup) * n_groups), segs_at = rows_at + sizeof(ScatterRow) * n_rows;
   const uint64_t bytes_at = up8(segs_at + sizeof(SortSeg) * segs.size()), stage_bytes = bytes_at + n_bytes;
 
-  Pending pend{nullptr, {}};
+  Pending pend;  // (a failed call frees it on return, after the stream has been synchronised)
   auto run = [&]() -> kwk_status {
     // the staging buffer is this call's once the last copy out of it is done
     if (ex->stage_busy) HIP_TRY(hipEventSynchronize(ex->ev_stage));
     ex->stage_busy = false;
-    if (stage_bytes > ex->h_stage_cap) {
-      if (ex->h_stage) HIP_TRY(hipHostFree(ex->h_stage));
-      ex->h_stage = nullptr;
-      ex->h_stage_cap = 0;
-      HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&ex->h_stage), (size_t)(stage_bytes + stage_bytes / 2), hipHostMallocDefault));
-      ex->h_stage_cap = stage_bytes + stage_bytes / 2;
-    }
-    if (stage_bytes > ex->d_stage_cap) {
-      if (ex->d_stage) pend.ptrs.push_back(ex->d_stage);
-      ex->d_stage = nullptr;
-      ex->d_stage_cap = 0;
-      HIP_TRY(hipMalloc(reinterpret_cast<void**>(&ex->d_stage), (size_t)(stage_bytes + stage_bytes / 2)));
-      ex->d_stage_cap = stage_bytes + stage_bytes / 2;
+    if (stage_bytes > ex->h_stage.size()) HIP_TRY(ex->h_stage.alloc((size_t)(stage_bytes + stage_bytes / 2)));
+    if (stage_bytes > ex->d_stage.size()) {
+      if (ex->d_stage) pend.bufs.push_back(std::move(ex->d_stage));
+      HIP_TRY(ex->d_stage.alloc((size_t)(stage_bytes + stage_bytes / 2)));
     }
     // an arena whose tail is full doubles: its rows keep their offsets
     for (const Grow& gr : grow) {
-      void* d = nullptr;
-      HIP_TRY(hipMalloc(&d, (size_t)gr.size));
+      DevBuf<char> d;
+      HIP_TRY(d.alloc((size_t)gr.size));
       HIP_TRY(hipMemcpyAsync(d, gr.a->d, (size_t)gr.a->tail + 8, hipMemcpyDeviceToDevice, ex->stream));
-      pend.ptrs.push_back(gr.a->d);
-      gr.a->d = static_cast<char*>(d);
+      pend.bufs.push_back(std::move(gr.a->d));
+      gr.a->d = std::move(d);
       gr.a->size = gr.size;
     }
     char* h = ex->h_stage;
@@ -1044,7 +995,7 @@ kwk_status kwk_expo_commit_rows(kwk_expo* ex) {
       Group& g = ex->groups[gi];
       tab[kArenas * gi + 0] = ArenaDev{g.blk.d, g.blk.d_ref};
       tab[kArenas * gi + 1] = ArenaDev{g.key.d, g.key.d_ref};
-      tab[kArenas * gi + 2] = ArenaDev{reinterpret_cast<char*>(g.d_perm), nullptr};
+      tab[kArenas * gi + 2] = ArenaDev{reinterpret_cast<char*>(g.d_perm.get()), nullptr};
       dgrp[gi] = DevGroup{g.blk.d_ref, g.blk.d, g.d_perm};
       for (uint32_t r : g.dirty) {
         for (uint32_t k = 0; k < 2; ++k) {
@@ -1093,11 +1044,10 @@ kwk_status kwk_expo_commit_rows(kwk_expo* ex) {
     }
     HIP_TRY(hipEventRecord(ex->ev_rows[2], ex->stream));
     ex->rows_timed = true;
-    if (!pend.ptrs.empty()) {
-      HIP_TRY(hipEventCreateWithFlags(&pend.ev, hipEventDisableTiming));
+    if (!pend.bufs.empty()) {
+      HIP_TRY(pend.ev.create(hipEventDisableTiming));
       HIP_TRY(hipEventRecord(pend.ev, ex->stream));
-      ex->pending.push_back(pend);
-      pend.ptrs.clear();
+      ex->pending.push_back(std::move(pend));
     }
     return KWK_OK;
   };
@@ -1105,8 +1055,6 @@ kwk_status kwk_expo_commit_rows(kwk_expo* ex) {
   if (st != KWK_OK) {  // the arenas may be half written: only a full commit makes them whole
     ex->full = ex->committed = false;
     hipStreamSynchronize(ex->stream);
-    if (pend.ev) hipEventDestroy(pend.ev);
-    for (void* q : pend.ptrs) hipFree(q);
     return st;
   }
   ex->committed = true;
@@ -1142,10 +1090,8 @@ kwk_status kwk_expo_reserve(kwk_expo* ex, uint64_t max_bytes) {
   if (!ex) return fail(KWK_EINVAL, "null writer");
   if (kwk_status st = bind(ex)) return st;
   HIP_TRY(hipStreamSynchronize(ex->stream));
-  if (ex->d_out) HIP_TRY(hipFree(ex->d_out));
-  ex->d_out = nullptr;
   ex->cap_bytes = 0;
-  HIP_TRY(hipMalloc(&ex->d_out, std::max<size_t>(8, (size_t)max_bytes)));
+  HIP_TRY(ex->d_out.alloc(std::max<size_t>(8, (size_t)max_bytes)));
   ex->cap_bytes = max_bytes;
   return KWK_OK;
 }
@@ -1166,15 +1112,10 @@ kwk_status kwk_expo_scrape(kwk_expo* ex, int64_t now_ns, uint32_t node_first, ui
   if (kwk_status st = bind(ex)) return st;
   if (!ex->d_out)
     if (kwk_status st = kwk_expo_reserve(ex, 0)) return st;
-  if (n_nodes + 1 > ex->cap_nodes) {
+  if ((size_t)n_nodes + 1 > ex->d_offsets.size()) {  // (allocated last of the two)
     HIP_TRY(hipStreamSynchronize(ex->stream));
-    if (ex->d_node_bytes) HIP_TRY(hipFree(ex->d_node_bytes));
-    if (ex->d_offsets) HIP_TRY(hipFree(ex->d_offsets));
-    ex->d_node_bytes = ex->d_offsets = nullptr;
-    ex->cap_nodes = 0;
-    HIP_TRY(hipMalloc(&ex->d_node_bytes, 8 * ((size_t)n_nodes + 1)));
-    HIP_TRY(hipMalloc(&ex->d_offsets, 8 * ((size_t)n_nodes + 1)));
-    ex->cap_nodes = n_nodes + 1;
+    HIP_TRY(ex->d_node_bytes.alloc((size_t)n_nodes + 1));
+    HIP_TRY(ex->d_offsets.alloc((size_t)n_nodes + 1));
   }
   HIP_TRY(hipEventRecord(ex->ev[0], ex->stream));
   ExpoArgs a{};
@@ -1226,13 +1167,9 @@ kwk_status kwk_expo_scrape(kwk_expo* ex, int64_t now_ns, uint32_t node_first, ui
                             "kwk_usage_config");
   const uint32_t width = ex->width ? ex->width : (n_nodes && (a.p1 - a.p0) / n_nodes > kWidePods) ? 256u : 64u;
   const uint64_t n_slots = n_vals + n_words;  // the histogram words' slots after the scalars'
-  if (n_slots > ex->stash_cap) {
+  if (n_slots > ex->d_stash.size() / 2) {  // a slot is two uint4
     HIP_TRY(hipStreamSynchronize(ex->stream));
-    if (ex->d_stash) HIP_TRY(hipFree(ex->d_stash));
-    ex->d_stash = nullptr;
-    ex->stash_cap = 0;
-    HIP_TRY(hipMalloc(&ex->d_stash, 32 * (size_t)n_slots));
-    ex->stash_cap = n_slots;
+    HIP_TRY(ex->d_stash.alloc(2 * (size_t)n_slots));
   }
   a.stash = ex->d_stash;
 #define KWK_EXPO_LAUNCH_H(WR, H)                                                                                    \
@@ -1287,7 +1224,7 @@ kwk_status kwk_expo_result(kwk_expo* ex, uint64_t* n_bytes) {
 kwk_status kwk_expo_device(kwk_expo* ex, const uint64_t** offsets, const char** bytes) {
   ErrScope es_(ex ? &ex->err : nullptr);
   if (!ex) return fail(KWK_EINVAL, "null writer");
-  if (offsets) *offsets = reinterpret_cast<const uint64_t*>(ex->d_offsets);
+  if (offsets) *offsets = reinterpret_cast<const uint64_t*>(ex->d_offsets.get());
   if (bytes) *bytes = ex->d_out;
   return KWK_OK;
 }
@@ -1317,13 +1254,13 @@ kwk_status kwk_expo_format_values(kwk_expo* ex, const double* host_values, uint3
   if (!ex || (n && (!host_values || !out || !lens))) return fail(KWK_EINVAL, "null argument");
   if (!n) return KWK_OK;
   if (kwk_status st = bind(ex)) return st;
-  double* d_v = nullptr;
-  char* d_o = nullptr;
-  uint8_t* d_l = nullptr;
+  DevBuf<double> d_v;
+  DevBuf<char> d_o;
+  DevBuf<uint8_t> d_l;
   auto run = [&]() -> kwk_status {
-    HIP_TRY(hipMalloc(&d_v, 8 * (size_t)n));
-    HIP_TRY(hipMalloc(&d_o, (size_t)kwkf64::kMaxBytes * n));
-    HIP_TRY(hipMalloc(&d_l, n));
+    HIP_TRY(d_v.alloc(n));
+    HIP_TRY(d_o.alloc((size_t)kwkf64::kMaxBytes * n));
+    HIP_TRY(d_l.alloc(n));
     if (kwk_status st = copy_in(ex, d_v, host_values, 8 * (size_t)n)) return st;
     HIP_TRY(hipMemsetAsync(d_o, 0, (size_t)kwkf64::kMaxBytes * n, ex->stream));
     hipLaunchKernelGGL(expo_format_kernel, dim3((n + kFmtBlock - 1) / kFmtBlock), dim3(kFmtBlock), 0, ex->stream, d_v, n, d_o,
@@ -1333,9 +1270,7 @@ kwk_status kwk_expo_format_values(kwk_expo* ex, const double* host_values, uint3
     return copy_out(ex, lens, d_l, n);
   };
   const kwk_status st = run();
-  hipStreamSynchronize(ex->stream);
-  for (void* p : {(void*)d_v, (void*)d_o, (void*)d_l})
-    if (p) hipFree(p);
+  hipStreamSynchronize(ex->stream);  // before the three buffers go
   return st;
 }
 
