@@ -503,7 +503,14 @@ kwk_status kwk_usage_read_containers(kwk_engine* eng, uint32_t first, uint32_t n
 #define KWK_MOP_MUL 5
 #define KWK_MOP_DIV 6
 #define KWK_MOP_NEG 7
-#define KWK_MIN_NOW_S 0               /* Now().UnixSecond() */
+/* usage programs only (kwk_usage_config_dyn; kwk_metrics_load does not accept them) */
+#define KWK_MOP_QFLOAT 8   /* x -> (double)go_int64(x * 10e9) * 1e-9: newQuantityFromFloat64 then AsApproximateFloat64 */
+#define KWK_MOP_LT 9       /* a b -> a < b ? 1.0 : 0.0 */
+#define KWK_MOP_LE 10
+#define KWK_MOP_GT 11
+#define KWK_MOP_GE 12
+#define KWK_MOP_SELECT 13  /* c a b -> c != 0.0 ? a : b */
+#define KWK_MIN_NOW_S 0              /* Now().UnixSecond() */
 #define KWK_MIN_CONTAINER_CPU 1       /* pod.Usage("cpu", container.name) */
 #define KWK_MIN_CONTAINER_MEM 2
 #define KWK_MIN_CONTAINER_CUM_CPU 3   /* pod.CumulativeUsage("cpu", container.name) */
@@ -539,6 +546,22 @@ kwk_status kwk_metrics_load(kwk_engine* pods, uint32_t n_metrics, const kwk_metr
  * node (controller.go:602-611); zero_time_unix_s = what UnixSecond() gives for the zero time */
 kwk_status kwk_metrics_inputs(kwk_engine* pods, const int64_t* pod_created_ns, const int64_t* node_created_ns,
                               const double* node_started, double zero_time_unix_s);
+
+/* Usage values that depend on the clock (a ResourceUsage expression reading pod.SinceSecond(),
+ * node.SinceSecond() or Now().UnixSecond(); kwok_amd/host/cel.py lower_usage): kwk_usage_config
+ * with, besides the constants, programs in the kwk_metric_op format.  A cpu value id v (of
+ * usage_key and of kwk_usage_mixed's ckeys) below n_cpu is cpu_values[v]; n_cpu <= v < n_cpu +
+ * n_cpu_progs is the program cpu_progs[v - n_cpu], which kwk_usage evaluates for the pod at its
+ * now_ns; memory alike (n_cpu + n_cpu_progs and n_mem + n_mem_progs at most 16384).  A program
+ * may load KWK_MIN_NOW_S, KWK_MIN_POD_SINCE, KWK_MIN_NODE_SINCE, KWK_MIN_POD_CREATED and
+ * KWK_MIN_NODE_CREATED only, has at most 64 ops and stack depth 8 and leaves one value.  With
+ * programs, kwk_usage needs the creation times of kwk_metrics_inputs (KWK_ESTATE without them;
+ * call it after this).  No programs: exactly kwk_usage_config. */
+typedef struct { uint32_t first_op, n_ops; } kwk_usage_prog;
+kwk_status kwk_usage_config_dyn(kwk_engine* eng, uint32_t n_nodes, const uint32_t* node_ptr, const uint32_t* usage_key,
+                                uint32_t n_cpu, const double* cpu_values, uint32_t n_cpu_progs, const kwk_usage_prog* cpu_progs,
+                                uint32_t n_mem, const double* mem_values, uint32_t n_mem_progs, const kwk_usage_prog* mem_progs,
+                                uint32_t n_ops, const kwk_metric_op* ops);
 /* every metric's series for the scrape of nodes [node_first, node_first + n_nodes) at now_ns
  * (after kwk_usage(now_ns)): metric by metric, node series per node, pod series per pod slot,
  * container series per container (kwk_usage_read_containers order); NaN for dead pods.

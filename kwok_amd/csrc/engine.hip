@@ -3082,6 +3082,19 @@ struct UsageArgs {
   uint32_t n_cmasks;
   uint32_t* __restrict__ cpart;       // [grid][kMaxCountMasks]
 };
+// usage_kernel<WB, true>'s further arguments (kwk_usage_config_dyn): a cpu value id >= n_cpu is program
+// id - n_cpu of progs, a memory id >= n_mem program n_cpu_progs + id - n_mem; evaluated per pod at `now`
+struct UsageDynArgs {
+  const uint2* __restrict__ progs;          // {first op, ops}
+  uint32_t n_cpu_progs, n_mem_progs;
+  const kwk_metric_op* __restrict__ uops;
+  uint32_t n_uops;
+  const int64_t* __restrict__ pod_created;  // kwk_metrics_inputs
+  const int64_t* __restrict__ node_created;
+  double zero_time_unix_s;
+  double* __restrict__ unit_val;    // with pod_out: per pod {cpu, mem} of one container (uniform pods)
+  double* __restrict__ cval;        // with pod_out: per container of a mixed pod {cpu, mem}, as ccum
+};
 constexpr uint32_t kUKeyDict = 256;  // entries of the 1-byte key column's value table
 constexpr uint32_t kUKeyZero = 255;  // its entry {0, 0}: the key a dead / out-of-range pod reads, so at
                                      // most 255 distinct keys take the 1-byte column
@@ -3094,6 +3107,78 @@ constexpr uint32_t kUKeyMixedIndex = 0x0FFFFFFFu;
 // time.Duration.Seconds() of now - last
 __device__ __forceinline__ double dur_seconds(int64_t d) {
   return (double)(d / 1000000000) + (double)(d % 1000000000) / 1e9;
+}
+
+// SinceSecond(): time.Since(creationTimestamp).Seconds() at the scrape's clock (metric and usage programs)
+__device__ __forceinline__ double since_seconds(int64_t now, int64_t created) {
+  if (created == INT64_MIN) return 9223372036.854775807;  // time.Since(zero time) saturates
+  int64_t d;
+  if (__builtin_sub_overflow(now, created, &d)) d = now > created ? INT64_MAX : INT64_MIN;
+  return dur_seconds(d);
+}
+
+// Usage values that depend on the clock (kwk_usage_config_dyn): one postfix program per value id
+// past the constants, in the metric op format plus KWK_MOP_QFLOAT / LT..GE / SELECT, evaluated
+// per pod by the lanes of usage_kernel<WB, true> that hold such an id.  The stack lives in registers:
+// its top is s[0] and a push / pop moves the entries (constant indices only, so nothing goes to
+// scratch); kwk_usage_config_dyn has checked depth <= 8, the op codes, the loads and that one
+// value is left.
+constexpr uint32_t kULdsOps = 256;    // program ops staged in LDS (else read via L1)
+constexpr uint32_t kULdsProgs = 256;  // program table entries staged in LDS
+constexpr uint32_t kUStack = 8;
+
+// newQuantityFromFloat64 (int64(v * 10e9) nano; amd64's out-of-range / NaN result is INT64_MIN),
+// then AsApproximateFloat64
+__device__ __forceinline__ double qfloat_approx(double v) {
+  const double x = v * 10e9;
+  const int64_t n = (x >= -9223372036854775808.0 && x < 9223372036854775808.0) ? (int64_t)x : INT64_MIN;
+  return (double)n * 1e-9;
+}
+
+__device__ __noinline__ double run_usage_program(const kwk_metric_op* ops, uint32_t n_ops, int64_t now,
+                                                 int64_t pod_created, int64_t node_created, double zero_time_unix_s) {
+  double s[kUStack] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  auto push = [&](double v) {
+#pragma unroll
+    for (int i = kUStack - 1; i > 0; --i) s[i] = s[i - 1];
+    s[0] = v;
+  };
+  auto drop = [&](int from) {  // entries from + 1.. move one up
+#pragma unroll
+    for (int i = 1; i < (int)kUStack - 1; ++i)
+      if (i >= from) s[i] = s[i + 1];
+  };
+  for (uint32_t i = 0; i < n_ops; ++i) {
+    const kwk_metric_op op = ops[i];
+    switch (op.op) {
+      case KWK_MOP_CONST: push(op.value); break;
+      case KWK_MOP_LOAD: {
+        double v;
+        if (op.arg == KWK_MIN_NOW_S) v = (double)now / 1e9;
+        else if (op.arg == KWK_MIN_POD_SINCE) v = since_seconds(now, pod_created);
+        else if (op.arg == KWK_MIN_NODE_SINCE) v = since_seconds(now, node_created);
+        else {
+          const int64_t c = op.arg == KWK_MIN_POD_CREATED ? pod_created : node_created;
+          v = c == INT64_MIN ? zero_time_unix_s : (double)c / 1e9;
+        }
+        push(v);
+        break;
+      }
+      case KWK_MOP_ADD: s[0] = s[1] + s[0]; drop(1); break;
+      case KWK_MOP_SUB: s[0] = s[1] - s[0]; drop(1); break;
+      case KWK_MOP_MUL: s[0] = s[1] * s[0]; drop(1); break;
+      case KWK_MOP_DIV: s[0] = s[1] / s[0]; drop(1); break;
+      case KWK_MOP_NEG: s[0] = -s[0]; break;
+      case KWK_MOP_QFLOAT: s[0] = qfloat_approx(s[0]); break;
+      case KWK_MOP_LT: s[0] = s[1] < s[0] ? 1.0 : 0.0; drop(1); break;
+      case KWK_MOP_LE: s[0] = s[1] <= s[0] ? 1.0 : 0.0; drop(1); break;
+      case KWK_MOP_GT: s[0] = s[1] > s[0] ? 1.0 : 0.0; drop(1); break;
+      case KWK_MOP_GE: s[0] = s[1] >= s[0] ? 1.0 : 0.0; drop(1); break;
+      case KWK_MOP_SELECT: s[0] = s[2] != 0.0 ? s[1] : s[0]; drop(1); drop(1); break;
+      default: break;
+    }
+  }
+  return s[0];
 }
 
 // alive flag of pod j of a lane's run (kURun words of WB bytes in WB 16-byte chunks)
@@ -3163,8 +3248,12 @@ __device__ __forceinline__ double readlane_f64(double v, int l) {
 // descriptor and first row are requested before the current chunk is worked on, so each
 // wave keeps one chunk's loads in flight (one block per chunk paid 3 memory latencies per
 // chunk back to back: 236-255 us for 100M pods, r2c-r2e)
-template <uint32_t WB>
-__global__ __launch_bounds__(kBlock) void usage_kernel(UsageArgs a) {
+// DYN: an engine with usage programs (kwk_usage_config_dyn): the same chunks, lanes, scan and
+// outputs; a value id past the constants is evaluated for its pod by run_usage_program.  Such an
+// engine always takes this kernel (no usage_fast_kernel: a pod's value is no table entry).
+// usage_kernel<WB> (DYN false) compiles to what it was before DYN existed; it does not read `d`.
+template <uint32_t WB, bool DYN = false>
+__global__ __launch_bounds__(kBlock) void usage_kernel(UsageArgs a, UsageDynArgs d) {
   __shared__ uint32_t s_ptr[kWavesPerBlock][kUChunkNodes + 1];
   __shared__ double2 s_sum[kWavesPerBlock][kUChunkNodes];  // node sums, each written once where the node closes
   __shared__ double s_val[kULdsValues];
@@ -3203,9 +3292,33 @@ __global__ __launch_bounds__(kBlock) void usage_kernel(UsageArgs a) {
     for (uint32_t j = threadIdx.x; j < a.n_cpu + a.n_mem; j += kBlock)
       s_val[j] = j < a.n_cpu ? a.cpu_v[j] : a.mem_v[j - a.n_cpu];
   }
+  // DYN: the program table and the ops, staged like the values where they fit
+  const uint2* progs = d.progs;
+  const kwk_metric_op* uops = d.uops;
+  if constexpr (DYN) {
+    __shared__ uint2 s_prog[kULdsProgs];
+    __shared__ kwk_metric_op s_uop[kULdsOps];
+    const uint32_t np = d.n_cpu_progs + d.n_mem_progs;
+    if (np <= kULdsProgs) {
+      for (uint32_t j = threadIdx.x; j < np; j += kBlock) s_prog[j] = d.progs[j];
+      progs = s_prog;
+    }
+    if (d.n_uops <= kULdsOps) {
+      for (uint32_t j = threadIdx.x; j < d.n_uops; j += kBlock) s_uop[j] = d.uops[j];
+      uops = s_uop;
+    }
+  }
   __syncthreads();
   const double* __restrict__ cpu_v = lds_vals ? s_val : a.cpu_v;
   const double* __restrict__ mem_v = lds_vals ? s_val + a.n_cpu : a.mem_v;
+  // DYN: the value of id for pod p of `node`: a constant as above, or its program at a.now (a
+  // wave none of whose lanes holds a program id branches past the interpreter)
+  auto dyn_value = [&](const double* __restrict__ vals, uint32_t n_const, uint32_t prog0, uint32_t id, uint32_t p,
+                       uint32_t node) -> double {
+    if (id < n_const) return vals[id];
+    const uint2 pr = progs[prog0 + id - n_const];
+    return run_usage_program(uops + pr.x, pr.y, a.now, d.pod_created[p], d.node_created[node], d.zero_time_unix_s);
+  };
   // the alive flag in the raw word (packed: at fshift; wide: in sched)
   const uint32_t abit = WB == 1 ? kIdAlive : (WB == 8 && !a.fmt.dw) ? (uint32_t)KWK_F_ALIVE
                                                                    : (uint32_t)(KWK_F_ALIVE >> 8) << a.fmt.fshift;
@@ -3298,15 +3411,33 @@ __global__ __launch_bounds__(kBlock) void usage_kernel(UsageArgs a) {
         uint2 fc = make_uint2(0u, 0u);
         if (alive) {
           if (nc) {
-            c1v = cpu_v[key & 0x3FFFu];
-            m1v = mem_v[(key >> 14) & 0x3FFFu];
+            if constexpr (DYN) {
+              c1v = dyn_value(cpu_v, a.n_cpu, 0u, key & 0x3FFFu, p, na + k);
+              m1v = dyn_value(mem_v, a.n_mem, d.n_cpu_progs, (key >> 14) & 0x3FFFu, p, na + k);
+              if (a.pod_out) reinterpret_cast<double2*>(d.unit_val)[p] = make_double2(c1v, m1v);
+            } else {
+              c1v = cpu_v[key & 0x3FFFu];
+              m1v = mem_v[(key >> 14) & 0x3FFFu];
+            }
             for (uint32_t c = 0; c < nc; ++c) { vc += c1v; vm += m1v; }
           } else {
             fc = a.mixed[key & kUKeyMixedIndex];
-            for (uint32_t c = 0; c < fc.y; ++c) {
-              const uint32_t ck = a.ckeys[fc.x + c];
-              vc += cpu_v[ck & 0x3FFFu];
-              vm += mem_v[(ck >> 14) & 0x3FFFu];
+            if constexpr (DYN) {  // each container's value once: kept in cval for the integrators and the readers
+              const uint32_t mb = a.pod_out ? a.mbase[p] : 0u;
+              for (uint32_t c = 0; c < fc.y; ++c) {
+                const uint32_t ck = a.ckeys[fc.x + c];
+                const double xc = dyn_value(cpu_v, a.n_cpu, 0u, ck & 0x3FFFu, p, na + k);
+                const double xm = dyn_value(mem_v, a.n_mem, d.n_cpu_progs, (ck >> 14) & 0x3FFFu, p, na + k);
+                if (a.pod_out) reinterpret_cast<double2*>(d.cval)[mb + c] = make_double2(xc, xm);
+                vc += xc;
+                vm += xm;
+              }
+            } else {
+              for (uint32_t c = 0; c < fc.y; ++c) {
+                const uint32_t ck = a.ckeys[fc.x + c];
+                vc += cpu_v[ck & 0x3FFFu];
+                vm += mem_v[(ck >> 14) & 0x3FFFu];
+              }
             }
           }
         }
@@ -3331,8 +3462,14 @@ __global__ __launch_bounds__(kBlock) void usage_kernel(UsageArgs a) {
                 const uint32_t ck = a.ckeys[fc.x + c];
                 double2 cu = reinterpret_cast<double2*>(a.ccum)[mb + c];
                 if (lt != INT64_MIN) {
-                  cu.x += dt * cpu_v[ck & 0x3FFFu];
-                  cu.y += dt * mem_v[(ck >> 14) & 0x3FFFu];
+                  if constexpr (DYN) {
+                    const double2 x = reinterpret_cast<const double2*>(d.cval)[mb + c];  // this lane's, from above
+                    cu.x += dt * x.x;
+                    cu.y += dt * x.y;
+                  } else {
+                    cu.x += dt * cpu_v[ck & 0x3FFFu];
+                    cu.y += dt * mem_v[(ck >> 14) & 0x3FFFu];
+                  }
                   reinterpret_cast<double2*>(a.ccum)[mb + c] = cu;
                 }
                 cc += cu.x;
@@ -3843,6 +3980,8 @@ struct MetricArgs {
   const double* __restrict__ pod_out;
   const double* __restrict__ pod_cum;
   const double* __restrict__ ccum;
+  const double* __restrict__ unit_val;  // an engine with usage programs: the last kwk_usage's per-container
+  const double* __restrict__ cval;      // values (uniform pods per pod, mixed pods per container), else null
   const double* __restrict__ node_out;
   const int64_t* __restrict__ pod_created;   // ns, INT64_MIN = the Go zero time
   const int64_t* __restrict__ node_created;
@@ -3859,13 +3998,6 @@ __device__ __forceinline__ uint32_t seg_of(const uint32_t* __restrict__ a, uint3
     if (a[mid] <= x) lo = mid; else hi = mid;
   }
   return lo;
-}
-
-__device__ __forceinline__ double since_seconds(int64_t now, int64_t created) {
-  if (created == INT64_MIN) return 9223372036.854775807;  // time.Since(zero time) saturates
-  int64_t d;
-  if (__builtin_sub_overflow(now, created, &d)) d = now > created ? INT64_MAX : INT64_MIN;
-  return dur_seconds(d);
 }
 
 // the series s of a metric: its node, pod and container index (false: a dead pod, no series)
@@ -3907,11 +4039,15 @@ __device__ double run_metric_program(const MetricArgs& a, const kwk_metric_op* _
           const bool cum = in >= KWK_MIN_CONTAINER_CUM_CPU;
           const uint32_t r = (in - KWK_MIN_CONTAINER_CPU) & 1u;
           if (k >> 28) {
-            v = cum ? a.pod_cum[2 * (uint64_t)pod + r] : (r ? a.mem_v[(k >> 14) & 0x3FFFu] : a.cpu_v[k & 0x3FFFu]);
+            v = cum ? a.pod_cum[2 * (uint64_t)pod + r]
+                : a.unit_val ? a.unit_val[2 * (uint64_t)pod + r]
+                             : (r ? a.mem_v[(k >> 14) & 0x3FFFu] : a.cpu_v[k & 0x3FFFu]);
           } else {
             const uint2 fc = a.mixed[k & kUKeyMixedIndex];
             const uint32_t ck = a.ckeys[fc.x + j];
-            v = cum ? a.ccum[2 * (uint64_t)(a.mbase[pod] + j) + r] : (r ? a.mem_v[(ck >> 14) & 0x3FFFu] : a.cpu_v[ck & 0x3FFFu]);
+            v = cum ? a.ccum[2 * (uint64_t)(a.mbase[pod] + j) + r]
+                : a.cval ? a.cval[2 * (uint64_t)(a.mbase[pod] + j) + r]
+                         : (r ? a.mem_v[(ck >> 14) & 0x3FFFu] : a.cpu_v[ck & 0x3FFFu]);
           }
         } else if (in >= KWK_MIN_POD_CPU && in <= KWK_MIN_POD_CUM_MEM) {
           v = a.pod_out[4 * (uint64_t)pod + (in - KWK_MIN_POD_CPU)];
@@ -4790,6 +4926,13 @@ struct kwk_engine {
   DevBuf<double> d_podv;          // usage_fast_kernel's pod values per (containers, value id)
   uint32_t podv_n = 0;
   uint32_t compact_small = 8192;  // KWK_TUNE_COMPACT_SMALL (kSmallSegs)
+  // usage programs (kwk_usage_config_dyn): the table (cpu programs, then memory), the ops, and with
+  // per-pod outputs the evaluated per-container values the readers take in place of the constants
+  DevBuf<uint2> d_uprogs;
+  DevBuf<kwk_metric_op> d_uops;
+  uint32_t n_cpu_progs = 0, n_mem_progs = 0, n_uops = 0;
+  DevBuf<double> d_unit_val, d_cval;
+  uint32_t inputs_pods = 0, inputs_nodes = 0;  // the configuration kwk_metrics_inputs was given for
   DevBuf<uint4> d_uchunk;         // usage_kernel's chunks of whole nodes {first pod, end pod, first node, end node}
   uint32_t n_uchunks = 0;
   // host copies of the usage configuration (per-container reads, metric scrapes)
@@ -6626,11 +6769,64 @@ kwk_status kwk_read(kwk_engine* e, uint32_t first, uint32_t n, kwk_hot* hot, int
   return KWK_OK;
 }
 
+// validates one usage program (kwk_usage_config_dyn): what run_usage_program relies on
+static kwk_status check_usage_program(const kwk_metric_op* ops, kwk_usage_prog pr, uint32_t n_ops) {
+  if (pr.n_ops == 0 || pr.n_ops > 64 || (uint64_t)pr.first_op + pr.n_ops > n_ops) return fail(KWK_EINVAL, "usage program ops range");
+  int depth = 0;
+  for (uint32_t i = pr.first_op; i < pr.first_op + pr.n_ops; ++i) {
+    const kwk_metric_op& op = ops[i];
+    const std::string at = " (op " + std::to_string(i) + ": " + std::to_string(op.op) + ")";
+    if (op.op == KWK_MOP_CONST || op.op == KWK_MOP_LOAD) {
+      if (++depth > (int)kUStack) return fail(KWK_EINVAL, "usage program deeper than 8" + at);
+      if (op.op == KWK_MOP_LOAD && op.arg != KWK_MIN_NOW_S && op.arg != KWK_MIN_POD_SINCE && op.arg != KWK_MIN_NODE_SINCE &&
+          op.arg != KWK_MIN_POD_CREATED && op.arg != KWK_MIN_NODE_CREATED)
+        return fail(KWK_EINVAL, "usage program loads input " + std::to_string(op.arg) + at);
+    } else if (op.op == KWK_MOP_NEG || op.op == KWK_MOP_QFLOAT) {
+      if (depth < 1) return fail(KWK_EINVAL, "usage program underflow" + at);
+    } else if ((op.op >= KWK_MOP_ADD && op.op <= KWK_MOP_DIV) || (op.op >= KWK_MOP_LT && op.op <= KWK_MOP_GE)) {
+      if (depth < 2) return fail(KWK_EINVAL, "usage program underflow" + at);
+      --depth;
+    } else if (op.op == KWK_MOP_SELECT) {
+      if (depth < 3) return fail(KWK_EINVAL, "usage program underflow" + at);
+      depth -= 2;
+    } else {
+      return fail(KWK_EINVAL, "usage program op" + at);
+    }
+  }
+  if (depth != 1) return fail(KWK_EINVAL, "a usage program leaves one value");
+  return KWK_OK;
+}
+
+// the evaluated per-container values of an engine with usage programs and per-pod outputs
+static kwk_status ensure_dyn_outputs(kwk_engine* e) {
+  if (e->n_cpu_progs + e->n_mem_progs == 0 || !e->d_pod_out || e->d_unit_val) return KWK_OK;
+  HIP_TRY(e->d_unit_val.alloc(2 * (size_t)e->capacity));
+  HIP_TRY(hipMemsetAsync(e->d_unit_val, 0, 16 * (size_t)e->capacity, e->stream));
+  return KWK_OK;
+}
+
 kwk_status kwk_usage_config(kwk_engine* e, uint32_t n_nodes, const uint32_t* node_ptr, const uint32_t* ukey,
                             uint32_t n_cpu, const double* cpu_values, uint32_t n_mem, const double* mem_values) {
+  return kwk_usage_config_dyn(e, n_nodes, node_ptr, ukey, n_cpu, cpu_values, 0, nullptr, n_mem, mem_values, 0, nullptr, 0,
+                              nullptr);
+}
+
+kwk_status kwk_usage_config_dyn(kwk_engine* e, uint32_t n_nodes, const uint32_t* node_ptr, const uint32_t* ukey,
+                                uint32_t n_cpu, const double* cpu_values, uint32_t n_cpu_progs,
+                                const kwk_usage_prog* cpu_progs, uint32_t n_mem, const double* mem_values,
+                                uint32_t n_mem_progs, const kwk_usage_prog* mem_progs, uint32_t n_ops,
+                                const kwk_metric_op* ops) {
   ErrScope es_(e ? &e->err : nullptr);
   if (!e || !node_ptr || !ukey || !cpu_values || !mem_values) return fail(KWK_EINVAL, "null argument");
   if (n_cpu == 0 || n_mem == 0 || n_cpu > 0x4000 || n_mem > 0x4000) return fail(KWK_EINVAL, "dictionary size");
+  if ((n_cpu_progs && !cpu_progs) || (n_mem_progs && !mem_progs) || (n_ops && !ops)) return fail(KWK_EINVAL, "null argument");
+  if ((uint64_t)n_cpu + n_cpu_progs > 0x4000 || (uint64_t)n_mem + n_mem_progs > 0x4000)
+    return fail(KWK_EINVAL, "dictionary size: constants and programs share 16384 ids");
+  for (uint32_t i = 0; i < n_cpu_progs; ++i)
+    if (kwk_status st = check_usage_program(ops, cpu_progs[i], n_ops)) return st;
+  for (uint32_t i = 0; i < n_mem_progs; ++i)
+    if (kwk_status st = check_usage_program(ops, mem_progs[i], n_ops)) return st;
+  const uint32_t n_progs = n_cpu_progs + n_mem_progs;
   if (node_ptr[0] != 0) return fail(KWK_EINVAL, "node_ptr[0] must be 0");
   for (uint32_t j = 0; j < n_nodes; ++j)
     if (node_ptr[j + 1] < node_ptr[j]) return fail(KWK_EINVAL, "node_ptr must be non-decreasing");
@@ -6642,7 +6838,7 @@ kwk_status kwk_usage_config(kwk_engine* e, uint32_t n_nodes, const uint32_t* nod
       mixed_keys = true;
       continue;
     }
-    if ((ukey[p] & 0x3FFFu) >= n_cpu || ((ukey[p] >> 14) & 0x3FFFu) >= n_mem)
+    if ((ukey[p] & 0x3FFFu) >= n_cpu + n_cpu_progs || ((ukey[p] >> 14) & 0x3FFFu) >= n_mem + n_mem_progs)
       return fail(KWK_EINVAL, "usage_key value id out of range");
   }
   if (kwk_status st = set_dev(e)) return st;
@@ -6651,6 +6847,8 @@ kwk_status kwk_usage_config(kwk_engine* e, uint32_t n_nodes, const uint32_t* nod
   // (the KWK_ESTATE guard of the usage calls, should a call below fail)
   e->d_node_ptr.reset(), e->d_ukey.reset(), e->d_cpu.reset(), e->d_mem.reset(), e->d_node_out.reset();
   e->d_node_cum.reset(), e->d_node_last.reset(), e->d_usage_part.reset(), e->d_cluster.reset(), e->d_uchunk.reset();
+  e->d_uprogs.reset(), e->d_uops.reset(), e->d_unit_val.reset(), e->d_cval.reset();
+  e->n_cpu_progs = e->n_mem_progs = e->n_uops = 0;
   // the usage kernels' chunks: whole nodes, at most kUChunkRows wave rows of pods (less the 8 of the
   // rounded start) and kUChunkNodes nodes each; a node with more pods than that gets a chunk of its
   // own (the wave carries its sum from row to row)
@@ -6676,7 +6874,7 @@ kwk_status kwk_usage_config(kwk_engine* e, uint32_t n_nodes, const uint32_t* nod
   e->podv_n = 0;
   e->kv_n = 0;
   const size_t nv = (size_t)n_cpu + n_mem;
-  if ((max_nc + 1) * nv <= kUFastVals) {
+  if (n_progs == 0 && (max_nc + 1) * nv <= kUFastVals) {  // (a program's value is no table entry)
     std::vector<double> podv((max_nc + 1) * nv, 0.0);
     for (uint32_t nc = 1; nc <= max_nc; ++nc) {
       for (uint32_t i = 0; i < n_cpu; ++i) {
@@ -6752,6 +6950,19 @@ kwk_status kwk_usage_config(kwk_engine* e, uint32_t n_nodes, const uint32_t* nod
   e->d_mixed.reset(), e->d_ckeys.reset(), e->d_ccum.reset(), e->d_cptr.reset(), e->d_mbase.reset();
   e->h_mbase.clear();
   if (e->d_pod_cum) HIP_TRY(hipMemsetAsync(e->d_pod_cum, 0, 16 * (size_t)e->capacity, e->stream));
+  if (n_progs) {
+    std::vector<uint2> progs;
+    for (uint32_t i = 0; i < n_cpu_progs; ++i) progs.push_back(make_uint2(cpu_progs[i].first_op, cpu_progs[i].n_ops));
+    for (uint32_t i = 0; i < n_mem_progs; ++i) progs.push_back(make_uint2(mem_progs[i].first_op, mem_progs[i].n_ops));
+    HIP_TRY(e->d_uprogs.alloc(progs.size()));
+    HIP_TRY(e->d_uops.alloc(n_ops));
+    HIP_TRY(upload(e, e->d_uprogs, progs.data(), sizeof(uint2) * progs.size()));
+    HIP_TRY(upload(e, e->d_uops, ops, sizeof(kwk_metric_op) * (size_t)n_ops));
+    e->n_cpu_progs = n_cpu_progs;
+    e->n_mem_progs = n_mem_progs;
+    e->n_uops = n_ops;
+    if (kwk_status st = ensure_dyn_outputs(e)) return st;
+  }
   e->d_node_ptr = std::move(d_node_ptr);
   return KWK_OK;
 }
@@ -6764,7 +6975,7 @@ kwk_status kwk_usage_mixed(kwk_engine* e, uint32_t n_mixed, const uint32_t* mixe
   for (uint32_t m = 0; m < n_mixed; ++m)
     if ((uint64_t)mixed[2 * m] + mixed[2 * m + 1] > n_ckeys) return fail(KWK_EINVAL, "mixed entry beyond ckeys");
   for (uint32_t c = 0; c < n_ckeys; ++c)
-    if ((ckeys[c] & 0x3FFFu) >= e->h_cpu.size() || ((ckeys[c] >> 14) & 0x3FFFu) >= e->h_mem.size())
+    if ((ckeys[c] & 0x3FFFu) >= e->h_cpu.size() + e->n_cpu_progs || ((ckeys[c] >> 14) & 0x3FFFu) >= e->h_mem.size() + e->n_mem_progs)
       return fail(KWK_EINVAL, "ckeys value id out of range");
   for (uint32_t p = 0; p < e->n_usage_pods; ++p)
     if ((e->h_ukey[p] >> 28) == 0 && (e->h_ukey[p] & kUKeyMixedIndex) >= n_mixed)
@@ -6772,7 +6983,7 @@ kwk_status kwk_usage_mixed(kwk_engine* e, uint32_t n_mixed, const uint32_t* mixe
   if (kwk_status st = set_dev(e)) return st;
   HIP_TRY(hipStreamSynchronize(e->stream));
   // (the engine has no mixed table until d_mixed is set again, at the end: the KWK_ESTATE guard)
-  e->d_mixed.reset(), e->d_ckeys.reset(), e->d_ccum.reset(), e->d_cptr.reset(), e->d_mbase.reset();
+  e->d_mixed.reset(), e->d_ckeys.reset(), e->d_ccum.reset(), e->d_cptr.reset(), e->d_mbase.reset(), e->d_cval.reset();
   e->h_cptr.clear();
   // integrators are per pod and container (mixed entries may be shared by pods whose containers
   // evaluate alike): each mixed pod's containers get their own range of ccum
@@ -6793,6 +7004,10 @@ kwk_status kwk_usage_mixed(kwk_engine* e, uint32_t n_mixed, const uint32_t* mixe
   if (n_ckeys) HIP_TRY(upload(e, e->d_ckeys, ckeys, 4 * (size_t)n_ckeys));
   if (e->n_usage_pods) HIP_TRY(upload(e, e->d_mbase, e->h_mbase.data(), 4 * (size_t)e->n_usage_pods));
   HIP_TRY(hipMemsetAsync(e->d_ccum, 0, 16 * ((size_t)nint + 1), e->stream));
+  if (e->n_cpu_progs + e->n_mem_progs) {  // the containers' evaluated values, laid out as ccum
+    HIP_TRY(e->d_cval.alloc(2 * ((size_t)nint + 1)));
+    HIP_TRY(hipMemsetAsync(e->d_cval, 0, 16 * ((size_t)nint + 1), e->stream));
+  }
   e->h_mixed.assign(mixed, mixed + 2 * (size_t)n_mixed);
   e->h_ckeys.assign(ckeys, ckeys + n_ckeys);
   e->d_mixed = std::move(d_mixed);
@@ -6851,14 +7066,26 @@ kwk_status kwk_usage_read_containers(kwk_engine* e, uint32_t first, uint32_t n, 
     cc.resize(2 * (size_t)(cmax - cmin));
     HIP_TRY(hipMemcpy(cc.data(), e->d_ccum + 2 * (size_t)cmin, 16 * (size_t)(cmax - cmin), hipMemcpyDeviceToHost));
   }
+  // an engine with usage programs: the values the last kwk_usage evaluated, not the constants
+  const bool dyn = e->n_cpu_progs + e->n_mem_progs != 0;
+  std::vector<double> uv, cv;
+  if (dyn) {
+    if (kwk_status st = ensure_dyn_outputs(e)) return st;
+    uv.resize(2 * (size_t)n);
+    HIP_TRY(hipMemcpy(uv.data(), e->d_unit_val + 2 * (size_t)first, 16 * (size_t)n, hipMemcpyDeviceToHost));
+    if (cmin < cmax) {
+      cv.resize(2 * (size_t)(cmax - cmin));
+      HIP_TRY(hipMemcpy(cv.data(), e->d_cval + 2 * (size_t)cmin, 16 * (size_t)(cmax - cmin), hipMemcpyDeviceToHost));
+    }
+  }
   size_t o = 0;
   for (uint32_t i = 0; i < n; ++i) {
     const uint32_t p = first + i, k = e->h_ukey[p];
     const bool alive = (st[i].y & KWK_F_ALIVE) != 0;
     if (k >> 28) {
       for (uint32_t j = 0; j < (k >> 28); ++j, o += 4) {
-        out[o] = alive ? e->h_cpu[k & 0x3FFFu] : 0.0;
-        out[o + 1] = alive ? e->h_mem[(k >> 14) & 0x3FFFu] : 0.0;
+        out[o] = !alive ? 0.0 : dyn ? uv[2 * (size_t)i] : e->h_cpu[k & 0x3FFFu];
+        out[o + 1] = !alive ? 0.0 : dyn ? uv[2 * (size_t)i + 1] : e->h_mem[(k >> 14) & 0x3FFFu];
         out[o + 2] = alive ? unit[2 * (size_t)i] : 0.0;
         out[o + 3] = alive ? unit[2 * (size_t)i + 1] : 0.0;
       }
@@ -6867,8 +7094,8 @@ kwk_status kwk_usage_read_containers(kwk_engine* e, uint32_t first, uint32_t n, 
       const uint32_t mb = e->h_mbase[p];
       for (uint32_t j = 0; j < c; ++j, o += 4) {
         const uint32_t ck = e->h_ckeys[f + j];
-        out[o] = alive ? e->h_cpu[ck & 0x3FFFu] : 0.0;
-        out[o + 1] = alive ? e->h_mem[(ck >> 14) & 0x3FFFu] : 0.0;
+        out[o] = !alive ? 0.0 : dyn ? cv[2 * (size_t)(mb + j - cmin)] : e->h_cpu[ck & 0x3FFFu];
+        out[o + 1] = !alive ? 0.0 : dyn ? cv[2 * (size_t)(mb + j - cmin) + 1] : e->h_mem[(ck >> 14) & 0x3FFFu];
         out[o + 2] = alive ? cc[2 * (size_t)(mb + j - cmin)] : 0.0;
         out[o + 3] = alive ? cc[2 * (size_t)(mb + j - cmin) + 1] : 0.0;
       }
@@ -6898,6 +7125,8 @@ static MetricArgs metric_args(kwk_engine* e, uint32_t dim, int64_t now_ns, uint3
   a.pod_out = e->d_pod_out;
   a.pod_cum = e->d_pod_cum;
   a.ccum = e->d_ccum;
+  a.unit_val = e->d_unit_val;
+  a.cval = e->d_cval;
   a.node_out = e->d_node_out;
   a.pod_created = e->d_pod_created;
   a.node_created = e->d_node_created;
@@ -6977,6 +7206,8 @@ kwk_status kwk_metrics_inputs(kwk_engine* e, const int64_t* pod_created, const i
     HIP_TRY(upload(e, e->d_node_started, started, 8 * (size_t)e->n_nodes));
   }
   e->zero_time_unix_s = zero_time_unix_s;
+  e->inputs_pods = e->n_usage_pods;
+  e->inputs_nodes = e->n_nodes;
   e->d_pod_created = std::move(d_pod_created);
   return KWK_OK;
 }
@@ -7231,6 +7462,15 @@ static kwk_status enqueue_usage(kwk_engine* e, int64_t now_ns, uint32_t* n_block
                e->d_node_last, now_ns, e->d_usage_part, e->d_pod_out, e->d_pod_cum, e->d_pod_last, e->d_mixed,
                e->d_ckeys, e->d_mbase, e->d_ccum, e->d_podv, e->podv_n, e->d_ukey8, e->d_kv, e->kv_n,
                cmasks, n_cmasks, e->d_count_part};
+  const bool dyn = e->n_cpu_progs + e->n_mem_progs != 0;
+  UsageDynArgs ud{};
+  if (dyn) {  // the programs read creation times
+    if (!e->d_pod_created || e->inputs_pods != e->n_usage_pods || e->inputs_nodes != e->n_nodes)
+      return fail(KWK_ESTATE, "kwk_metrics_inputs must be called first (usage programs read creation times)");
+    if (kwk_status st = ensure_dyn_outputs(e)) return st;
+    ud = UsageDynArgs{e->d_uprogs, e->n_cpu_progs, e->n_mem_progs, e->d_uops, e->n_uops, e->d_pod_created,
+                      e->d_node_created, e->zero_time_unix_s, e->d_unit_val, e->d_cval};
+  }
   const uint32_t wb = word_bytes(e->fmt);
   // the kernels are specialised on the state word's bytes (1: dictionary ids, 2, 4, 8)
 #define USAGE_KERNEL(K, ...) (wb == 1 ? (const void*)K<1 __VA_ARGS__> : wb == 2 ? (const void*)K<2 __VA_ARGS__>   \
@@ -7250,11 +7490,11 @@ static kwk_status enqueue_usage(kwk_engine* e, int64_t now_ns, uint32_t* n_block
     return KWK_OK;
   }
   // persistent grid (every block slot the occupancy allows), at most one chunk per wave
-  const void* kern = USAGE_KERNEL(usage_kernel);
+  const void* kern = dyn ? USAGE_KERNEL(usage_kernel, , true) : USAGE_KERNEL(usage_kernel);
 #undef USAGE_KERNEL
   const uint32_t grid = persist_grid(e, kern, ublocks);
   if (grid) {
-    void* args[] = {&ua};
+    void* args[] = {&ua, &ud};
     HIP_TRY(hipLaunchKernel(kern, dim3(grid), dim3(kBlock), args, 0, e->stream));
   }
   *n_blocks = grid;
@@ -7279,7 +7519,7 @@ kwk_status kwk_usage_pods(kwk_engine* e, uint32_t enable) {
   if (!e) return fail(KWK_EINVAL, "null engine");
   if (kwk_status st = set_dev(e)) return st;
   HIP_TRY(hipStreamSynchronize(e->stream));
-  e->d_pod_out.reset(), e->d_pod_cum.reset(), e->d_pod_last.reset();
+  e->d_pod_out.reset(), e->d_pod_cum.reset(), e->d_pod_last.reset(), e->d_unit_val.reset();
   if (!enable) return KWK_OK;
   const size_t n = e->capacity;
   DevBuf<double> d_pod_out;  // the engine's at the end: its presence turns the per-pod outputs on
@@ -7291,7 +7531,7 @@ kwk_status kwk_usage_pods(kwk_engine* e, uint32_t enable) {
   std::vector<int64_t> lasts(n, INT64_MIN);
   HIP_TRY(upload(e, e->d_pod_last, lasts.data(), 8 * n));
   e->d_pod_out = std::move(d_pod_out);
-  return KWK_OK;
+  return ensure_dyn_outputs(e);
 }
 
 kwk_status kwk_usage_read_pods(kwk_engine* e, uint32_t first, uint32_t n, double* pod_out) {

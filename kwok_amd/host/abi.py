@@ -156,6 +156,10 @@ class MetricDesc(C.Structure):
 
 
 METRIC_DIM = {"node": 0, "pod": 1, "container": 2}
+# KWK_MOP_* of usage programs (kwk_usage_config_dyn) beyond the metric ops
+MOP_QFLOAT, MOP_LT, MOP_LE, MOP_GT, MOP_GE, MOP_SELECT = 8, 9, 10, 11, 12, 13
+USAGE_OP_DTYPE = np.dtype([("op", "<u4"), ("arg", "<u4"), ("value", "<f8")])  # kwk_metric_op
+USAGE_PROG_DTYPE = np.dtype([("first_op", "<u4"), ("n_ops", "<u4")])         # kwk_usage_prog
 
 
 class MetricBucket(C.Structure):
@@ -194,6 +198,7 @@ EXPORTS = [
     "kwk_last_sweep", "kwk_tick_bind", "kwk_tick", "kwk_tick_n", "kwk_histograms_load", "kwk_histograms_eval",
     "kwk_fired_fetch", "kwk_fired_fetch_wait", "kwk_fired_keep",
     "kwk_metrics_eval_device", "kwk_histograms_eval_device", "kwk_metrics_series_device", "kwk_ring_view",
+    "kwk_usage_config_dyn",
 ]
 ABI_VERSION = 3  # KWK_ABI_VERSION of include/kwok_engine.h: the library must match the structs above
 TICK_COMPACT = 1 << 0  # KWK_TICK_COMPACT
@@ -275,6 +280,9 @@ def lib():
     L.kwk_sync.argtypes = [C.c_void_p]
     L.kwk_usage_config.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
                                    C.c_uint32, C.c_void_p]
+    L.kwk_usage_config_dyn.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                       C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
+                                       C.c_uint32, C.c_void_p]
     L.kwk_usage.argtypes = [C.c_void_p, C.c_int64]
     L.kwk_usage_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.kwk_usage_pods.argtypes = [C.c_void_p, C.c_uint32]

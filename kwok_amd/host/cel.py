@@ -12,7 +12,7 @@ resource_list.go).  Results become float64 through ``AsFloat64`` (environment.go
 This module parses that language (the CEL grammar: ?:, ||, &&, relations incl. ``in``,
 + -, * / %, unary ! -, member / index / call, literals, lists, maps) and evaluates it with
 CEL's typing rules (no implicit int <-> double arithmetic, int64 overflow is an error,
-heterogeneous numeric equality, error-absorbing && / ||).  Two uses:
+heterogeneous numeric equality, error-absorbing && / ||).  Three uses:
 
 * ``evaluate(expr, data)`` — the host evaluation of an expression for one (node, pod,
   container) binding (the value of a ResourceUsage expression for a pod, constant folding);
@@ -20,6 +20,10 @@ heterogeneous numeric equality, error-absorbing && / ||).  Two uses:
   quantities the engine keeps (usage, cumulative usage, creation times, the scrape's now) that
   ``metrics_kernel`` evaluates for every series of a scrape (engine.hip).  Sub-expressions that
   do not depend on the series fold to constants on the host.
+* ``lower_usage(ast, pod, node, container)`` — the device form of a ResourceUsage expression
+  that reads the clock: everything clock-free folds for the pod with the evaluator, the rest
+  becomes a postfix program ``usage_kernel`` runs per pod at every scrape
+  (``kwk_usage_config_dyn``); ``run_usage_program`` interprets one on the host.
 
 Quantities are modelled as apimachinery's int64Amount (unscaled integer x 10^scale), with
 AsApproximateFloat64, ScaledValue(Nano) and kwok's Quantity x double rule
@@ -1047,3 +1051,277 @@ def lower(src: str, dimension: str) -> List[Tuple[int, float]]:
     if emit(ast) != "double":
         raise LowerError("the value is not a double")
     return prog
+
+
+# ------------------------------------------------------------------ usage lowering
+# A ResourceUsage expression that reads the clock (pod / node SinceSecond, Now().UnixSecond()) is
+# evaluated by the usage kernel at every scrape: lower_usage folds what does not depend on the
+# clock with the evaluator above, for one pod, and lowers the rest to the metric op format plus
+# the ops below (include/kwok_engine.h KWK_MOP_*).
+OP_QFLOAT = 8                                 # x -> approx(newQuantityFromFloat64(x))
+OP_LT, OP_LE, OP_GT, OP_GE = 9, 10, 11, 12    # a b -> 1.0 / 0.0
+OP_SELECT = 13                                # c a b -> c != 0 ? a : b
+USAGE_MAX_OPS, USAGE_MAX_DEPTH = 64, 8
+USAGE_LOADS = (IN_NOW_S, IN_POD_SINCE, IN_NODE_SINCE, IN_POD_CREATED, IN_NODE_CREATED)
+
+_CLOCK_CALLS = ("Now", "now", "SinceSecond")
+_USAGE_REFUSED = ("Rand", "Usage", "CumulativeUsage", "StartedContainersTotal", "startedContainersTotal")
+_NOW = (("call", "Now", []), ("call", "now", []))
+_OBJ = (("ident", "pod"), ("ident", "node"))
+
+
+class UsageLowerError(ValueError):
+    """The expression reads the clock in a way the usage kernel has no form for."""
+
+
+def _calls(n, names) -> Optional[str]:
+    """The first function / method of `names` the expression calls."""
+    if isinstance(n, tuple):
+        if n and n[0] == "call" and n[1] in names:
+            return n[1]
+        if n and n[0] == "method" and n[2] in names:
+            return n[2]
+        for x in n[1:] if n and isinstance(n[0], str) else n:
+            r = _calls(x, names)
+            if r:
+                return r
+    elif isinstance(n, list):
+        for x in n:
+            r = _calls(x, names)
+            if r:
+                return r
+    return None
+
+
+def usage_reads_clock(ast) -> bool:
+    return _calls(ast, _CLOCK_CALLS) is not None
+
+
+def usage_refused_call(ast) -> Optional[str]:
+    """Rand / Usage / ... : what a usage expression may not call (None: nothing)."""
+    return _calls(ast, _USAGE_REFUSED)
+
+
+def usage_bad_clock(n) -> Optional[str]:
+    """A clock read no usage program has a form for, whatever the pod: a Now() that is not the
+    argument of UnixSecond, a SinceSecond of something other than pod / node (None: nothing)."""
+    if isinstance(n, list):
+        for x in n:
+            r = usage_bad_clock(x)
+            if r:
+                return r
+        return None
+    if not isinstance(n, tuple) or not n:
+        return None
+    if isinstance(n[0], str) and n[0] in ("call", "method"):
+        name = n[2] if n[0] == "method" else n[1]
+        full = ([n[1]] if n[0] == "method" else []) + list(n[3] if n[0] == "method" else n[2])
+        if name in ("Now", "now"):
+            return "Now() other than Now().UnixSecond()"
+        if name == "UnixSecond" and len(full) == 1 and full[0] in _NOW:
+            return None
+        if name == "SinceSecond":
+            return None if len(full) == 1 and full[0] in _OBJ else "SinceSecond of something other than pod / node"
+    for x in n[1:] if isinstance(n[0], str) else n:
+        r = usage_bad_clock(x)
+        if r:
+            return r
+    return None
+
+
+@dataclass
+class _Dyn:
+    kind: str                      # "double" | "quantity" | "bool"
+    code: List[Tuple[int, float]]
+
+
+def _go_qfloat(x: float) -> float:
+    return _from_float(x).approx()
+
+
+def lower_usage(ast, pod=None, node=None, container=None):
+    """The value of a usage expression for one (pod, node, container) as a function of the clock:
+    -> a float (no clock read is left: the constant, as_float64 of the evaluator's value) or a
+    postfix program [(op, operand)] over doubles that gives evaluate_float64 at the scrape's now.
+    Raises CELError where the evaluator errors whatever the clock says (the usage is then 0) and
+    UsageLowerError for what has no device form."""
+    vars = {"node": Obj("Node", node or {}), "pod": Obj("Pod", pod or {}),
+            "container": Obj("Container", container or {})}
+    static = Evaluator(Env(), vars)
+
+    def code_of(v, what) -> Tuple[str, List[Tuple[int, float]]]:
+        """kind and code of an operand (a folded value becomes one CONST)."""
+        if isinstance(v, _Dyn):
+            return v.kind, v.code
+        if isinstance(v, bool):
+            return "bool", [(OP_CONST, 1.0 if v else 0.0)]
+        if isinstance(v, float):
+            return "double", [(OP_CONST, v)]
+        if isinstance(v, Quantity):
+            return "quantity", [(OP_CONST, v.approx())]
+        if isinstance(v, UInt):
+            return "uint", []
+        if isinstance(v, int):
+            return "int", []
+        return type_name(v), []
+
+    def pe(n):
+        if not usage_reads_clock(n):
+            return static.ev(n)
+        k = n[0]
+        if k in ("method", "call"):
+            name = n[2] if k == "method" else n[1]
+            full = ([n[1]] if k == "method" else []) + list(n[3] if k == "method" else n[2])
+            if name == "SinceSecond" and len(full) == 1 and full[0] in _OBJ:
+                return _Dyn("double", [(OP_LOAD, IN_POD_SINCE if full[0] == _OBJ[0] else IN_NODE_SINCE)])
+            if name == "UnixSecond" and len(full) == 1 and full[0] in _NOW:
+                return _Dyn("double", [(OP_LOAD, IN_NOW_S)])
+            if name in ("Now", "now") or any(a in _NOW for a in full):
+                raise UsageLowerError("Now() other than Now().UnixSecond() has no device form")
+            if name == "SinceSecond":
+                raise UsageLowerError("SinceSecond of something other than pod / node")
+            if name == "double" and k == "call" and len(full) == 1:
+                v = pe(full[0])
+                kind, code = code_of(v, "double()")
+                if kind in ("double", "quantity"):
+                    return _Dyn("double", code)
+                raise UsageLowerError(f"double() of a clock-dependent {kind}")
+            raise UsageLowerError(f"{name}() of a clock-dependent value has no device form")
+        if k == "cond":
+            c = pe(n[1])
+            if not isinstance(c, _Dyn):
+                if not isinstance(c, bool):
+                    raise CELError("no such overload: ternary condition")
+                return pe(n[2]) if c else pe(n[3])  # CEL's short circuit: only the taken branch
+            if c.kind != "bool":
+                raise CELError("no such overload: ternary condition")
+            try:
+                a, b = pe(n[2]), pe(n[3])
+            except CELError as e:
+                raise UsageLowerError(f"an error that depends on a clock-dependent condition: {e}")
+            (ka, ca), (kb, cb) = code_of(a, "?:"), code_of(b, "?:")
+            if ka != kb or ka not in ("double", "quantity", "bool"):
+                raise UsageLowerError(f"branches of types {ka} / {kb} under a clock-dependent condition")
+            return _Dyn(ka, c.code + ca + cb + [(OP_SELECT, 0.0)])
+        if k == "unary":
+            v = pe(n[2])
+            kind, code = code_of(v, n[1])
+            if n[1] == "-" and kind in ("double", "quantity"):
+                return _Dyn(kind, code + [(OP_NEG, 0.0)])
+            if n[1] == "!" and kind == "bool":
+                raise UsageLowerError("! of a clock-dependent condition has no device form")
+            raise CELError(f"no such overload: {n[1]}{kind}")
+        if k == "binary":
+            op = n[1]
+            if op in ("&&", "||"):
+                for side in (n[2], n[3]):
+                    try:
+                        v = pe(side)
+                    except CELError:
+                        continue
+                    if isinstance(v, bool) and v is (op == "||"):  # decides the result whatever the other side gives
+                        return v
+                raise UsageLowerError(f"{op} of a clock-dependent condition has no device form")
+            a, b = pe(n[2]), pe(n[3])
+            (ka, ca), (kb, cb) = code_of(a, op), code_of(b, op)
+            if op in ("<", "<=", ">", ">="):
+                if ka == "double" and kb == "double":
+                    return _Dyn("bool", ca + cb + [({"<": OP_LT, "<=": OP_LE, ">": OP_GT, ">=": OP_GE}[op], 0.0)])
+                if ka == "quantity" and kb == "quantity":
+                    raise UsageLowerError("comparison of a clock-dependent Quantity has no device form")
+                if ka == "bool" and kb == "bool":
+                    raise UsageLowerError("comparison of clock-dependent conditions has no device form")
+                raise CELError(f"no such overload: {ka} {op} {kb}")
+            if op in ("==", "!=", "in"):
+                raise UsageLowerError(f"{op} of a clock-dependent value has no device form")
+            if op in ("+", "-", "*", "/"):
+                aop = {"+": OP_ADD, "-": OP_SUB, "*": OP_MUL, "/": OP_DIV}[op]
+                if ka == "double" and kb == "double":
+                    return _Dyn("double", ca + cb + [(aop, 0.0)])
+                if ka == "quantity" and kb == "quantity" and op in ("+", "-"):
+                    return _Dyn("quantity", ca + cb + [(aop, 0.0)])
+                if ka == "quantity" and kb == "double" and op in ("*", "/"):
+                    return _Dyn("quantity", ca + cb + [(aop, 0.0), (OP_QFLOAT, 0.0)])
+                if ka == "quantity" and kb in ("int", "uint") and op in ("*", "/"):
+                    raise UsageLowerError(f"clock-dependent Quantity {op} int (nano arithmetic) has no device form")
+            raise CELError(f"no such overload: {ka} {op} {kb}")
+        raise UsageLowerError(f"{k} of a clock-dependent value has no device form")
+
+    v = pe(ast)
+    if not isinstance(v, _Dyn):
+        return as_float64(v)
+    depth = top = 0
+    for op, _ in v.code:
+        depth += usage_op_effect(op)
+        top = max(top, depth)
+    if len(v.code) > USAGE_MAX_OPS:
+        raise UsageLowerError(f"more than {USAGE_MAX_OPS} ops ({len(v.code)})")
+    if top > USAGE_MAX_DEPTH:
+        raise UsageLowerError(f"stack depth {top} beyond {USAGE_MAX_DEPTH}")
+    return v.code
+
+
+def usage_op_effect(op: int) -> int:
+    """Net stack effect of one op."""
+    if op in (OP_CONST, OP_LOAD):
+        return 1
+    if op in (OP_NEG, OP_QFLOAT):
+        return 0
+    return -2 if op == OP_SELECT else -1
+
+
+def zero_time_unix_second() -> float:
+    """creationTimestamp.UnixSecond() of an unset timestamp (UnixNano wraps)."""
+    return GO_ZERO_TIME.unix_second()
+
+
+def run_usage_program(ops, now_ns: int, pod_created_ns: Optional[int], node_created_ns: Optional[int]) -> float:
+    """What the usage kernel computes for one pod: the program of lower_usage at now_ns, with the
+    pod's and its node's creationTimestamp (unix ns; None: unset, the Go zero time)."""
+    def since(c):
+        ct = GO_ZERO_TIME.ns if c is None else c
+        return _dur_seconds(clamp_int64(now_ns - ct))
+
+    def created(c):
+        return zero_time_unix_second() if c is None else float(c) / 1e9
+
+    def div(a, b):
+        if b == 0.0:
+            return math.copysign(math.inf, a) * math.copysign(1.0, b) if a != 0 and a == a else math.nan
+        return a / b
+
+    stk: List[float] = []
+    for op, x in ops:
+        if op == OP_CONST:
+            stk.append(float(x))
+        elif op == OP_LOAD:
+            x = int(x)
+            if x not in USAGE_LOADS:
+                raise ValueError(f"usage program loads input {x}")
+            stk.append(float(now_ns) / 1e9 if x == IN_NOW_S else since(pod_created_ns) if x == IN_POD_SINCE
+                       else since(node_created_ns) if x == IN_NODE_SINCE
+                       else created(pod_created_ns) if x == IN_POD_CREATED else created(node_created_ns))
+        elif op == OP_NEG:
+            stk[-1] = -stk[-1]
+        elif op == OP_QFLOAT:
+            stk[-1] = _go_qfloat(stk[-1])
+        elif op == OP_SELECT:
+            b, a, c = stk.pop(), stk.pop(), stk.pop()
+            stk.append(a if c != 0.0 else b)
+        else:
+            b, a = stk.pop(), stk.pop()
+            if op == OP_ADD:
+                stk.append(a + b)
+            elif op == OP_SUB:
+                stk.append(a - b)
+            elif op == OP_MUL:
+                stk.append(a * b)
+            elif op == OP_DIV:
+                stk.append(div(a, b))
+            elif op in (OP_LT, OP_LE, OP_GT, OP_GE):
+                stk.append(1.0 if {OP_LT: a < b, OP_LE: a <= b, OP_GT: a > b, OP_GE: a >= b}[op] else 0.0)
+            else:
+                raise ValueError(f"usage program op {op}")
+    if len(stk) != 1:
+        raise ValueError("a usage program leaves one value")
+    return stk[0]

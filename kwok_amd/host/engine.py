@@ -396,16 +396,27 @@ class Engine:
         return out
 
     # usage
-    def usage_config(self, node_ptr, usage_key, cpu_values, mem_values, mixed=None, ckeys=None):
+    def usage_config(self, node_ptr, usage_key, cpu_values, mem_values, mixed=None, ckeys=None, cpu_progs=None,
+                     mem_progs=None, ops=None):
         """kwk_usage_config (+ kwk_usage_mixed when some pod's containers differ): the columns
-        usage.usage_columns computes."""
+        usage.usage_columns computes; with cpu_progs / mem_progs / ops (usage.usage_columns_dyn's
+        program tables, even empty ones) kwk_usage_config_dyn."""
         self._uargs = [np.ascontiguousarray(node_ptr, dtype=np.uint32), np.ascontiguousarray(usage_key, dtype=np.uint32),
                        np.ascontiguousarray(cpu_values, dtype=np.float64),
                        np.ascontiguousarray(mem_values, dtype=np.float64)]
         np_, uk, cv, mv = self._uargs
         self.n_nodes = len(np_) - 1
-        self._check(abi.lib().kwk_usage_config(self.h, self.n_nodes, abi.ptr(np_), abi.ptr(uk), len(cv), abi.ptr(cv),
-                                             len(mv), abi.ptr(mv)), "kwk_usage_config")
+        if cpu_progs is None and mem_progs is None and ops is None:
+            self._check(abi.lib().kwk_usage_config(self.h, self.n_nodes, abi.ptr(np_), abi.ptr(uk), len(cv), abi.ptr(cv),
+                                                 len(mv), abi.ptr(mv)), "kwk_usage_config")
+        else:
+            cp = np.ascontiguousarray(np.zeros((0, 2)) if cpu_progs is None else cpu_progs, dtype=np.uint32).reshape(-1, 2)
+            mp = np.ascontiguousarray(np.zeros((0, 2)) if mem_progs is None else mem_progs, dtype=np.uint32).reshape(-1, 2)
+            op = np.ascontiguousarray(np.zeros(0, dtype=abi.USAGE_OP_DTYPE) if ops is None else ops,
+                                      dtype=abi.USAGE_OP_DTYPE)
+            self._check(abi.lib().kwk_usage_config_dyn(self.h, self.n_nodes, abi.ptr(np_), abi.ptr(uk), len(cv), abi.ptr(cv),
+                                                     len(cp), abi.ptr(cp), len(mv), abi.ptr(mv), len(mp), abi.ptr(mp),
+                                                     len(op), abi.ptr(op)), "kwk_usage_config_dyn")
         mixed = np.zeros(0, dtype=np.uint32) if mixed is None else np.ascontiguousarray(mixed, dtype=np.uint32)
         ckeys = np.zeros(0, dtype=np.uint32) if ckeys is None else np.ascontiguousarray(ckeys, dtype=np.uint32)
         if len(mixed) or np.any((uk >> 28) == 0):

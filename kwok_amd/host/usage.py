@@ -8,12 +8,20 @@ entry with no containers) and ``evaluateContainerResourceUsage`` (:136-168: a st
 ``value`` via AsApproximateFloat64, or a CEL ``expression`` evaluated with the pod, its node
 and the container bound — kwok_amd/host/cel.py; any error -> 0).
 
-Usage expressions are evaluated once per pod variant at ingest, so they must not depend on
-the clock or on other usages (``Now``, ``Rand``, ``SinceSecond``, ``Usage``, ...): such an
-expression is rejected at compile time rather than frozen.  The device gets, per pod, either
-one interned cpu / memory value and the number of containers that carry it, or — when the
-pod's containers differ — a {first, count} entry into a per-container key table
-(``kwk_usage_mixed``); per-node sums and all cumulative integrators run in ``usage_kernel``.
+A usage expression that does not read the clock is evaluated once per pod variant at ingest
+and interned as a constant.  One that reads it through ``pod.SinceSecond()``,
+``node.SinceSecond()`` or ``Now().UnixSecond()`` (a usage that ramps with the pod's age) is
+partially evaluated for the pod — everything clock-free folds, cel.lower_usage — and the rest
+becomes a postfix program the usage kernel runs at every scrape's ``now``
+(``kwk_usage_config_dyn``, ``usage_columns_dyn``).  ``Rand``, other usages (``Usage``,
+``CumulativeUsage``, ``StartedContainersTotal``), any other use of ``Now()`` and the forms
+the program format cannot express (clock-dependent Quantity x int, Quantity comparisons,
+errors under a clock-dependent condition, more than 64 ops or 8 stack entries) are refused with
+``UsageCompileError`` rather than frozen.  The device gets, per pod, either one interned
+cpu / memory value id (a constant or a program) and the number of containers that carry it,
+or — when the pod's containers differ — a {first, count} entry into a per-container key table
+(``kwk_usage_mixed``); per-node sums and all cumulative integrators run in ``usage_kernel`` /
+its clock-dependent variant.
 """
 from __future__ import annotations
 
@@ -24,29 +32,12 @@ import numpy as np
 import yaml
 
 from . import cel
+from .abi import USAGE_OP_DTYPE
 from .quantity import parse_quantity_or_none
 
 
 class UsageCompileError(ValueError):
     pass
-
-
-_CLOCKED = ("Now", "now", "Rand", "SinceSecond", "Usage", "CumulativeUsage", "StartedContainersTotal",
-            "startedContainersTotal")
-
-
-def _reads_clock(ast) -> bool:
-    if not isinstance(ast, tuple):
-        return False
-    if ast[0] in ("call", "method") and ast[1 if ast[0] == "call" else 2] in _CLOCKED:
-        return True
-    for x in ast[1:]:
-        if isinstance(x, tuple) and _reads_clock(x):
-            return True
-        if isinstance(x, list) and any(_reads_clock(y) if isinstance(y, tuple) and isinstance(y[0], str)
-                                       else any(_reads_clock(z) for z in y) for y in x):
-            return True
-    return False
 
 
 @dataclass
@@ -65,8 +56,14 @@ class UsageValue:
                 ast = cel.compile(self.expression)
             except cel.CELSyntaxError:
                 return ("const", 0.0)  # Compile fails -> 0 (metrics_resource_usage.go:150-155)
-            if _reads_clock(ast):
-                raise UsageCompileError(f"usage expression depends on the clock / other usages: {self.expression!r}")
+            bad = cel.usage_refused_call(ast)
+            if bad is not None:
+                raise UsageCompileError(f"usage expression calls {bad}: {self.expression!r}")
+            if cel.usage_reads_clock(ast):
+                bad = cel.usage_bad_clock(ast)
+                if bad is not None:
+                    raise UsageCompileError(f"usage expression reads {bad}: {self.expression!r}")
+                return ("dyn", self.expression, ast)
             return ("cel", self.expression)
         return ("const", 0.0)
 
@@ -171,7 +168,18 @@ class UsageProgram:
 
     def container_value(self, pod: dict, container: str, resource: str, node: Optional[dict] = None) -> float:
         """evaluateContainerResourceUsage (:136-168) for the container named `container` (the
-        first with that name, as containerResourceUsage's slices.Find, :111-134)."""
+        first with that name, as containerResourceUsage's slices.Find, :111-134), where it does
+        not depend on the clock."""
+        v = self.container_program(pod, container, resource, node)
+        if not isinstance(v, float):
+            raise UsageCompileError(f"the {resource} usage of container {container!r} of pod "
+                                    f"{(pod.get('metadata') or {}).get('name', '')!r} depends on the clock: "
+                                    "use usage_columns_dyn")
+        return v
+
+    def container_program(self, pod: dict, container: str, resource: str, node: Optional[dict] = None):
+        """container_value, or — for an expression that reads the clock — its program for this pod
+        (a tuple of (op, operand), cel.lower_usage)."""
         md = pod.get("metadata") or {}
         u = self._entry(md.get("name", ""), md.get("namespace", ""), container)
         if u is None or u.usage is None:
@@ -183,6 +191,14 @@ class UsageProgram:
         if c[0] == "const":
             return c[1]
         cobj = next((x for x in (pod.get("spec") or {}).get("containers") or [] if x.get("name", "") == container), {})
+        if c[0] == "dyn":
+            try:
+                r = cel.lower_usage(c[2], pod=pod, node=node or {}, container=cobj)
+            except cel.CELError:
+                return 0.0  # an error whatever the clock says
+            except cel.UsageLowerError as e:
+                raise UsageCompileError(f"usage expression {c[1]!r}: {e}")
+            return r if isinstance(r, float) else tuple(r)
         try:
             return cel.evaluate_float64(c[1], node=node or {}, pod=pod, container=cobj)
         except cel.CELError:
@@ -192,6 +208,12 @@ class UsageProgram:
         """(cpu, memory) of each of the pod's containers, in spec order."""
         names = [c.get("name", "") for c in (pod.get("spec") or {}).get("containers") or []]
         return [(self.container_value(pod, n, "cpu", node), self.container_value(pod, n, "memory", node)) for n in names]
+
+    def pod_container_programs(self, pod: dict, node: Optional[dict] = None) -> List[tuple]:
+        """pod_container_values where a value may be a program (container_program)."""
+        names = [c.get("name", "") for c in (pod.get("spec") or {}).get("containers") or []]
+        return [(self.container_program(pod, n, "cpu", node), self.container_program(pod, n, "memory", node))
+                for n in names]
 
 
 def usage_columns(program: UsageProgram, pods: Sequence[dict], nodes: Optional[Dict[str, dict]] = None):
@@ -229,3 +251,88 @@ def usage_columns(program: UsageProgram, pods: Sequence[dict], nodes: Optional[D
     cv = np.array(sorted(cpu_ids, key=cpu_ids.get), dtype=np.float64) if cpu_ids else np.zeros(1)
     mv = np.array(sorted(mem_ids, key=mem_ids.get), dtype=np.float64) if mem_ids else np.zeros(1)
     return keys, cv, mv, np.array(mixed, dtype=np.uint32), np.array(ckeys, dtype=np.uint32)
+
+
+OP_DTYPE = USAGE_OP_DTYPE  # kwk_metric_op
+
+
+def usage_columns_dyn(program: UsageProgram, pods: Sequence[dict], nodes: Optional[Dict[str, dict]] = None):
+    """usage_columns for programs with clock-dependent expressions (kwk_usage_config_dyn):
+    -> usage_key, cpu_values, mem_values, mixed, ckeys as usage_columns, then
+    cpu_progs u32[n_cpu_progs, 2], mem_progs u32[n_mem_progs, 2] = {first_op, n_ops} and
+    ops (OP_DTYPE).  A value id v < len(cpu_values) is the constant cpu_values[v], an id
+    len(cpu_values) <= v < len(cpu_values) + len(cpu_progs) is program v - len(cpu_values); memory
+    alike; constants and programs share the 14-bit id space.  Programs are interned by their op
+    bytes.  Without a clock-dependent value this is usage_columns with empty program tables."""
+    PROG = 1 << 20  # provisional ids of programs, rebased past the constants at the end
+    ids = ({}, {})       # per resource: constant -> id
+    pids = ({}, {})      # per resource: program bytes -> program index
+    ptab = ([], [])      # per resource: [first_op, n_ops]
+    oplist: List[tuple] = []
+    interned: Dict[bytes, Tuple[int, int]] = {}
+    ukeys: List[tuple] = []   # (cpu id, mem id, containers) or (mixed index,)
+    mixed: List[int] = []
+    cks: List[tuple] = []
+    memo: Dict[tuple, int] = {}
+
+    def pack(prog) -> bytes:
+        a = np.zeros(len(prog), dtype=OP_DTYPE)
+        for i, (op, x) in enumerate(prog):
+            a[i] = (op, int(x), 0.0) if op == cel.OP_LOAD else (op, 0, float(x) if op == cel.OP_CONST else 0.0)
+        return a.tobytes()
+
+    def one(r, v):
+        if isinstance(v, float):
+            return ids[r].setdefault(v, len(ids[r]))
+        b = pack(v)
+        i = pids[r].get(b)
+        if i is None:
+            span = interned.get(b)
+            if span is None:
+                span = interned[b] = (len(oplist), len(v))
+                oplist.append(b)
+            i = pids[r][b] = len(ptab[r])
+            ptab[r].append(span)
+        return PROG | i
+
+    def vid(c, m):
+        ci, mi = one(0, c), one(1, m)
+        for r in (0, 1):
+            if len(ids[r]) + len(ptab[r]) > 1 << 14:
+                raise UsageCompileError("more than 16384 distinct usage values and programs")
+        return ci, mi
+
+    for p in pods:
+        node = (nodes or {}).get((p.get("spec") or {}).get("nodeName", ""))
+        vals = program.pod_container_programs(p, node)
+        if 1 <= len(vals) <= 15 and all(v == vals[0] for v in vals):
+            ukeys.append(vid(*vals[0]) + (len(vals),))
+            continue
+        t = tuple(vals)
+        m = memo.get(t)
+        if m is None:
+            m = memo[t] = len(mixed) // 2
+            mixed += [len(cks), len(vals)]
+            cks += [vid(c, mm) for c, mm in vals]
+        ukeys.append((m,))
+    cv = np.array(sorted(ids[0], key=ids[0].get), dtype=np.float64) if ids[0] else np.zeros(1)
+    mv = np.array(sorted(ids[1], key=ids[1].get), dtype=np.float64) if ids[1] else np.zeros(1)
+    if len(cv) + len(ptab[0]) > 1 << 14 or len(mv) + len(ptab[1]) > 1 << 14:
+        raise UsageCompileError("more than 16384 distinct usage values and programs")
+
+    def final(ci, mi):
+        ci = len(cv) + (ci ^ PROG) if ci & PROG else ci
+        mi = len(mv) + (mi ^ PROG) if mi & PROG else mi
+        return ci | (mi << 14)
+
+    keys = np.array([k[0] if len(k) == 1 else final(k[0], k[1]) | (k[2] << 28) for k in ukeys], dtype=np.uint32)
+    ckeys = np.array([final(c, m) for c, m in cks], dtype=np.uint32)
+    # the op array: each interned program's ops, in order; spans were recorded in programs, so
+    # turn them into op offsets
+    firsts, pos = [], 0
+    for b in oplist:
+        firsts.append(pos)
+        pos += len(b) // OP_DTYPE.itemsize
+    ops = np.frombuffer(b"".join(oplist), dtype=OP_DTYPE).copy() if oplist else np.zeros(0, dtype=OP_DTYPE)
+    tabs = [np.array([[firsts[f], n] for f, n in t], dtype=np.uint32).reshape(-1, 2) for t in ptab]
+    return keys, cv, mv, np.array(mixed, dtype=np.uint32), ckeys, tabs[0], tabs[1], ops
