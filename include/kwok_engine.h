@@ -562,6 +562,84 @@ kwk_status kwk_usage_config_dyn(kwk_engine* eng, uint32_t n_nodes, const uint32_
                                 uint32_t n_cpu, const double* cpu_values, uint32_t n_cpu_progs, const kwk_usage_prog* cpu_progs,
                                 uint32_t n_mem, const double* mem_values, uint32_t n_mem_progs, const kwk_usage_prog* mem_progs,
                                 uint32_t n_ops, const kwk_metric_op* ops);
+
+/* Incremental usage updates: what an informer event changes, without a reconfiguration.  The node
+ * integrators, node_ptr and the chunks are not touched (a slot belongs to its node's range; a pod
+ * that moves to another node is a kwk_delete of the old slot and a row for the new one), every
+ * integrator of a slot no row names lives on, and the update is ordered on the engine's stream
+ * before the next kwk_usage.
+ *
+ * kwk_usage_set_rows gives the pod in each row's slot a new usage_key: the uniform form (value
+ * ids and 1..15 containers) or a mixed index with a 0 container count.
+ *   KWK_USAGE_ROW_RESET    another pod took the slot: its first evaluation only records the time,
+ *                          its integrators (unit and per container) and kept program values are 0.
+ *                          Without it the pod is the same and only its value changed: the
+ *                          integrators continue.  A uniform pod whose containers now differ (a
+ *                          mixed key) gives each container the total they shared; a mixed pod
+ *                          with more containers keeps its first containers' totals, and the new
+ *                          ones integrate from the pod's last evaluation (the time of the last
+ *                          evaluation is kept per pod).  A mixed pod that turns uniform starts
+ *                          its one shared integrator at 0: differing totals have no uniform form.
+ *   KWK_USAGE_ROW_CREATED  the slot's creation time (kwk_metrics_inputs' pod_created_ns column,
+ *                          read by usage programs and Metric programs) becomes created_ns
+ *                          (INT64_MIN = unset); KWK_ESTATE when no inputs are loaded.
+ * KWK_EINVAL with a message naming the row, and nothing changed: a slot at or beyond
+ * node_ptr[n_nodes], a value id or mixed index outside the tables, a slot named twice in the call.
+ * KWK_ESTATE before any kwk_usage_config.  *layout_changed (may be null) = 1 when some slot's
+ * container count changed: that shifts the container-series layout (cptr) of kwk_metrics_eval*,
+ * kwk_usage_read_containers and the exposition; the engine rebuilds its own lazily, the caller
+ * follows the call with kwk_expo_commit.
+ * A mixed pod's per-container integrators are a range of their own: a row reuses the slot's old
+ * range when it is large enough, else it takes a new one at the end of the buffer, which grows
+ * geometrically.  Abandoned ranges are reclaimed only by the next full kwk_usage_mixed.
+ * A call whose keys are all in use or in the tables, whose container counts fit the old ranges
+ * and whose size an earlier call had makes no stream synchronisation and no device allocation
+ * (kwk_usage_info's counters): one staged copy and one kernel launch.
+ * The three calls check their arguments first and change nothing when they refuse them.  A
+ * KWK_EHIP (a failed allocation or copy) after that can leave the host mirrors ahead of the
+ * device: the usage configuration is then undefined until the next full kwk_usage_config. */
+#define KWK_USAGE_ROW_RESET (1u << 0)
+#define KWK_USAGE_ROW_CREATED (1u << 1)
+typedef struct {
+  uint32_t slot, usage_key, flags, reserved;
+  int64_t created_ns;
+} kwk_usage_row; /* 24 bytes */
+kwk_status kwk_usage_set_rows(kwk_engine* eng, uint32_t n, const kwk_usage_row* rows, uint32_t* layout_changed);
+/* Appends constants and / or programs to the value tables; ids continue where the tables end,
+ * under kwk_usage_config_dyn's id rule (an id below n_cpu is a constant, ids past it programs).
+ * So constants can be appended only while the engine has no program of either resource
+ * (KWK_ESTATE otherwise: send the constant as a one-op KWK_MOP_CONST program).  A program's
+ * first_op indexes the engine's op table as it is after the append (the n_ops new ops follow the
+ * old ones), so programs may share earlier ops.  Programs are checked as kwk_usage_config_dyn
+ * checks them; 16384 ids per resource.  An engine that gets its first program needs
+ * kwk_metrics_inputs before the next kwk_usage (KWK_ESTATE there without them).  Synchronises. */
+kwk_status kwk_usage_append(kwk_engine* eng, uint32_t n_cpu, const double* cpu_values, uint32_t n_cpu_progs,
+                            const kwk_usage_prog* cpu_progs, uint32_t n_mem, const double* mem_values,
+                            uint32_t n_mem_progs, const kwk_usage_prog* mem_progs, uint32_t n_ops,
+                            const kwk_metric_op* ops);
+/* Appends {first, count} entries and container keys to kwk_usage_mixed's tables (creating them
+ * where the engine has none); indices continue, `first` indexes the container keys as they are
+ * after the append; at most 2^28 - 1 entries.  Synchronises. */
+kwk_status kwk_usage_mixed_append(kwk_engine* eng, uint32_t n_mixed, const uint32_t* mixed, uint32_t n_ckeys,
+                                  const uint32_t* ckeys);
+/* which kernel the next kwk_usage takes, the table sizes, and counters since the engine's creation */
+#define KWK_USAGE_KERNEL_FAST8 0u      /* usage_fast_kernel over the 1-byte key column */
+#define KWK_USAGE_KERNEL_FAST32 1u     /* usage_fast_kernel over the 4-byte keys */
+#define KWK_USAGE_KERNEL_GENERAL 2u    /* usage_kernel (per-pod outputs, mixed pods, large tables) */
+#define KWK_USAGE_KERNEL_PROGRAMS 3u   /* usage_kernel evaluating usage programs */
+typedef struct {
+  uint32_t kernel;            /* KWK_USAGE_KERNEL_* */
+  uint32_t n_pods, n_cpu, n_mem, n_cpu_progs, n_mem_progs, n_ops, n_mixed, n_ckeys;
+  uint32_t n_keys8;           /* distinct keys of the 1-byte dictionary (0: no 1-byte column) */
+  uint32_t max_containers;    /* of a uniform key in use */
+  uint32_t fused_counts;      /* 1: kwk_aggregate(<= 4 masks, KWK_AGG_USAGE) counts inside the usage kernel */
+  uint64_t mixed_pods;        /* pods with a mixed key */
+  uint64_t n_integrators;     /* per-container integrators handed out (abandoned ranges included) */
+  uint64_t row_calls;         /* kwk_usage_set_rows calls */
+  uint64_t syncs, allocs;     /* stream synchronisations / device allocations made by kwk_usage_set_rows,
+                                 kwk_usage_append and kwk_usage_mixed_append */
+} kwk_usage_info;
+kwk_status kwk_usage_info_get(kwk_engine* eng, kwk_usage_info* out);
 /* every metric's series for the scrape of nodes [node_first, node_first + n_nodes) at now_ns
  * (after kwk_usage(now_ns)): metric by metric, node series per node, pod series per pod slot,
  * container series per container (kwk_usage_read_containers order); NaN for dead pods.

@@ -36,6 +36,7 @@
 #include "id8_compose.hpp"
 #include "errscope.hpp"
 #include "devmem.hpp"
+#include "usage_rows.hpp"
 
 namespace {
 
@@ -4936,14 +4937,31 @@ struct kwk_engine {
   DevBuf<uint4> d_uchunk;         // usage_kernel's chunks of whole nodes {first pod, end pod, first node, end node}
   uint32_t n_uchunks = 0;
   // host copies of the usage configuration (per-container reads, metric scrapes)
-  std::vector<uint32_t> h_node_ptr, h_ukey, h_mixed, h_ckeys, h_cptr;
+  std::vector<uint32_t> h_node_ptr, h_cptr;
+  usage_rows::Book ub;            // the keys, the mixed tables and what is derived from them (usage_rows.hpp)
   std::vector<double> h_cpu, h_mem;
+  std::vector<double> h_podv;     // d_podv's values (the 1-byte dictionary's kv entries are taken from it)
+  std::vector<double2> h_kv;      // d_kv's (kUKeyDict entries)
+  std::vector<kwk_usage_prog> h_cpu_progs, h_mem_progs;  // kwk_usage_append re-lays the program table
+  std::vector<kwk_metric_op> h_uops;
+  // kwk_usage_set_rows: two pinned staging slots used in turn ({the kv table, the rows}; a slot is
+  // rewritten once its copy is done), the rows on the device, capacities of the buffers that grow
+  struct RowStage {
+    HostBuf<char> buf;
+    Event copied;
+    bool pending = false;
+  };
+  RowStage row_stage[2];
+  uint32_t row_stage_cur = 0;
+  DevBuf<usage_rows::DevRow> d_rows;
+  std::vector<usage_rows::DevRow> rows_tmp;
+  size_t ccum_cap = 0, mixed_cap = 0, ckeys_cap = 0;  // entries of d_ccum (and d_cval), d_mixed, d_ckeys
+  uint64_t n_row_calls = 0, n_row_syncs = 0, n_row_allocs = 0;  // kwk_usage_info
   bool has_mixed_keys = false;
   DevBuf<uint2> d_mixed;          // {first, count} per mixed pod
   DevBuf<uint32_t> d_ckeys;
   DevBuf<double> d_ccum;          // per container of a mixed pod: {cpu, mem} integrators
   DevBuf<uint32_t> d_mbase;       // per pod: first integrator of its containers in d_ccum (mixed pods)
-  std::vector<uint32_t> h_mbase;
   DevBuf<uint32_t> d_cptr;        // per pod: first container (metric scrapes)
   // Metric CRD programs
   DevBuf<kwk_metric_op> d_mops;
@@ -6805,6 +6823,82 @@ static kwk_status ensure_dyn_outputs(kwk_engine* e) {
   return KWK_OK;
 }
 
+// usage_fast_kernel's table for the engine's values and the largest container count in use: row
+// nc = the value of a pod with nc alike containers, summed container by container
+// (podResourceUsage's order, :170-193) — what usage_kernel's loop adds.  None where the engine has
+// programs (a program's value is no table entry) or the table would not fit kUFastVals.
+// `counted`: the incremental calls' counters (kwk_usage_info); synchronises where it uploads.
+static kwk_status build_podv(kwk_engine* e, bool counted) {
+  const uint32_t n_cpu = (uint32_t)e->h_cpu.size(), n_mem = (uint32_t)e->h_mem.size(), max_nc = e->ub.max_nc();
+  const size_t nv = (size_t)n_cpu + n_mem;
+  if (e->d_podv && counted) ++e->n_row_syncs;  // (hipFree waits for the device)
+  e->d_podv.reset();
+  e->podv_n = 0;
+  e->h_podv.clear();
+  if (e->ub.n_cpu_progs + e->ub.n_mem_progs != 0 || (max_nc + 1) * nv > kUFastVals) return KWK_OK;
+  std::vector<double>& podv = e->h_podv;
+  podv.assign((max_nc + 1) * nv, 0.0);
+  for (uint32_t nc = 1; nc <= max_nc; ++nc) {
+    for (uint32_t i = 0; i < n_cpu; ++i) {
+      double v = 0.0;
+      for (uint32_t c = 0; c < nc; ++c) v += e->h_cpu[i];
+      podv[nc * nv + i] = v;
+    }
+    for (uint32_t i = 0; i < n_mem; ++i) {
+      double v = 0.0;
+      for (uint32_t c = 0; c < nc; ++c) v += e->h_mem[i];
+      podv[nc * nv + n_cpu + i] = v;
+    }
+  }
+  HIP_TRY(e->d_podv.alloc(podv.size()));
+  HIP_TRY(upload(e, e->d_podv, podv.data(), sizeof(double) * podv.size()));
+  e->podv_n = (uint32_t)podv.size();
+  if (counted) ++e->n_row_allocs, ++e->n_row_syncs;
+  return KWK_OK;
+}
+
+// the 1-byte dictionary's {cpu, mem} values (kUKeyDict entries) out of podv
+static void fill_kv(kwk_engine* e) {
+  e->h_kv.resize(kUKeyDict, make_double2(0.0, 0.0));
+  e->ub.fill_kv(e->h_podv, reinterpret_cast<double*>(e->h_kv.data()));
+}
+
+static void drop_key8(kwk_engine* e, bool counted) {
+  if ((e->d_ukey8 || e->d_kv) && counted) ++e->n_row_syncs;
+  e->d_ukey8.reset(), e->d_kv.reset();
+  e->kv_n = 0;
+  e->ub.drop_dict();
+}
+
+// the 1-byte key column and its value table, where podv exists, no pod is mixed and at most
+// kUKeyZero distinct keys are in use
+// (ready: the column configure() built with the book's dictionary in the same pass)
+static kwk_status build_key8(kwk_engine* e, bool counted, std::vector<uint8_t>* ready = nullptr) {
+  std::vector<uint8_t> k8;
+  if (ready && e->ub.key8 && e->podv_n) {
+    k8.swap(*ready);
+    e->d_ukey8.reset(), e->d_kv.reset();
+  } else {
+    drop_key8(e, counted);
+    if (!e->podv_n || !e->ub.build_dict(k8)) return KWK_OK;
+  }
+  e->h_kv.assign(kUKeyDict, make_double2(0.0, 0.0));
+  fill_kv(e);
+  HIP_TRY(e->d_ukey8.alloc(k8.size() + 16));
+  HIP_TRY(e->d_kv.alloc(kUKeyDict));
+  HIP_TRY(upload(e, e->d_ukey8, k8.data(), k8.size()));
+  HIP_TRY(upload(e, e->d_kv, e->h_kv.data(), sizeof(double2) * kUKeyDict));
+  e->kv_n = (uint32_t)e->ub.dict.size();
+  if (counted) e->n_row_allocs += 2, ++e->n_row_syncs;
+  return KWK_OK;
+}
+
+// both, for a configuration or after an update that changed what they are built from
+static kwk_status build_fast_tables(kwk_engine* e, std::vector<uint8_t>* ready_k8) {
+  if (kwk_status st = build_podv(e, false)) return st;
+  return build_key8(e, false, ready_k8);
+}
+
 kwk_status kwk_usage_config(kwk_engine* e, uint32_t n_nodes, const uint32_t* node_ptr, const uint32_t* ukey,
                             uint32_t n_cpu, const double* cpu_values, uint32_t n_mem, const double* mem_values) {
   return kwk_usage_config_dyn(e, n_nodes, node_ptr, ukey, n_cpu, cpu_values, 0, nullptr, n_mem, mem_values, 0, nullptr, 0,
@@ -6866,58 +6960,9 @@ kwk_status kwk_usage_config_dyn(kwk_engine* e, uint32_t n_nodes, const uint32_t*
   if (!chunks.empty())
     HIP_TRY(upload(e, e->d_uchunk, chunks.data(), sizeof(uint4) * chunks.size()));
   e->n_uchunks = (uint32_t)chunks.size();
-  // usage_fast_kernel's table: row nc = the value of a pod with nc alike containers, summed
-  // container by container (podResourceUsage's order, :170-193) — what usage_kernel's loop adds
-  uint32_t max_nc = 0;
-  for (uint32_t p = 0; p < n_pods; ++p) max_nc = (ukey[p] >> 28) > max_nc ? (ukey[p] >> 28) : max_nc;
   e->d_podv.reset(), e->d_ukey8.reset(), e->d_kv.reset();
   e->podv_n = 0;
   e->kv_n = 0;
-  const size_t nv = (size_t)n_cpu + n_mem;
-  if (n_progs == 0 && (max_nc + 1) * nv <= kUFastVals) {  // (a program's value is no table entry)
-    std::vector<double> podv((max_nc + 1) * nv, 0.0);
-    for (uint32_t nc = 1; nc <= max_nc; ++nc) {
-      for (uint32_t i = 0; i < n_cpu; ++i) {
-        double v = 0.0;
-        for (uint32_t c = 0; c < nc; ++c) v += cpu_values[i];
-        podv[nc * nv + i] = v;
-      }
-      for (uint32_t i = 0; i < n_mem; ++i) {
-        double v = 0.0;
-        for (uint32_t c = 0; c < nc; ++c) v += mem_values[i];
-        podv[nc * nv + n_cpu + i] = v;
-      }
-    }
-    HIP_TRY(e->d_podv.alloc(podv.size()));
-    HIP_TRY(upload(e, e->d_podv, podv.data(), sizeof(double) * podv.size()));
-    e->podv_n = (uint32_t)podv.size();
-    // distinct keys -> 1-byte column + {cpu, mem} values (the same podv entries, so the sums are
-    // bit-identical to the 4-byte-key kernel's)
-    std::vector<uint32_t> dict;
-    std::vector<uint8_t> k8(n_pods);
-    bool fits = true;
-    for (uint32_t p = 0; p < n_pods && fits; ++p) {
-      uint32_t d = 0;
-      while (d < dict.size() && dict[d] != ukey[p]) ++d;  // few distinct keys: linear search
-      if (d == dict.size()) {
-        if (dict.size() == kUKeyZero) { fits = false; break; }
-        dict.push_back(ukey[p]);
-      }
-      k8[p] = (uint8_t)d;
-    }
-    if (fits && n_pods) {
-      std::vector<double2> kv(dict.size());
-      for (size_t d = 0; d < dict.size(); ++d) {
-        const uint32_t k = dict[d], row = (k >> 28) * (uint32_t)nv;
-        kv[d] = make_double2(podv[row + (k & 0x3FFFu)], podv[row + n_cpu + ((k >> 14) & 0x3FFFu)]);
-      }
-      HIP_TRY(e->d_ukey8.alloc((size_t)n_pods + 16));
-      HIP_TRY(e->d_kv.alloc(kv.size()));
-      HIP_TRY(upload(e, e->d_ukey8, k8.data(), n_pods));
-      HIP_TRY(upload(e, e->d_kv, kv.data(), sizeof(double2) * kv.size()));
-      e->kv_n = (uint32_t)kv.size();
-    }
-  }
   DevBuf<uint32_t> d_node_ptr;
   HIP_TRY(d_node_ptr.alloc((size_t)n_nodes + 1));
   HIP_TRY(e->d_ukey.alloc((size_t)n_pods + 1));
@@ -6941,14 +6986,17 @@ kwk_status kwk_usage_config_dyn(kwk_engine* e, uint32_t n_nodes, const uint32_t*
   e->n_usage_pods = n_pods;
   e->has_mixed_keys = mixed_keys;
   e->h_node_ptr.assign(node_ptr, node_ptr + n_nodes + 1);
-  e->h_ukey.assign(ukey, ukey + n_pods);
+  std::vector<uint8_t> k8;
+  e->ub.configure(ukey, n_pods, n_cpu, n_cpu_progs, n_mem, n_mem_progs, &k8);
   e->h_cpu.assign(cpu_values, cpu_values + n_cpu);
   e->h_mem.assign(mem_values, mem_values + n_mem);
-  e->h_mixed.clear();
-  e->h_ckeys.clear();
+  e->h_cpu_progs.assign(cpu_progs, cpu_progs + n_cpu_progs);
+  e->h_mem_progs.assign(mem_progs, mem_progs + n_mem_progs);
+  e->h_uops.assign(ops, ops + (n_progs ? n_ops : 0u));
   e->h_cptr.clear();
   e->d_mixed.reset(), e->d_ckeys.reset(), e->d_ccum.reset(), e->d_cptr.reset(), e->d_mbase.reset();
-  e->h_mbase.clear();
+  e->ccum_cap = e->mixed_cap = e->ckeys_cap = 0;
+  if (kwk_status st = build_fast_tables(e, &k8)) return st;
   if (e->d_pod_cum) HIP_TRY(hipMemsetAsync(e->d_pod_cum, 0, 16 * (size_t)e->capacity, e->stream));
   if (n_progs) {
     std::vector<uint2> progs;
@@ -6978,7 +7026,7 @@ kwk_status kwk_usage_mixed(kwk_engine* e, uint32_t n_mixed, const uint32_t* mixe
     if ((ckeys[c] & 0x3FFFu) >= e->h_cpu.size() + e->n_cpu_progs || ((ckeys[c] >> 14) & 0x3FFFu) >= e->h_mem.size() + e->n_mem_progs)
       return fail(KWK_EINVAL, "ckeys value id out of range");
   for (uint32_t p = 0; p < e->n_usage_pods; ++p)
-    if ((e->h_ukey[p] >> 28) == 0 && (e->h_ukey[p] & kUKeyMixedIndex) >= n_mixed)
+    if ((e->ub.ukey[p] >> 28) == 0 && (e->ub.ukey[p] & kUKeyMixedIndex) >= n_mixed)
       return fail(KWK_EINVAL, "usage_key mixed index out of range");
   if (kwk_status st = set_dev(e)) return st;
   HIP_TRY(hipStreamSynchronize(e->stream));
@@ -6987,14 +7035,9 @@ kwk_status kwk_usage_mixed(kwk_engine* e, uint32_t n_mixed, const uint32_t* mixe
   e->h_cptr.clear();
   // integrators are per pod and container (mixed entries may be shared by pods whose containers
   // evaluate alike): each mixed pod's containers get their own range of ccum
-  e->h_mbase.assign(e->n_usage_pods, 0u);
-  uint64_t nint = 0;
-  for (uint32_t p = 0; p < e->n_usage_pods; ++p)
-    if ((e->h_ukey[p] >> 28) == 0) {
-      e->h_mbase[p] = (uint32_t)nint;
-      nint += mixed[2 * (size_t)(e->h_ukey[p] & kUKeyMixedIndex) + 1];
-      if (nint > 0xFFFFFFFFull) return fail(KWK_ECAP, "more than 2^32 containers of mixed pods");
-    }
+  const std::string bad = e->ub.set_mixed(mixed, n_mixed, ckeys, n_ckeys);
+  if (!bad.empty()) return fail(KWK_ECAP, bad);
+  const uint64_t nint = e->ub.ccum_end;
   DevBuf<uint2> d_mixed;
   HIP_TRY(d_mixed.alloc((size_t)n_mixed + 1));
   HIP_TRY(e->d_ckeys.alloc((size_t)n_ckeys + 1));
@@ -7002,22 +7045,286 @@ kwk_status kwk_usage_mixed(kwk_engine* e, uint32_t n_mixed, const uint32_t* mixe
   HIP_TRY(e->d_mbase.alloc((size_t)e->n_usage_pods + 1));
   if (n_mixed) HIP_TRY(upload(e, d_mixed, mixed, 8 * (size_t)n_mixed));
   if (n_ckeys) HIP_TRY(upload(e, e->d_ckeys, ckeys, 4 * (size_t)n_ckeys));
-  if (e->n_usage_pods) HIP_TRY(upload(e, e->d_mbase, e->h_mbase.data(), 4 * (size_t)e->n_usage_pods));
+  if (e->n_usage_pods) HIP_TRY(upload(e, e->d_mbase, e->ub.mbase.data(), 4 * (size_t)e->n_usage_pods));
   HIP_TRY(hipMemsetAsync(e->d_ccum, 0, 16 * ((size_t)nint + 1), e->stream));
   if (e->n_cpu_progs + e->n_mem_progs) {  // the containers' evaluated values, laid out as ccum
     HIP_TRY(e->d_cval.alloc(2 * ((size_t)nint + 1)));
     HIP_TRY(hipMemsetAsync(e->d_cval, 0, 16 * ((size_t)nint + 1), e->stream));
   }
-  e->h_mixed.assign(mixed, mixed + 2 * (size_t)n_mixed);
-  e->h_ckeys.assign(ckeys, ckeys + n_ckeys);
+  e->mixed_cap = (size_t)n_mixed + 1, e->ckeys_cap = (size_t)n_ckeys + 1, e->ccum_cap = (size_t)nint + 1;
   e->d_mixed = std::move(d_mixed);
+  return KWK_OK;
+}
+
+// ---- incremental usage updates (kwk_usage_set_rows, kwk_usage_append, kwk_usage_mixed_append)
+// One thread per row of a kwk_usage_set_rows call: the slot's keys, its integrator range and what
+// a reset clears (usage_rows.hpp says which).  Slots are unique within a call, so plain stores do;
+// the 1-byte key is a byte store (four rows may share a dword of that column).
+__global__ __launch_bounds__(kBlock) void usage_rows_kernel(const usage_rows::DevRow* __restrict__ rows, uint32_t n,
+                                                            usage_rows::RowTargets a) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i < n) usage_rows::write_row(rows[i], a);
+}
+
+// a stream synchronisation / a device allocation of the incremental calls (kwk_usage_info)
+static hipError_t rows_sync(kwk_engine* e) {
+  ++e->n_row_syncs;
+  return hipStreamSynchronize(e->stream);
+}
+
+// buf with room for `need` entries of `per` elements each, what it held carried over (a new
+// allocation of at least twice the old, a device copy on the stream, swap; releasing the old
+// block waits for the device)
+extern "C++" template <class T>
+static kwk_status grow_kept(kwk_engine* e, DevBuf<T>& buf, size_t& cap, size_t need, bool zero_rest, size_t per = 1) {
+  if (need <= cap && buf) return KWK_OK;
+  const size_t ncap = std::max(std::max(need, 2 * cap), (size_t)64);
+  DevBuf<T> nb;
+  HIP_TRY(nb.alloc(per * ncap));
+  ++e->n_row_allocs;
+  const size_t kept = buf ? cap : 0;
+  if (kept) HIP_TRY(hipMemcpyAsync(nb, buf, sizeof(T) * per * kept, hipMemcpyDeviceToDevice, e->stream));
+  if (zero_rest) HIP_TRY(hipMemsetAsync(nb.get() + per * kept, 0, sizeof(T) * per * (ncap - kept), e->stream));
+  HIP_TRY(rows_sync(e));
+  buf = std::move(nb);
+  cap = ncap;
+  return KWK_OK;
+}
+
+// the mixed pods' integrators (and, with programs, kept values: {cpu, mem} per container) with
+// room for the book's ranges
+static kwk_status grow_ccum(kwk_engine* e) {
+  size_t cap = e->ccum_cap;
+  if (kwk_status st = grow_kept(e, e->d_ccum, cap, (size_t)e->ub.ccum_end + 1, true, 2)) return st;
+  if (e->n_cpu_progs + e->n_mem_progs) {
+    size_t vcap = e->d_cval ? e->ccum_cap : 0;
+    if (kwk_status st = grow_kept(e, e->d_cval, vcap, cap, true, 2)) return st;
+  }
+  e->ccum_cap = cap;
+  return KWK_OK;
+}
+
+// the fast path's tables after an update: rebuilt where the largest container count, the values
+// or the set of keys no longer match them; the dictionary's new entries into h_kv (*kv_dirty: the
+// staged copy of kwk_usage_set_rows carries the table)
+static kwk_status refresh_fast_tables(kwk_engine* e, const usage_rows::Effects& fx, bool values_changed, bool* kv_dirty) {
+  *kv_dirty = false;
+  const size_t nv = e->h_cpu.size() + e->h_mem.size();
+  const bool fast = e->ub.n_cpu_progs + e->ub.n_mem_progs == 0 && (e->ub.max_nc() + 1) * nv <= kUFastVals;
+  const bool podv_ok = fast ? (e->podv_n && !values_changed && e->podv_n >= (e->ub.max_nc() + 1) * nv) : !e->podv_n;
+  if (!podv_ok) {
+    if (kwk_status st = build_podv(e, true)) return st;
+    if (e->ub.key8 && e->podv_n) {  // the same keys, their values from the new table
+      fill_kv(e);
+      *kv_dirty = true;
+    }
+  }
+  const bool want8 = e->podv_n && !e->ub.has_mixed() && e->ub.keys.size() <= usage_rows::kDictMax && e->ub.n_pods();
+  if (!want8 || fx.key8_dropped || !e->ub.key8) {
+    *kv_dirty = false;
+    for (usage_rows::DevRow& r : e->rows_tmp) r.flags &= ~usage_rows::kDevKey8;  // (entries of the dictionary that ended)
+    if (want8) return build_key8(e, true);  // (an engine that comes back to at most 255 keys)
+    drop_key8(e, true);
+    return KWK_OK;
+  }
+  if (!fx.kv_set.empty()) fill_kv(e), *kv_dirty = true;
+  e->kv_n = (uint32_t)e->ub.dict.size();
+  return KWK_OK;
+}
+
+kwk_status kwk_usage_set_rows(kwk_engine* e, uint32_t n, const kwk_usage_row* rows, uint32_t* layout_changed) {
+  ErrScope es_(e ? &e->err : nullptr);
+  if (!e || (n && !rows)) return fail(KWK_EINVAL, "null argument");
+  if (layout_changed) *layout_changed = 0;
+  if (!e->d_node_ptr) return fail(KWK_ESTATE, "kwk_usage_config must be called first");
+  if (e->has_mixed_keys && !e->d_mixed) return fail(KWK_ESTATE, "kwk_usage_mixed must be called first");
+  for (uint32_t i = 0; i < n; ++i)
+    if ((rows[i].flags & KWK_USAGE_ROW_CREATED) && (!e->d_pod_created || e->inputs_pods != e->n_usage_pods))
+      return fail(KWK_ESTATE, "row " + std::to_string(i) + ": KWK_USAGE_ROW_CREATED needs kwk_metrics_inputs first");
+  ++e->n_row_calls;
+  if (n == 0) return KWK_OK;
+  if (kwk_status st = set_dev(e)) return st;
+  usage_rows::Effects fx;
+  const std::string bad = e->ub.apply(rows, n, e->rows_tmp, fx);
+  if (!bad.empty()) return fail(KWK_EINVAL, bad);
+  // the mirrors hold the new columns from here on; the device follows on the stream
+  e->has_mixed_keys = e->ub.has_mixed();
+  if (fx.layout_changed) {
+    if (e->d_cptr) {  // rebuilt by the next reader (ensure_cptr)
+      HIP_TRY(rows_sync(e));
+      e->d_cptr.reset();
+    }
+    e->h_cptr.clear();
+    if (layout_changed) *layout_changed = 1;
+  }
+  if (e->d_mixed && (size_t)e->ub.ccum_end + 1 > e->ccum_cap)
+    if (kwk_status st = grow_ccum(e)) return st;
+  bool kv_dirty = false;
+  if (kwk_status st = refresh_fast_tables(e, fx, false, &kv_dirty)) return st;
+  // stage {kv table, rows} in the pinned slot whose last copy is done, copy, scatter
+  kwk_engine::RowStage& sg = e->row_stage[e->row_stage_cur];
+  e->row_stage_cur ^= 1u;
+  constexpr size_t kv_bytes = sizeof(double2) * kUKeyDict;
+  const size_t row_bytes = sizeof(usage_rows::DevRow) * (size_t)n;
+  if (sg.pending) {
+    if (hipEventQuery(sg.copied) != hipSuccess) {  // (two calls in flight already: wait for the older one's copy)
+      ++e->n_row_syncs;
+      HIP_TRY(hipEventSynchronize(sg.copied));
+    }
+    sg.pending = false;
+  }
+  if (sg.buf.size() < kv_bytes + row_bytes) HIP_TRY(sg.buf.alloc(kv_bytes + std::max(2 * row_bytes, (size_t)4096)));
+  HIP_TRY(sg.copied.create(hipEventDisableTiming));
+  if (e->d_rows.size() < n) {
+    if (e->d_rows) HIP_TRY(rows_sync(e));
+    HIP_TRY(e->d_rows.alloc(std::max((size_t)2 * n, (size_t)256)));
+    ++e->n_row_allocs;
+  }
+  if (kv_dirty) {
+    memcpy(sg.buf.get(), e->h_kv.data(), kv_bytes);
+    HIP_TRY(hipMemcpyAsync(e->d_kv, sg.buf.get(), kv_bytes, hipMemcpyHostToDevice, e->stream));
+  }
+  memcpy(sg.buf.get() + kv_bytes, e->rows_tmp.data(), row_bytes);
+  HIP_TRY(hipMemcpyAsync(e->d_rows, sg.buf.get() + kv_bytes, row_bytes, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipEventRecord(sg.copied, e->stream));
+  sg.pending = true;
+  const bool mixed = e->d_mixed != nullptr;
+  usage_rows::RowTargets a{e->d_ukey, e->d_ukey8, mixed ? e->d_mbase.get() : nullptr, e->d_pod_out ? e->d_pod_last.get() : nullptr,
+                           e->d_pod_cum, e->d_unit_val, mixed ? e->d_ccum.get() : nullptr, e->d_cval, e->d_pod_created};
+  hipLaunchKernelGGL(usage_rows_kernel, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, e->stream,
+                     (const usage_rows::DevRow*)e->d_rows, n, a);
+  HIP_TRY(hipGetLastError());
+  return KWK_OK;
+}
+
+kwk_status kwk_usage_append(kwk_engine* e, uint32_t n_cpu, const double* cpu_values, uint32_t n_cpu_progs,
+                            const kwk_usage_prog* cpu_progs, uint32_t n_mem, const double* mem_values,
+                            uint32_t n_mem_progs, const kwk_usage_prog* mem_progs, uint32_t n_ops,
+                            const kwk_metric_op* ops) {
+  ErrScope es_(e ? &e->err : nullptr);
+  if (!e || (n_cpu && !cpu_values) || (n_mem && !mem_values) || (n_cpu_progs && !cpu_progs) || (n_mem_progs && !mem_progs) ||
+      (n_ops && !ops))
+    return fail(KWK_EINVAL, "null argument");
+  if (!e->d_node_ptr) return fail(KWK_ESTATE, "kwk_usage_config must be called first");
+  const bool had_progs = e->n_cpu_progs + e->n_mem_progs != 0;
+  if ((n_cpu || n_mem) && had_progs)
+    return fail(KWK_ESTATE, "constants cannot be appended to value tables with programs (ids below the constants' count "
+                            "are constants): append the constant as a one-op KWK_MOP_CONST program");
+  if ((uint64_t)e->h_cpu.size() + e->n_cpu_progs + n_cpu + n_cpu_progs > 0x4000 ||
+      (uint64_t)e->h_mem.size() + e->n_mem_progs + n_mem + n_mem_progs > 0x4000)
+    return fail(KWK_EINVAL, "dictionary size: constants and programs share 16384 ids");
+  if ((uint64_t)e->h_uops.size() + n_ops > 0xFFFFFFFFull) return fail(KWK_EINVAL, "usage program ops range");
+  std::vector<kwk_metric_op> all(e->h_uops);
+  all.insert(all.end(), ops, ops + n_ops);
+  for (uint32_t i = 0; i < n_cpu_progs; ++i)
+    if (kwk_status st = check_usage_program(all.data(), cpu_progs[i], (uint32_t)all.size())) return st;
+  for (uint32_t i = 0; i < n_mem_progs; ++i)
+    if (kwk_status st = check_usage_program(all.data(), mem_progs[i], (uint32_t)all.size())) return st;
+  if (n_cpu + n_mem + n_cpu_progs + n_mem_progs + n_ops == 0) return KWK_OK;
+  if (kwk_status st = set_dev(e)) return st;
+  HIP_TRY(rows_sync(e));  // the tables below are replaced: nothing on the stream reads them any more
+  if (n_cpu) {
+    e->h_cpu.insert(e->h_cpu.end(), cpu_values, cpu_values + n_cpu);
+    HIP_TRY(e->d_cpu.alloc(e->h_cpu.size()));
+    HIP_TRY(upload(e, e->d_cpu, e->h_cpu.data(), 8 * e->h_cpu.size()));
+    ++e->n_row_allocs;
+  }
+  if (n_mem) {
+    e->h_mem.insert(e->h_mem.end(), mem_values, mem_values + n_mem);
+    HIP_TRY(e->d_mem.alloc(e->h_mem.size()));
+    HIP_TRY(upload(e, e->d_mem, e->h_mem.data(), 8 * e->h_mem.size()));
+    ++e->n_row_allocs;
+  }
+  if (n_cpu_progs + n_mem_progs + n_ops) {
+    e->h_cpu_progs.insert(e->h_cpu_progs.end(), cpu_progs, cpu_progs + n_cpu_progs);
+    e->h_mem_progs.insert(e->h_mem_progs.end(), mem_progs, mem_progs + n_mem_progs);
+    e->h_uops = std::move(all);
+    std::vector<uint2> progs;  // the cpu programs, then memory's
+    for (const kwk_usage_prog& pr : e->h_cpu_progs) progs.push_back(make_uint2(pr.first_op, pr.n_ops));
+    for (const kwk_usage_prog& pr : e->h_mem_progs) progs.push_back(make_uint2(pr.first_op, pr.n_ops));
+    HIP_TRY(e->d_uprogs.alloc(progs.size() + 1));
+    HIP_TRY(e->d_uops.alloc(e->h_uops.size() + 1));
+    if (!progs.empty()) HIP_TRY(upload(e, e->d_uprogs, progs.data(), sizeof(uint2) * progs.size()));
+    if (!e->h_uops.empty()) HIP_TRY(upload(e, e->d_uops, e->h_uops.data(), sizeof(kwk_metric_op) * e->h_uops.size()));
+    e->n_row_allocs += 2;
+    e->n_cpu_progs = (uint32_t)e->h_cpu_progs.size();
+    e->n_mem_progs = (uint32_t)e->h_mem_progs.size();
+    e->n_uops = (uint32_t)e->h_uops.size();
+  }
+  e->ub.n_cpu = (uint32_t)e->h_cpu.size(), e->ub.n_mem = (uint32_t)e->h_mem.size();
+  e->ub.n_cpu_progs = e->n_cpu_progs, e->ub.n_mem_progs = e->n_mem_progs;
+  if (!had_progs && e->n_cpu_progs + e->n_mem_progs) {  // the first program: the kept per-container values
+    if (kwk_status st = ensure_dyn_outputs(e)) return st;
+    if (e->d_mixed) {
+      HIP_TRY(e->d_cval.alloc(2 * e->ccum_cap));
+      HIP_TRY(hipMemsetAsync(e->d_cval, 0, 16 * e->ccum_cap, e->stream));
+      ++e->n_row_allocs;
+    }
+  }
+  bool kv_dirty = false;
+  if (kwk_status st = refresh_fast_tables(e, usage_rows::Effects{}, n_cpu + n_mem != 0, &kv_dirty)) return st;
+  if (kv_dirty) HIP_TRY(upload(e, e->d_kv, e->h_kv.data(), sizeof(double2) * kUKeyDict));
+  return KWK_OK;
+}
+
+kwk_status kwk_usage_mixed_append(kwk_engine* e, uint32_t n_mixed, const uint32_t* mixed, uint32_t n_ckeys,
+                                  const uint32_t* ckeys) {
+  ErrScope es_(e ? &e->err : nullptr);
+  if (!e || (n_mixed && !mixed) || (n_ckeys && !ckeys)) return fail(KWK_EINVAL, "null argument");
+  if (!e->d_node_ptr) return fail(KWK_ESTATE, "kwk_usage_config must be called first");
+  if (e->has_mixed_keys && !e->d_mixed) return fail(KWK_ESTATE, "kwk_usage_mixed must be called first");
+  const size_t m0 = e->ub.n_mixed(), c0 = e->ub.ckeys.size();
+  const bool had_tables = e->ub.mixed_tables;
+  const std::string bad = e->ub.mixed_append(mixed, n_mixed, ckeys, n_ckeys);
+  if (!bad.empty()) return fail(KWK_EINVAL, bad);
+  if (kwk_status st = set_dev(e)) return st;
+  if (!had_tables) {  // as kwk_usage_mixed of empty tables leaves the engine
+    HIP_TRY(rows_sync(e));
+    HIP_TRY(e->d_mbase.alloc((size_t)e->n_usage_pods + 1));
+    HIP_TRY(hipMemsetAsync(e->d_mbase, 0, 4 * ((size_t)e->n_usage_pods + 1), e->stream));
+    ++e->n_row_allocs;
+    e->d_ccum.reset(), e->d_cval.reset(), e->d_mixed.reset(), e->d_ckeys.reset();
+    e->ccum_cap = e->mixed_cap = e->ckeys_cap = 0;
+    if (kwk_status st = grow_ccum(e)) return st;
+  }
+  DevBuf<uint2> d_mixed(std::move(e->d_mixed));  // the engine's again at the end (the KWK_ESTATE guard looks at it)
+  if (kwk_status st = grow_kept(e, d_mixed, e->mixed_cap, m0 + n_mixed + 1, false)) return st;
+  if (kwk_status st = grow_kept(e, e->d_ckeys, e->ckeys_cap, c0 + n_ckeys + 1, false)) return st;
+  if (n_mixed) HIP_TRY(upload(e, d_mixed.get() + m0, mixed, 8 * (size_t)n_mixed));
+  if (n_ckeys) HIP_TRY(upload(e, e->d_ckeys.get() + c0, ckeys, 4 * (size_t)n_ckeys));
+  if (n_mixed || n_ckeys) ++e->n_row_syncs;
+  e->d_mixed = std::move(d_mixed);
+  return KWK_OK;
+}
+
+static bool usage_counts(const kwk_engine* e, uint32_t n_masks);
+
+kwk_status kwk_usage_info_get(kwk_engine* e, kwk_usage_info* out) {
+  ErrScope es_(e ? &e->err : nullptr);
+  if (!e || !out) return fail(KWK_EINVAL, "null argument");
+  memset(out, 0, sizeof(*out));
+  if (e->d_node_ptr) {  // the choice enqueue_usage makes
+    const bool fast = !e->has_mixed_keys && !e->d_pod_out && e->podv_n;
+    out->kernel = fast ? (e->d_ukey8 && e->usage_key8 ? KWK_USAGE_KERNEL_FAST8 : KWK_USAGE_KERNEL_FAST32)
+                       : (e->n_cpu_progs + e->n_mem_progs ? KWK_USAGE_KERNEL_PROGRAMS : KWK_USAGE_KERNEL_GENERAL);
+    out->n_pods = e->n_usage_pods;
+    out->n_cpu = (uint32_t)e->h_cpu.size(), out->n_mem = (uint32_t)e->h_mem.size();
+    out->n_cpu_progs = e->n_cpu_progs, out->n_mem_progs = e->n_mem_progs, out->n_ops = e->n_uops;
+    out->n_mixed = e->ub.n_mixed(), out->n_ckeys = (uint32_t)e->ub.ckeys.size();
+    out->n_keys8 = e->d_ukey8 ? e->ub.dict_live() : 0u;
+    out->max_containers = e->ub.max_nc();
+    out->fused_counts = usage_counts(e, 1) ? 1u : 0u;
+    out->mixed_pods = e->ub.n_mixed_pods;
+    out->n_integrators = e->ub.ccum_end;
+  }
+  out->row_calls = e->n_row_calls, out->syncs = e->n_row_syncs, out->allocs = e->n_row_allocs;
   return KWK_OK;
 }
 
 // containers per pod of the usage configuration
 static uint32_t pod_containers(const kwk_engine* e, uint32_t p) {
-  const uint32_t k = e->h_ukey[p];
-  return (k >> 28) ? (k >> 28) : e->h_mixed[2 * (size_t)(k & kUKeyMixedIndex) + 1];
+  const uint32_t k = e->ub.ukey[p];
+  return (k >> 28) ? (k >> 28) : e->ub.mixed[2 * (size_t)(k & kUKeyMixedIndex) + 1];
 }
 
 static kwk_status ensure_cptr(kwk_engine* e) {
@@ -7041,14 +7348,47 @@ kwk_status kwk_usage_read_containers(kwk_engine* e, uint32_t first, uint32_t n, 
   if (!e->d_pod_out) return fail(KWK_ESTATE, "kwk_usage_pods(eng, 1) must be called first");
   if ((uint64_t)first + n > e->n_usage_pods) return fail(KWK_EINVAL, "pods beyond the usage configuration");
   if (e->has_mixed_keys && !e->d_mixed) return fail(KWK_ESTATE, "kwk_usage_mixed must be called first");
-  uint64_t total = 0;
+  // the mixed pods' integrator ranges lie anywhere in ccum (kwk_usage_set_rows appends ranges at
+  // the end and leaves abandoned ones behind): one copy of the span they cover while that is at most
+  // twice what is read, else one copy per pod
+  uint64_t total = 0, n_mixed_c = 0;
   uint32_t cmin = 0xFFFFFFFFu, cmax = 0;
   for (uint32_t p = first; p < first + n; ++p) {
     total += pod_containers(e, p);
-    const uint32_t k = e->h_ukey[p];
+    const uint32_t k = e->ub.ukey[p];
     if (!(k >> 28)) {
-      const uint32_t f = e->h_mbase[p], c = e->h_mixed[2 * (size_t)(k & kUKeyMixedIndex) + 1];
+      const uint32_t f = e->ub.mbase[p], c = e->ub.mixed[2 * (size_t)(k & kUKeyMixedIndex) + 1];
       if (c) { cmin = f < cmin ? f : cmin; cmax = f + c > cmax ? f + c : cmax; }
+      n_mixed_c += c;
+    }
+  }
+  const bool span = cmin < cmax && (uint64_t)(cmax - cmin) <= 2 * n_mixed_c + 1024;
+  // pod i's containers in cc / cv: pos[i] (span: their place in ccum less cmin; else packed in pod order)
+  std::vector<size_t> pos(n, 0);
+  auto gather = [&](const double* src, std::vector<double>& dst) -> hipError_t {
+    if (cmin >= cmax) return hipSuccess;
+    if (span) {
+      dst.resize(2 * (size_t)(cmax - cmin));
+      return hipMemcpy(dst.data(), src + 2 * (size_t)cmin, 16 * (size_t)(cmax - cmin), hipMemcpyDeviceToHost);
+    }
+    dst.resize(2 * (size_t)n_mixed_c);
+    for (uint32_t i = 0; i < n; ++i) {
+      const uint32_t k = e->ub.ukey[first + i];
+      const uint32_t c = (k >> 28) ? 0u : e->ub.mixed[2 * (size_t)(k & kUKeyMixedIndex) + 1];
+      if (!c) continue;
+      const hipError_t r = hipMemcpy(dst.data() + 2 * pos[i], src + 2 * (size_t)e->ub.mbase[first + i], 16 * (size_t)c,
+                                     hipMemcpyDeviceToHost);
+      if (r != hipSuccess) return r;
+    }
+    return hipSuccess;
+  };
+  {
+    size_t at = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+      const uint32_t k = e->ub.ukey[first + i];
+      if (k >> 28) continue;
+      pos[i] = span ? (size_t)(e->ub.mbase[first + i] - cmin) : at;
+      at += e->ub.mixed[2 * (size_t)(k & kUKeyMixedIndex) + 1];
     }
   }
   *n_out = (uint32_t)total;
@@ -7062,10 +7402,7 @@ kwk_status kwk_usage_read_containers(kwk_engine* e, uint32_t first, uint32_t n, 
   std::vector<double> unit(2 * (size_t)n);
   HIP_TRY(hipMemcpy(unit.data(), e->d_pod_cum + 2 * (size_t)first, 16 * (size_t)n, hipMemcpyDeviceToHost));
   std::vector<double> cc;
-  if (cmin < cmax) {
-    cc.resize(2 * (size_t)(cmax - cmin));
-    HIP_TRY(hipMemcpy(cc.data(), e->d_ccum + 2 * (size_t)cmin, 16 * (size_t)(cmax - cmin), hipMemcpyDeviceToHost));
-  }
+  HIP_TRY(gather(e->d_ccum, cc));
   // an engine with usage programs: the values the last kwk_usage evaluated, not the constants
   const bool dyn = e->n_cpu_progs + e->n_mem_progs != 0;
   std::vector<double> uv, cv;
@@ -7073,14 +7410,11 @@ kwk_status kwk_usage_read_containers(kwk_engine* e, uint32_t first, uint32_t n, 
     if (kwk_status st = ensure_dyn_outputs(e)) return st;
     uv.resize(2 * (size_t)n);
     HIP_TRY(hipMemcpy(uv.data(), e->d_unit_val + 2 * (size_t)first, 16 * (size_t)n, hipMemcpyDeviceToHost));
-    if (cmin < cmax) {
-      cv.resize(2 * (size_t)(cmax - cmin));
-      HIP_TRY(hipMemcpy(cv.data(), e->d_cval + 2 * (size_t)cmin, 16 * (size_t)(cmax - cmin), hipMemcpyDeviceToHost));
-    }
+    HIP_TRY(gather(e->d_cval, cv));
   }
   size_t o = 0;
   for (uint32_t i = 0; i < n; ++i) {
-    const uint32_t p = first + i, k = e->h_ukey[p];
+    const uint32_t p = first + i, k = e->ub.ukey[p];
     const bool alive = (st[i].y & KWK_F_ALIVE) != 0;
     if (k >> 28) {
       for (uint32_t j = 0; j < (k >> 28); ++j, o += 4) {
@@ -7090,14 +7424,13 @@ kwk_status kwk_usage_read_containers(kwk_engine* e, uint32_t first, uint32_t n, 
         out[o + 3] = alive ? unit[2 * (size_t)i + 1] : 0.0;
       }
     } else {
-      const uint32_t f = e->h_mixed[2 * (size_t)(k & kUKeyMixedIndex)], c = e->h_mixed[2 * (size_t)(k & kUKeyMixedIndex) + 1];
-      const uint32_t mb = e->h_mbase[p];
+      const uint32_t f = e->ub.mixed[2 * (size_t)(k & kUKeyMixedIndex)], c = e->ub.mixed[2 * (size_t)(k & kUKeyMixedIndex) + 1];
       for (uint32_t j = 0; j < c; ++j, o += 4) {
-        const uint32_t ck = e->h_ckeys[f + j];
-        out[o] = !alive ? 0.0 : dyn ? cv[2 * (size_t)(mb + j - cmin)] : e->h_cpu[ck & 0x3FFFu];
-        out[o + 1] = !alive ? 0.0 : dyn ? cv[2 * (size_t)(mb + j - cmin) + 1] : e->h_mem[(ck >> 14) & 0x3FFFu];
-        out[o + 2] = alive ? cc[2 * (size_t)(mb + j - cmin)] : 0.0;
-        out[o + 3] = alive ? cc[2 * (size_t)(mb + j - cmin) + 1] : 0.0;
+        const uint32_t ck = e->ub.ckeys[f + j];
+        out[o] = !alive ? 0.0 : dyn ? cv[2 * (pos[i] + j)] : e->h_cpu[ck & 0x3FFFu];
+        out[o + 1] = !alive ? 0.0 : dyn ? cv[2 * (pos[i] + j) + 1] : e->h_mem[(ck >> 14) & 0x3FFFu];
+        out[o + 2] = alive ? cc[2 * (pos[i] + j)] : 0.0;
+        out[o + 3] = alive ? cc[2 * (pos[i] + j) + 1] : 0.0;
       }
     }
   }

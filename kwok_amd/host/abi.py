@@ -160,6 +160,18 @@ METRIC_DIM = {"node": 0, "pod": 1, "container": 2}
 MOP_QFLOAT, MOP_LT, MOP_LE, MOP_GT, MOP_GE, MOP_SELECT = 8, 9, 10, 11, 12, 13
 USAGE_OP_DTYPE = np.dtype([("op", "<u4"), ("arg", "<u4"), ("value", "<f8")])  # kwk_metric_op
 USAGE_PROG_DTYPE = np.dtype([("first_op", "<u4"), ("n_ops", "<u4")])         # kwk_usage_prog
+# kwk_usage_row (kwk_usage_set_rows) and its flags
+USAGE_ROW_DTYPE = np.dtype([("slot", "<u4"), ("usage_key", "<u4"), ("flags", "<u4"), ("reserved", "<u4"),
+                            ("created_ns", "<i8")])
+USAGE_ROW_RESET, USAGE_ROW_CREATED = 1 << 0, 1 << 1
+USAGE_KERNELS = ("fast8", "fast32", "general", "programs")  # KWK_USAGE_KERNEL_*
+
+
+class UsageInfo(C.Structure):
+    """kwk_usage_info."""
+    _fields_ = [(n, C.c_uint32) for n in ("kernel", "n_pods", "n_cpu", "n_mem", "n_cpu_progs", "n_mem_progs", "n_ops",
+                                          "n_mixed", "n_ckeys", "n_keys8", "max_containers", "fused_counts")] + \
+               [(n, C.c_uint64) for n in ("mixed_pods", "n_integrators", "row_calls", "syncs", "allocs")]
 
 
 class MetricBucket(C.Structure):
@@ -183,6 +195,7 @@ assert C.sizeof(MetricOp) == 16 and C.sizeof(MetricDesc) == 16
 assert C.sizeof(MetricBucket) == 24 and C.sizeof(HistogramDesc) == 16
 assert C.sizeof(Hot) == 16 and C.sizeof(Value) == 16 and C.sizeof(StageDesc) == 96
 assert C.sizeof(Lease) == 32 == LEASE_DTYPE.itemsize and C.sizeof(LeaseParams) == 32
+assert USAGE_ROW_DTYPE.itemsize == 24 and C.sizeof(UsageInfo) == 88
 assert HOT_DTYPE.itemsize == 16 and VALUE_DTYPE.itemsize == 16 and FIRED_DTYPE.itemsize == 8
 
 # every symbol include/kwok_engine.h declares (checked by the CPU test suite)
@@ -198,7 +211,7 @@ EXPORTS = [
     "kwk_last_sweep", "kwk_tick_bind", "kwk_tick", "kwk_tick_n", "kwk_histograms_load", "kwk_histograms_eval",
     "kwk_fired_fetch", "kwk_fired_fetch_wait", "kwk_fired_keep",
     "kwk_metrics_eval_device", "kwk_histograms_eval_device", "kwk_metrics_series_device", "kwk_ring_view",
-    "kwk_usage_config_dyn",
+    "kwk_usage_config_dyn", "kwk_usage_set_rows", "kwk_usage_append", "kwk_usage_mixed_append", "kwk_usage_info_get",
 ]
 ABI_VERSION = 3  # KWK_ABI_VERSION of include/kwok_engine.h: the library must match the structs above
 TICK_COMPACT = 1 << 0  # KWK_TICK_COMPACT
@@ -283,6 +296,11 @@ def lib():
     L.kwk_usage_config_dyn.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
                                        C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
                                        C.c_uint32, C.c_void_p]
+    L.kwk_usage_set_rows.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, _p(C.c_uint32)]
+    L.kwk_usage_append.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
+                                   C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
+    L.kwk_usage_mixed_append.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
+    L.kwk_usage_info_get.argtypes = [C.c_void_p, _p(UsageInfo)]
     L.kwk_usage.argtypes = [C.c_void_p, C.c_int64]
     L.kwk_usage_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.kwk_usage_pods.argtypes = [C.c_void_p, C.c_uint32]

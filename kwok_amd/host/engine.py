@@ -428,6 +428,58 @@ class Engine:
         if np.any(mx):
             nc[mx] = mixed[1::2].astype(np.int64)[(uk[mx] & 0x0FFFFFFF).astype(np.int64)]
         self.usage_containers = nc
+        self._usage_mixed_counts = mixed[1::2].astype(np.int64)
+
+    def usage_set_rows(self, rows: np.ndarray) -> bool:
+        """kwk_usage_set_rows: rows of abi.USAGE_ROW_DTYPE (usage.UsageTable.rows) -> whether some
+        slot's container count changed (the container-series layout: follow with an exposition commit)."""
+        rows = np.ascontiguousarray(rows, dtype=abi.USAGE_ROW_DTYPE)
+        changed = C.c_uint32()
+        self._check(abi.lib().kwk_usage_set_rows(self.h, len(rows), abi.ptr(rows), C.byref(changed)), "kwk_usage_set_rows")
+        if len(rows):  # containers per pod, as usage_config keeps them
+            nc = (rows["usage_key"] >> 28).astype(np.int64)
+            mx = nc == 0
+            if np.any(mx):
+                nc[mx] = self._usage_mixed_counts[(rows["usage_key"][mx] & 0x0FFFFFFF).astype(np.int64)]
+            self.usage_containers[rows["slot"].astype(np.int64)] = nc
+        return bool(changed.value)
+
+    def usage_append(self, cpu_values=None, mem_values=None, cpu_progs=None, mem_progs=None, ops=None):
+        """kwk_usage_append: further constants and / or programs (first_op counts in the engine's
+        whole op table, the new ops following the old)."""
+        cv = np.ascontiguousarray(np.zeros(0) if cpu_values is None else cpu_values, dtype=np.float64)
+        mv = np.ascontiguousarray(np.zeros(0) if mem_values is None else mem_values, dtype=np.float64)
+        cp = np.ascontiguousarray(np.zeros((0, 2)) if cpu_progs is None else cpu_progs, dtype=np.uint32).reshape(-1, 2)
+        mp = np.ascontiguousarray(np.zeros((0, 2)) if mem_progs is None else mem_progs, dtype=np.uint32).reshape(-1, 2)
+        op = np.ascontiguousarray(np.zeros(0, dtype=abi.USAGE_OP_DTYPE) if ops is None else ops, dtype=abi.USAGE_OP_DTYPE)
+        self._check(abi.lib().kwk_usage_append(self.h, len(cv), abi.ptr(cv), len(cp), abi.ptr(cp), len(mv), abi.ptr(mv),
+                                               len(mp), abi.ptr(mp), len(op), abi.ptr(op)), "kwk_usage_append")
+
+    def usage_mixed_append(self, mixed, ckeys):
+        """kwk_usage_mixed_append: further {first, count} entries (u32[2 * n]) and container keys."""
+        mixed = np.ascontiguousarray(mixed, dtype=np.uint32).reshape(-1)
+        ckeys = np.ascontiguousarray(ckeys, dtype=np.uint32)
+        self._check(abi.lib().kwk_usage_mixed_append(self.h, len(mixed) // 2, abi.ptr(mixed), len(ckeys), abi.ptr(ckeys)),
+                    "kwk_usage_mixed_append")
+        self._usage_mixed_counts = np.concatenate([self._usage_mixed_counts, mixed[1::2].astype(np.int64)])
+
+    def usage_apply(self, update: dict) -> bool:
+        """One usage.UsageTable.rows() result: its appends, then its rows."""
+        if len(update["cpu_values"]) or len(update["mem_values"]) or len(update["cpu_progs"]) or len(update["mem_progs"]):
+            self.usage_append(update["cpu_values"], update["mem_values"], update["cpu_progs"], update["mem_progs"],
+                              update["ops"])
+        if len(update["mixed"]) or len(update["ckeys"]):
+            self.usage_mixed_append(update["mixed"], update["ckeys"])
+        return self.usage_set_rows(update["rows"])
+
+    def usage_info(self) -> dict:
+        """kwk_usage_info: the kernel the next kwk_usage takes ("fast8" | "fast32" | "general" |
+        "programs"), table sizes, and the incremental calls' counters."""
+        info = abi.UsageInfo()
+        self._check(abi.lib().kwk_usage_info_get(self.h, C.byref(info)), "kwk_usage_info_get")
+        d = {n: int(getattr(info, n)) for n, _ in abi.UsageInfo._fields_}
+        d["kernel"] = abi.USAGE_KERNELS[d["kernel"]]
+        return d
 
     def usage_read_containers(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
         """containers x {cpu, mem, cpu_cumulative, mem_cumulative} of pods [first, first+n)."""

@@ -192,6 +192,12 @@ class Exposition:
                 keys += [r[1] for r in rows]
             flush()
 
+    def layout_changed(self):
+        """After Engine.usage_set_rows returned True (some slot's container count changed): the
+        container rows' places follow the engine's new layout; set the moved pods' rows again and
+        commit()."""
+        self.cptr = np.concatenate([[0], np.cumsum(self.eng.usage_containers)]).astype(np.int64)
+
     def commit(self):
         """kwk_expo_commit: the full commit (re-reads the layout, sorts and uploads every row)."""
         self._check(lib().kwk_expo_commit(self.h), "kwk_expo_commit")
