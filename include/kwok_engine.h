@@ -227,7 +227,7 @@ kwk_status kwk_engine_destroy(kwk_engine* eng);
 #define KWK_TUNE_COMPACT_SMALL 8 /* fired hand-back: the most segments compacted in one launch (each block sums
                                    the counts before its own), 0..8192 (default 8192); more use the scan +
                                    expansion pair; 0 = always the pair */
-#define KWK_TUNE_TAIL_HANDBACK 20 /* kwk_step_n / _pair / kwk_tick on 2-byte table-only engines swept one tile per
+#define KWK_TUNE_TAIL_HANDBACK 20 /* a one-step launch of kwk_step_n / _pair / kwk_tick on 2-byte table-only engines swept one tile per
                                      workgroup (node kinds, the strong-scaling shards' node engines), at most a
                                      quarter as many workgroups as the device has CUs: 1 (default) = the sweep writes the step's
                                      list itself (each workgroup adds the counts of the ones before it, then copies
@@ -240,11 +240,13 @@ kwk_status kwk_engine_destroy(kwk_engine* eng);
 #define KWK_TUNE_WORD_TILES 10 /* word sweep (4-byte, fused and wide formats): tiles per workgroup, 1..16
                                   (exactly), or 0 (default: 8 fused, 4 otherwise, but at least 5 workgroups
                                   per CU) */
-#define KWK_TUNE_FUSE_STEPS 17 /* kwk_step_n / _pair on 1-byte engines with <= 4 stages and no delayed stage: up to
+#define KWK_TUNE_FUSE_STEPS 17 /* kwk_step_n / _pair on 1-byte engines with <= 4 stages and no delayed stage, and on
+                                  2-byte table-only engines swept one tile per workgroup: up to
                                   4 (default) or 2 steps per sweep launch (each id read once, stepped in LDS,
                                   written once; each step's fired records and hand-back kept apart), or 0 / 1 (one step
                                   per launch).  Results are bit-identical; kwk_step_stats.bytes / line_bytes count
-                                  the fused launch's own reads and writes */
+                                  the fused launch's own reads and writes on 1-byte engines, and every step as its
+                                  own launch would count it on 2-byte ones */
 kwk_status kwk_set_tuning(kwk_engine* eng, uint32_t key, uint32_t value);
 
 /* stage table + per-(class, stage) deltas; replaces the previous table (version bump) */
@@ -386,8 +388,10 @@ kwk_status kwk_fired_read(kwk_engine* eng, uint32_t format, void* out, uint64_t 
 kwk_status kwk_fired_device(kwk_engine* eng, uint32_t format, const void** list, const uint32_t** count);
 /* n steps (now0 + k * dt, step0 + k for k < n), each with its hand-back in the format `compact` when
  * compact != 0 (enqueue only): the per-tick loop of kwk_step / kwk_fired_compact in one call.
- * On 1-byte engines with <= 4 stages and no delayed stage (KWK_TUNE_FUSE_STEPS) the steps are swept
- * in launches of up to 4 steps (each id read and written once per launch) and the launch's
+ * On 1-byte engines with <= 4 stages and no delayed stage, and on 2-byte table-only engines swept
+ * one tile per workgroup (the node kinds; delayed stages included: a step sees the due times the
+ * steps before it in its launch stored) (KWK_TUNE_FUSE_STEPS), the steps are swept
+ * in launches of up to 4 steps (each id or word read and written once per launch) and the launch's
  * hand-backs run as one launch: results are those of the per-step calls, and every step's list is
  * compacted into its own ring slot (tag step0 + k), so kwk_fired_fetch(eng, step0 + k, ...)
  * reads it while the ring holds it.  The engine's list (kwk_fired_read, kwk_fired_fetch(KWK_STEP_LAST))
@@ -399,7 +403,8 @@ kwk_status kwk_fired_device(kwk_engine* eng, uint32_t format, const void** list,
 kwk_status kwk_step_n(kwk_engine* eng, uint32_t n, int64_t now0_ns, int64_t dt_ns, uint64_t seed, uint64_t step0,
                       uint32_t compact, uint32_t ev_every, uint32_t ev_j0);
 /* kwk_step_n over two engines of one shard (the pod and node kinds), enqueued launch by launch in
- * turn — eng's sweep launch (+ events) and hand-back, then as many of other's steps — so that
+ * turn — eng's sweep launch (+ events) and hand-back, then as many of other's steps, in fused
+ * launches of its own where it takes them — so that
  * neither stream waits for the host to finish enqueuing the other's n steps; events go on eng's
  * stream only, as in kwk_step_n.  Both engines' steps are tagged step0 + k in their rings.
  * Messages: eng's handle. */

@@ -358,11 +358,25 @@ __device__ __forceinline__ uint32_t match_mask(const kwk_stage_table* __restrict
   return m;
 }
 
-template <bool kProbe = false>
+// a step's clock and number: the launch's own (read from the SweepArgs where they are used), or those
+// of a later step of a fused 2-byte launch
+struct ClockOfArgs {
+  const SweepArgs& a;
+  __device__ __forceinline__ int64_t now() const { return a.now; }
+  __device__ __forceinline__ uint64_t step() const { return a.step; }
+};
+struct ClockAt {
+  int64_t now_ns;
+  uint64_t step_no;
+  __device__ __forceinline__ int64_t now() const { return now_ns; }
+  __device__ __forceinline__ uint64_t step() const { return step_no; }
+};
+
+template <bool kProbe = false, class Clock>
 __device__ __forceinline__ bool match_object(const SweepArgs& a, const kwk_stage_table* __restrict__ T,
                                              uint32_t n_stages, uint64_t i, uint32_t pred, uint32_t& sched,
                                              int64_t& due, uint32_t& bytes, const uint32_t* lut, uint32_t lut_n,
-                                             uint32_t& gen) {
+                                             uint32_t& gen, const Clock& clk) {
   const uint32_t m = match_mask(T, n_stages, pred, lut, lut_n, a.lut_bytes, a.lut_rest);
   sched &= ~(KWK_F_DIRTY | KWK_F_MATCHERR);
   if (m == 0) return false;  // no match: a queued job stays queued (pod_controller.go:222-229)
@@ -379,7 +393,7 @@ __device__ __forceinline__ bool match_object(const SweepArgs& a, const kwk_stage
   // the stages with a Delay jitter, kwk_load_stages)
   uint64_t u_pick = 0, u_jit = 0;
   if (!kProbe && (cnt > 1 || (m & T->reserved[0]))) {
-    uint32_t c0 = (uint32_t)gslot, c1 = (uint32_t)a.step, c2 = (uint32_t)(a.step >> 32), c3 = kSitePick;
+    uint32_t c0 = (uint32_t)gslot, c1 = (uint32_t)clk.step(), c2 = (uint32_t)(clk.step() >> 32), c3 = kSitePick;
     philox10(c0, c1, c2, c3, (uint32_t)a.key, (uint32_t)(a.key >> 32));
     u_pick = (uint64_t)c0 | ((uint64_t)c1 << 32);
     u_jit = (uint64_t)c2 | ((uint64_t)c3 << 32);
@@ -438,12 +452,12 @@ __device__ __forceinline__ bool match_object(const SweepArgs& a, const kwk_stage
     }
     const int64_t dels = need_del ? a.del_s[i] : KWK_DEL_ABSENT;
     if (need_del) bytes += 8;
-    const Getter d = eval_getter(S.delay_slot, S.delay_default, true, sched, rec, dels, a.now, true);
+    const Getter d = eval_getter(S.delay_slot, S.delay_default, true, sched, rec, dels, clk.now(), true);
     if (d.ok) {
       delay = d.v;
       if (S.has_jitter) {
         const Getter j = eval_getter(S.jitter_slot, S.jitter_default, S.jitter_default_ok != 0, sched, rec, dels,
-                                     a.now, true);
+                                     clk.now(), true);
         if (j.ok) {
           if (j.v < delay) {
             delay = j.v;
@@ -460,7 +474,7 @@ __device__ __forceinline__ bool match_object(const SweepArgs& a, const kwk_stage
     }
   }
   sched = (sched & ~0xFFu) | (uint32_t)pick;
-  due = sat_add(a.now, delay);  // addStageJob / AddWeightAfter (weight_delaying_queue.go:73-95)
+  due = sat_add(clk.now(), delay);  // addStageJob / AddWeightAfter (weight_delaying_queue.go:73-95)
   return true;
 }
 
@@ -510,13 +524,13 @@ __device__ __forceinline__ void fire_object(const SweepArgs& a, const kwk_stage_
 // pending past this step (a stage that fires in the same step never needs its due stored).
 // kProbe: see match_object; the due time a scheduled stage would store goes to due_w (gen and
 // due_w are unused otherwise).  kDueOut (the fused format): the due time goes to due_w and gen = 1
-// instead of the due column (the caller encodes it into the record)
-template <bool kHarness, uint32_t kWordBytes, bool kProbe = false, bool kDueOut = false>
+// instead of the due column (the caller encodes it into the record).  clk: the step's clock and number
+template <bool kHarness, uint32_t kWordBytes, bool kProbe = false, bool kDueOut = false, class Clock>
 __device__ __forceinline__ uint2 process_object(const SweepArgs& a, const kwk_stage_table* __restrict__ T,
                                                const kwk_delta* __restrict__ deltas, uint32_t n_stages,
                                                uint32_t fin_group, uint64_t i, uint32_t pred, uint32_t sched,
                                                int64_t due, Fire& f, uint32_t& n_matched, const uint32_t* lut,
-                                               uint32_t lut_n, uint32_t& gen, int64_t& due_w) {
+                                               uint32_t lut_n, uint32_t& gen, int64_t& due_w, const Clock& clk) {
   if (kHarness) {
     if (!(sched & KWK_F_ALIVE)) {  // re-create a deleted object from its spec
       pred &= a.harness.keep_mask;  // same spec: class bits and record flag stay
@@ -528,8 +542,8 @@ __device__ __forceinline__ uint2 process_object(const SweepArgs& a, const kwk_st
       }
     } else if ((pred & a.harness.terminal_mask) && !(pred & a.harness.deletion_bit)) {
       pred |= a.harness.deletion_bit;  // the user deletes a finished pod
-      int64_t sec = a.now / 1000000000;
-      if (a.now % 1000000000 < 0) sec -= 1;
+      int64_t sec = clk.now() / 1000000000;
+      if (clk.now() % 1000000000 < 0) sec -= 1;
       if (a.harness.track_deletion) {
         if constexpr (kProbe) gen = 1;
         else a.del_s[i] = sec;
@@ -547,12 +561,12 @@ __device__ __forceinline__ uint2 process_object(const SweepArgs& a, const kwk_st
         // stays queued (it still fires)
         sched &= ~KWK_F_DIRTY;
       } else {
-        scheduled = match_object<kProbe>(a, T, n_stages, i, pred, sched, due, f.bytes, lut, lut_n, gen);
+        scheduled = match_object<kProbe>(a, T, n_stages, i, pred, sched, due, f.bytes, lut, lut_n, gen, clk);
         n_matched += scheduled ? 1 : 0;
       }
     }
     const uint32_t st = sched & 0xFFu;
-    if (a.fire && st < n_stages && due <= a.now) fire_object(a, T, deltas, n_stages, fin_group, sched >> KWK_CLASS_SHIFT, st,
+    if (a.fire && st < n_stages && due <= clk.now()) fire_object(a, T, deltas, n_stages, fin_group, sched >> KWK_CLASS_SHIFT, st,
                                                    pred, sched, f);
   }
   if (scheduled && (sched & 0xFFu) < n_stages) {
@@ -568,6 +582,16 @@ __device__ __forceinline__ uint2 process_object(const SweepArgs& a, const kwk_st
   }
   f.bytes += kWordBytes;  // the state write-back (done by the caller)
   return make_uint2(pred, sched);
+}
+// at the launch's own clock (a.now, a.step): every sweep but the later steps of a fused 2-byte launch
+template <bool kHarness, uint32_t kWordBytes, bool kProbe = false, bool kDueOut = false>
+__device__ __forceinline__ uint2 process_object(const SweepArgs& a, const kwk_stage_table* __restrict__ T,
+                                               const kwk_delta* __restrict__ deltas, uint32_t n_stages,
+                                               uint32_t fin_group, uint64_t i, uint32_t pred, uint32_t sched,
+                                               int64_t due, Fire& f, uint32_t& n_matched, const uint32_t* lut,
+                                               uint32_t lut_n, uint32_t& gen, int64_t& due_w) {
+  return process_object<kHarness, kWordBytes, kProbe, kDueOut>(a, T, deltas, n_stages, fin_group, i, pred, sched, due, f,
+                                                               n_matched, lut, lut_n, gen, due_w, ClockOfArgs{a});
 }
 
 // wave-ballot compaction of the fired set into the wave's private segment + per-stage counts
@@ -613,6 +637,11 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, uint3
 }
 __device__ __forceinline__ int64_t buf_load_i64(__amdgpu_buffer_rsrc_t r, uint32_t off) {
   const auto t = __builtin_amdgcn_raw_buffer_load_b64(r, off, 0, 0);
+  return (int64_t)(((uint64_t)t[1] << 32) | t[0]);
+}
+// the same served by the L2, past the CU's vector L1 (aux 16: sc1)
+__device__ __forceinline__ int64_t buf_load_i64_sc1(__amdgpu_buffer_rsrc_t r, uint32_t off) {
+  const auto t = __builtin_amdgcn_raw_buffer_load_b64(r, off, 0, 16);
   return (int64_t)(((uint64_t)t[1] << 32) | t[0]);
 }
 
@@ -969,8 +998,11 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(Q >= 4 ?
 // kernel's SweepArgs by reference faulted twice — the one-block-per-tile Q = 1 node engine of
 // test_node_fast_heartbeat and the C5 bench — and was reverted; DESIGN.md §5 records what its ISA
 // shows and why the shared code it called is not the cause.)
-template <bool kHarness>
-__device__ __forceinline__ uint2 general16(uint32_t i, uint32_t raw) {
+// kAt: a later step of a fused launch, at its own clock and step number (now, step) instead of the
+// launch's; the item's due time may have been stored by another lane of this wave in a step before
+// (see the kernel's note on due times), so it is loaded past the vector L1
+template <bool kHarness, bool kAt = false>
+__device__ __forceinline__ uint2 general16(uint32_t i, uint32_t raw, int64_t now = 0, uint64_t step = 0) {
   // the kernel's SweepArgs (its only argument, at offset 0 of the kernarg segment) and the stage
   // table are read through a VGPR address: their values land in VGPRs, which the lookup loop
   // leaves free, instead of taking SGPRs from it (SGPR spills into VGPR lanes cost ~4 us)
@@ -981,12 +1013,20 @@ __device__ __forceinline__ uint2 general16(uint32_t i, uint32_t raw) {
   asm volatile("" : "+v"(tp));
   const kwk_stage_table* __restrict__ T = reinterpret_cast<const kwk_stage_table*>(tp);
   const uint2 s = fmt_unpack(raw, a.fmt);
-  const int64_t due = ((s.y & 0xFFu) != KWK_STAGE_NONE) ? a.due[i] : 0;
   Fire f{false, 0, 0, 0};
   uint32_t nm = 0, gen_unused = 0;
   int64_t due_unused = 0;
-  const uint2 nv = process_object<kHarness, 2>(a, T, a.deltas, T->n_stages, T->fin_group_mask, i, s.x, s.y, due, f, nm,
-                                               a.lut, a.lut_n, gen_unused, due_unused);
+  uint2 nv;
+  if constexpr (kAt) {
+    const int64_t due = ((s.y & 0xFFu) != KWK_STAGE_NONE)
+                            ? __hip_atomic_load(&a.due[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
+    nv = process_object<kHarness, 2>(a, T, a.deltas, T->n_stages, T->fin_group_mask, i, s.x, s.y, due, f, nm, a.lut,
+                                     a.lut_n, gen_unused, due_unused, ClockAt{now, step});
+  } else {
+    const int64_t due = ((s.y & 0xFFu) != KWK_STAGE_NONE) ? a.due[i] : 0;
+    nv = process_object<kHarness, 2>(a, T, a.deltas, T->n_stages, T->fin_group_mask, i, s.x, s.y, due, f, nm, a.lut,
+                                     a.lut_n, gen_unused, due_unused);
+  }
   uint32_t e = fmt_pack(nv.x, nv.y, a.fmt) & 0xFFFFu;
   e |= (f.stage & 31u) << 16 | (f.fire ? 1u : 0u) << 21 | (f.flags & 7u) << 22 | (nm & 1u) << 25;
   return make_uint2(e, f.bytes);
@@ -1078,13 +1118,33 @@ __device__ __forceinline__ void tail_handback(const SweepArgs& a, uint32_t wave_
 
 constexpr int kFsmBatch = 4;  // passes (64 work items each) whose lookups are in flight together
 constexpr uint32_t kFsmKernelDefault = 2;  // table-only sweep with its prefetch depth (0: never)
-template <bool kHarness, int Q, bool kPersist, int kDepth>
+// kSteps > 1 (one tile per workgroup only): fused steps, as sweep8_kernel's — the tile is loaded once,
+// stepped kSteps times (step s at a.nowx[s - 1] with step number a.step + s: the Philox draws and
+// general16 take that number, as separate launches would) and written once; step 0's records and
+// counts go to a.fired / a.wave_counts, step s's to a.firedx / a.countsx[s - 1] (step_group,
+// DESIGN §2).  The statistics are summed over the steps, each step counted as its own launch would
+// count it (the words it reads, the lines it would have rewritten), so that kwk_stats does not
+// depend on how a caller's steps were grouped.  The steps are a loop, not unrolled: the cold path
+// (process_object) stays one copy.
+// Due times between the steps of a launch: this table schedules delayed stages, so a step must see
+// the due times a step before it stored — by the lane that worked the item (pass / process_object),
+// while phase 1 loads them in the lane that owns the slot, of the same wave (a tile's wave region is
+// one wave's in every step).  Chosen: the stores are waited for (vmcnt(0) behind a workgroup-scope
+// release) before the next step's loads, and those loads go past the vector L1 (sc1: served by the
+// L2 the stores have reached).  The CU's write-through L1 is already coherent for one wave's own
+// program order; the sc1 loads make that independent of what a line held before the store.  A
+// table of due times in LDS beside the tile was the alternative: 16 KB per wave at Q = 1 for a
+// column of which a step touches a few percent, and general16's own loads and stores (the due
+// column through a.due, the deletion column) would still go through memory.
+template <bool kHarness, int Q, bool kPersist, int kDepth, int kSteps = 1>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(Q >= 4 ? 4 : 5))) void sweep16_fsm_kernel(SweepArgs a) {
   constexpr int K = 8 * Q;                 // words per lane
   constexpr uint32_t kWave = 64u * K;      // words per wave region
   constexpr uint32_t kTile = kBlock * K;   // words per block
   constexpr int B = kFsmBatch;
   static_assert(kDepth >= 1 && kDepth <= 2 && (kPersist || kDepth == 1), "prefetch depth");
+  static_assert(kSteps >= 1 && kSteps <= (int)kMaxFuseSteps && (kSteps == 1 || !kPersist), "fused steps: one tile per block");
+  constexpr bool kFused = kSteps > 1;
   __shared__ unsigned int s_stat[kStatWords];
   __shared__ uint16_t s_work[kWavesPerBlock][kWave];
   __shared__ uint4 s_tile[kWavesPerBlock][64 * Q];
@@ -1140,204 +1200,256 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(Q >= 4 ?
   auto tile_body = [&](uint4 (&v)[Q], const uint32_t tile) __attribute__((always_inline)) {
     const uint32_t wbase = tile * kTile + wave * kWave;
     const bool full = (uint64_t)(tile + 1) * kTile <= a.n;
+    // the segment and its records so far (fused: of the step at hand)
     uint32_t seg_n = 0;  // wave-uniform
     const uint64_t seg_id = (uint64_t)tile * kWavesPerBlock + wave;
     uint32_t* __restrict__ seg32 = reinterpret_cast<uint32_t*>(a.fired) + seg_id * kSeg16;
-    const __amdgpu_buffer_rsrc_t seg_rs = make_rsrc(seg32, kSeg16 * 4u);
+    __amdgpu_buffer_rsrc_t seg_rs = make_rsrc(seg32, kSeg16 * 4u);
     uint4 cur_copy[Q];
     if (kDepth == 1) {
 #pragma unroll
       for (int q = 0; q < Q; ++q) cur_copy[q] = v[q];
     }
     uint4 (&cur)[Q] = kDepth == 1 ? cur_copy : v;
-    // ---- phase 1 (as sweep16_kernel); in a partial tile, row q of the lane holds
-    // c = clamp(n - first word, 0, 8) words: its low words are bits q*4 + [0, (c+1)/2), its
-    // high words bits 16 + q*4 + [0, c/2) (no per-bit constants: they would pin ~25 VGPRs)
-    constexpr uint32_t kHalfMask = (1u << (4 * Q)) - 1u;
-    uint32_t in_range = kHalfMask | kHalfMask << 16;
-    if (!full) {
-      in_range = 0;
+    // fused: the words as the steps so far left them (cur stays the tile as loaded), and whether
+    // one of those steps worked, i.e. the tile sits in LDS (wave-uniform)
+    uint4 mid[kFused ? Q : 1];
+    bool in_lds = false;
+    if constexpr (kFused) {
+#pragma unroll
+      for (int q = 0; q < Q; ++q) mid[q] = cur[q];
+    }
+    // one step on the words ws (fused: step s, its clock, number and segments)
+    auto step_body = [&](uint4 (&ws)[Q], const uint32_t s) __attribute__((always_inline)) {
+      // (one launch's step reads a.now and a.wave_counts where it uses them, as it always has: where
+      // the kernel arguments are loaded decides how the compiler allocates the scalar registers)
+      const int64_t now_s = kFused && s ? a.nowx[s - 1] : 0;
+      auto now = [&]() __attribute__((always_inline)) { return kFused && s ? now_s : a.now; };
+      if (kFused && s) {
+        seg_n = 0;
+        seg32 = reinterpret_cast<uint32_t*>(a.firedx[s - 1]) + seg_id * kSeg16;
+        seg_rs = make_rsrc(seg32, kSeg16 * 4u);
+      }
+      // ---- phase 1 (as sweep16_kernel); in a partial tile, row q of the lane holds
+      // c = clamp(n - first word, 0, 8) words: its low words are bits q*4 + [0, (c+1)/2), its
+      // high words bits 16 + q*4 + [0, c/2) (no per-bit constants: they would pin ~25 VGPRs)
+      constexpr uint32_t kHalfMask = (1u << (4 * Q)) - 1u;
+      uint32_t in_range = kHalfMask | kHalfMask << 16;
+      if (!full) {
+        in_range = 0;
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+          const int64_t left = (int64_t)a.n - (int64_t)(wbase + (uint32_t)q * 512u + lane * 8u);
+          const uint32_t c = left <= 0 ? 0u : left >= 8 ? 8u : (uint32_t)left;
+          in_range |= (((1u << ((c + 1u) >> 1)) - 1u) << (4 * q)) | (((1u << (c >> 1)) - 1u) << (16 + 4 * q));
+        }
+      }
+      uint32_t pend = 0, need = 0, ready = 0;
 #pragma unroll
       for (int q = 0; q < Q; ++q) {
-        const int64_t left = (int64_t)a.n - (int64_t)(wbase + (uint32_t)q * 512u + lane * 8u);
-        const uint32_t c = left <= 0 ? 0u : left >= 8 ? 8u : (uint32_t)left;
-        in_range |= (((1u << ((c + 1u) >> 1)) - 1u) << (4 * q)) | (((1u << (c >> 1)) - 1u) << (16 + 4 * q));
-      }
-    }
-    uint32_t pend = 0, need = 0, ready = 0;
+        const uint32_t dw[4] = {ws[q].x, ws[q].y, ws[q].z, ws[q].w};
 #pragma unroll
-    for (int q = 0; q < Q; ++q) {
-      const uint32_t dw[4] = {cur[q].x, cur[q].y, cur[q].z, cur[q].w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const uint32_t d = dw[j];
-        const uint32_t mg = (d & X.m2) << X.sm;
-        const uint32_t pe = (((d & X.s2) ^ X.n2) + 0x7FFF7FFFu) & 0x80008000u;
-        uint32_t nb = (d & X.d2) << X.sd;
-        if (kHarness) {
-          nb |= (~d & X.a2) << X.sa;
-          nb |= (((d & X.t2) + 0x7FFF7FFFu) & 0x80008000u) & ~((d & X.l2) << X.sl);
+        for (int j = 0; j < 4; ++j) {
+          const uint32_t d = dw[j];
+          const uint32_t mg = (d & X.m2) << X.sm;
+          const uint32_t pe = (((d & X.s2) ^ X.n2) + 0x7FFF7FFFu) & 0x80008000u;
+          uint32_t nb = (d & X.d2) << X.sd;
+          if (kHarness) {
+            nb |= (~d & X.a2) << X.sa;
+            nb |= (((d & X.t2) + 0x7FFF7FFFu) & 0x80008000u) & ~((d & X.l2) << X.sl);
+          }
+          const uint32_t n2 = mg & nb, p2 = mg & pe;
+          const int jj = q * 4 + j;
+          need |= n2 >> (15 - jj);
+          pend |= p2 >> (15 - jj);
         }
-        const uint32_t n2 = mg & nb, p2 = mg & pe;
-        const int jj = q * 4 + j;
-        need |= n2 >> (15 - jj);
-        pend |= p2 >> (15 - jj);
       }
-    }
-    pend &= in_range;
-    need &= in_range;
-    if (__ballot(pend != 0)) {
+      pend &= in_range;
+      need &= in_range;
+      if (__ballot(pend != 0)) {
 #pragma unroll 8
-      for (int t = 0; t < K; ++t) {
-        const int k = t < 4 * Q ? t : 16 + t - 4 * Q;
-        const uint32_t p = (pend >> k) & 1u;
-        const int64_t d = buf_load_i64(due_rs, p ? (wbase + bit_word((uint32_t)k) + lane * 8u) * 8u : kOOB);
-        ready |= (p & (uint32_t)(d <= a.now)) << k;
+        for (int t = 0; t < K; ++t) {
+          const int k = t < 4 * Q ? t : 16 + t - 4 * Q;
+          const uint32_t p = (pend >> k) & 1u;
+          const int64_t d = kFused ? buf_load_i64_sc1(due_rs, p ? (wbase + bit_word((uint32_t)k) + lane * 8u) * 8u : kOOB)
+                                   : buf_load_i64(due_rs, p ? (wbase + bit_word((uint32_t)k) + lane * 8u) * 8u : kOOB);
+          ready |= (p & (uint32_t)(d <= now())) << k;
+        }
+        need |= ready;
       }
-      need |= ready;
-    }
-    n_bytes += 2u * (uint32_t)__popc(in_range) + 8u * (uint32_t)__popc(pend);
-    uint32_t n_work = 0, pos = 0;
-    {
-      const uint32_t cnt = (uint32_t)__popc(need);
-      const unsigned long long lt = (1ull << lane) - 1ull;
+      n_bytes += 2u * (uint32_t)__popc(in_range) + 8u * (uint32_t)__popc(pend);
+      uint32_t n_work = 0, pos = 0;
+      {
+        const uint32_t cnt = (uint32_t)__popc(need);
+        const unsigned long long lt = (1ull << lane) - 1ull;
 #pragma unroll
-      for (int b = 0; b < 6; ++b) {
-        const unsigned long long bal = __ballot((cnt >> b) & 1u);
-        pos += (uint32_t)__popcll(bal & lt) << b;
-        n_work += (uint32_t)__popcll(bal) << b;
+        for (int b = 0; b < 6; ++b) {
+          const unsigned long long bal = __ballot((cnt >> b) & 1u);
+          pos += (uint32_t)__popcll(bal & lt) << b;
+          n_work += (uint32_t)__popcll(bal) << b;
+        }
+        for (uint32_t m = need; m; m &= m - 1u) {
+          const uint32_t k = (uint32_t)__ffs(m) - 1u;
+          wl[pos++] = (uint16_t)(bit_word(k) + lane * 8u + (((ready >> k) & 1u) << 15));
+        }
       }
-      for (uint32_t m = need; m; m &= m - 1u) {
-        const uint32_t k = (uint32_t)__ffs(m) - 1u;
-        wl[pos++] = (uint16_t)(bit_word(k) + lane * 8u + (((ready >> k) & 1u) << 15));
-      }
-    }
-    // ---- phase 2: lookups of the first kFsmBatch passes (straight-line code, so the
-    // compiler's wait for a lookup counts the prefetch issued after it), then the prefetch
-    uint32_t we[B], raw[B], ent[B];
-    auto fetch = [&](const uint32_t c0) __attribute__((always_inline)) {
+      // ---- phase 2: lookups of the first kFsmBatch passes (straight-line code, so the
+      // compiler's wait for a lookup counts the prefetch issued after it), then the prefetch
+      uint32_t we[B], raw[B], ent[B];
+      auto fetch = [&](const uint32_t c0) __attribute__((always_inline)) {
 #pragma unroll
-      for (int b = 0; b < B; ++b) {
-        const uint32_t c = c0 + 64u * b + lane;
-        const bool in = c < n_work;
-        const uint32_t x0 = (uint32_t)wl[c & (kWave - 1u)];  // read unconditionally (no exec branch)
-        const uint32_t x = in ? x0 : 0u;
-        we[b] = in ? x : 0xFFFFFFFFu;
-        raw[b] = (uint32_t)tw[x & 0x7FFFu];
-        ent[b] = __builtin_amdgcn_raw_buffer_load_b32(fsm_rs, in ? ((((x >> 15) << fbits) | raw[b]) * 4u) : kOOB, 0, 0);
-      }
-    };
-    // fired record + per-stage counts of one 64-item pass (e: the item's table entry)
-    auto emit = [&](const bool fire, const uint32_t w, const uint32_t e) __attribute__((always_inline)) {
-      const unsigned long long bal = __ballot(fire);
-      if (bal) {
-        const uint32_t pos = seg_n + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
-        const uint32_t rec = w | ((e >> 16) & 31u) << 13 | ((e >> 22) & 7u) << 18;
-        __builtin_amdgcn_raw_buffer_store_b32(rec, seg_rs, fire ? (1u + pos) * 4u : kOOB, 0, 0);
-        const uint32_t nf = (uint32_t)__popcll(bal);
-        seg_n += nf;
-        w_bytes += 4u * nf;
-        const uint32_t code = fire ? ((e >> 16) & 31u) : 31u;
-        if (n_stages <= 4) {  // per-lane 16-bit counters, stages 0-1 / 2-3 (reduced once per block)
-          const uint32_t inc = 1u << (16u * (code & 1u));
-          stc01 += code < 2u ? inc : 0u;
-          stc23 += (code - 2u) < 2u ? inc : 0u;
-        } else {
-          for (uint32_t st = 0; st < n_stages; ++st) {  // one ballot per stage
-            const unsigned long long same = __ballot(code == st);
-            if (same && lane == 0) atomicAdd(&s_stat[3 + st], (unsigned)__popcll(same));
+        for (int b = 0; b < B; ++b) {
+          const uint32_t c = c0 + 64u * b + lane;
+          const bool in = c < n_work;
+          const uint32_t x0 = (uint32_t)wl[c & (kWave - 1u)];  // read unconditionally (no exec branch)
+          const uint32_t x = in ? x0 : 0u;
+          we[b] = in ? x : 0xFFFFFFFFu;
+          raw[b] = (uint32_t)tw[x & 0x7FFFu];
+          ent[b] = __builtin_amdgcn_raw_buffer_load_b32(fsm_rs, in ? ((((x >> 15) << fbits) | raw[b]) * 4u) : kOOB, 0, 0);
+        }
+      };
+      // fired record + per-stage counts of one 64-item pass (e: the item's table entry)
+      auto emit = [&](const bool fire, const uint32_t w, const uint32_t e) __attribute__((always_inline)) {
+        const unsigned long long bal = __ballot(fire);
+        if (bal) {
+          const uint32_t pos = seg_n + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+          const uint32_t rec = w | ((e >> 16) & 31u) << 13 | ((e >> 22) & 7u) << 18;
+          __builtin_amdgcn_raw_buffer_store_b32(rec, seg_rs, fire ? (1u + pos) * 4u : kOOB, 0, 0);
+          const uint32_t nf = (uint32_t)__popcll(bal);
+          seg_n += nf;
+          w_bytes += 4u * nf;
+          const uint32_t code = fire ? ((e >> 16) & 31u) : 31u;
+          if (n_stages <= 4) {  // per-lane 16-bit counters, stages 0-1 / 2-3 (reduced once per block)
+            const uint32_t inc = 1u << (16u * (code & 1u));
+            stc01 += code < 2u ? inc : 0u;
+            stc23 += (code - 2u) < 2u ? inc : 0u;
+          } else {
+            for (uint32_t st = 0; st < n_stages; ++st) {  // one ballot per stage
+              const unsigned long long same = __ballot(code == st);
+              if (same && lane == 0) atomicAdd(&s_stat[3 + st], (unsigned)__popcll(same));
+            }
           }
         }
-      }
-    };
-    // Items whose entry is general are deferred to one loop after the lookups (records are
-    // unordered within a region): their slots are compacted to the front of the work list,
-    // whose entries up to the current batch are already in registers; their words stay
-    // unchanged in the LDS tile until then.
-    uint32_t n_gen = 0;  // wave-uniform
-    auto pass = [&](const int b) __attribute__((always_inline)) {
-      const uint32_t cwe = we[b], e = ent[b];
-      const bool act = cwe != 0xFFFFFFFFu;
-      const uint32_t w = cwe & 0x7FFFu;
-      const bool gen = act && (e & kFsmGeneral);
-      const unsigned long long gb = __ballot(gen);
-      if (gb) {
-        if (gen) wl[n_gen + __builtin_amdgcn_mbcnt_hi((uint32_t)(gb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)gb, 0u))] = (uint16_t)w;
-        n_gen += (uint32_t)__popcll(gb);
-      }
-      const bool tab = act && !gen;
-      if (tab) {
-        tw[w] = (uint16_t)e;
-        n_matched += (e >> 25) & 1u;
-        n_bytes += ((e >> 26) & 15u) * 2u;
-      }
-      const bool dw = tab && (e & kFsmDue);
-      if (__ballot(dw)) {  // a delayed stage is scheduled (rare for table-only programs)
-        const int64_t dd = buf_load_i64(fdue_rs, dw ? ((((cwe >> 15) << fbits) | raw[b]) * 8u) : kOOB);
-        const int64_t v = sat_add(a.now, dd);
-        const uint32_t off = dw ? (wbase + w) * 8u : kOOB;
-        __builtin_amdgcn_raw_buffer_store_b32((uint32_t)v, due_rs, off, 0, 0);
-        __builtin_amdgcn_raw_buffer_store_b32((uint32_t)((uint64_t)v >> 32), due_rs, off + 4u, 0, 0);
-      }
-      emit(tab && ((e >> 21) & 1u), w, e);
-    };
-    if (n_work) {
-#pragma unroll
-      for (int q = 0; q < Q; ++q) tq[q * 64 + lane] = cur[q];
-      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-      fetch(0);
-    }
-    if (kPersist && kDepth == 1) issue_tile(v, tile + gridDim.x);
-    if (n_work) {
-#pragma unroll
-      for (int b = 0; b < B; ++b)
-        if (64u * b < n_work) pass(b);  // wave-uniform
-      for (uint32_t c0 = 64u * B; c0 < n_work; c0 += 64u * B) {  // more than kFsmBatch passes
-        fetch(c0);
-#pragma unroll
-        for (int b = 0; b < B; ++b)
-          if (c0 + 64u * b < n_work) pass(b);
-      }
-      // cold: the general items (a Philox draw, a value record or the deletion column)
-      for (uint32_t j = 0; j < n_gen; j += 64u) {
-        const bool in = j + lane < n_gen;
-        const uint32_t w = in ? (uint32_t)wl[j + lane] : 0u;
-        uint32_t e = 0;
-        if (in) {
-          const uint2 r = general16<kHarness>(wbase + w, (uint32_t)tw[w]);
-          e = r.x;
+      };
+      // Items whose entry is general are deferred to one loop after the lookups (records are
+      // unordered within a region): their slots are compacted to the front of the work list,
+      // whose entries up to the current batch are already in registers; their words stay
+      // unchanged in the LDS tile until then.
+      uint32_t n_gen = 0;  // wave-uniform
+      auto pass = [&](const int b) __attribute__((always_inline)) {
+        const uint32_t cwe = we[b], e = ent[b];
+        const bool act = cwe != 0xFFFFFFFFu;
+        const uint32_t w = cwe & 0x7FFFu;
+        const bool gen = act && (e & kFsmGeneral);
+        const unsigned long long gb = __ballot(gen);
+        if (gb) {
+          if (gen) wl[n_gen + __builtin_amdgcn_mbcnt_hi((uint32_t)(gb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)gb, 0u))] = (uint16_t)w;
+          n_gen += (uint32_t)__popcll(gb);
+        }
+        const bool tab = act && !gen;
+        if (tab) {
           tw[w] = (uint16_t)e;
           n_matched += (e >> 25) & 1u;
-          n_bytes += r.y;
+          n_bytes += ((e >> 26) & 15u) * 2u;
         }
-        emit(in && ((e >> 21) & 1u), w, e);
-      }
-      w_line -= 2u * n_work;  // the words' own writes are replaced by the line stores below
-      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-      // ---- phase 3: whole 128-byte lines wherever a word changed
+        const bool dw = tab && (e & kFsmDue);
+        if (__ballot(dw)) {  // a delayed stage is scheduled (rare for table-only programs)
+          const int64_t dd = buf_load_i64(fdue_rs, dw ? ((((cwe >> 15) << fbits) | raw[b]) * 8u) : kOOB);
+          const int64_t v = sat_add(now(), dd);
+          const uint32_t off = dw ? (wbase + w) * 8u : kOOB;
+          __builtin_amdgcn_raw_buffer_store_b32((uint32_t)v, due_rs, off, 0, 0);
+          __builtin_amdgcn_raw_buffer_store_b32((uint32_t)((uint64_t)v >> 32), due_rs, off + 4u, 0, 0);
+        }
+        emit(tab && ((e >> 21) & 1u), w, e);
+      };
+      if (n_work) {
+        if (!kFused || !in_lds) {  // (fused: a step before this one has put the tile there)
 #pragma unroll
-      for (int q = 0; q < Q; ++q) {
-        const uint4 nv = tq[q * 64 + lane];
-        const bool ch = (nv.x ^ cur[q].x) | (nv.y ^ cur[q].y) | (nv.z ^ cur[q].z) | (nv.w ^ cur[q].w);
-        const unsigned long long bal = __ballot(ch);
-        if ((bal >> (lane & ~(kStoreLanes - 1u))) & ((1ull << kStoreLanes) - 1ull)) {
-          store_chunk_nt(&gq[(wbase + (uint32_t)q * 512u + lane * 8u) / 8u], nv);
-          n_lline += 16u;
+          for (int q = 0; q < Q; ++q) tq[q * 64 + lane] = ws[q];
+        }
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        fetch(0);
+      }
+      if (kPersist && kDepth == 1) issue_tile(v, tile + gridDim.x);
+      if (n_work) {
+#pragma unroll
+        for (int b = 0; b < B; ++b)
+          if (64u * b < n_work) pass(b);  // wave-uniform
+        for (uint32_t c0 = 64u * B; c0 < n_work; c0 += 64u * B) {  // more than kFsmBatch passes
+          fetch(c0);
+#pragma unroll
+          for (int b = 0; b < B; ++b)
+            if (c0 + 64u * b < n_work) pass(b);
+        }
+        // cold: the general items (a Philox draw, a value record or the deletion column)
+        for (uint32_t j = 0; j < n_gen; j += 64u) {
+          const bool in = j + lane < n_gen;
+          const uint32_t w = in ? (uint32_t)wl[j + lane] : 0u;
+          uint32_t e = 0;
+          if (in) {
+            uint2 r;
+            if constexpr (kFused) r = general16<kHarness, true>(wbase + w, (uint32_t)tw[w], now(), a.step + s);
+            else r = general16<kHarness>(wbase + w, (uint32_t)tw[w]);
+            e = r.x;
+            tw[w] = (uint16_t)e;
+            n_matched += (e >> 25) & 1u;
+            n_bytes += r.y;
+          }
+          emit(in && ((e >> 21) & 1u), w, e);
+        }
+        w_line -= 2u * n_work;  // the words' own writes are replaced by the line stores below
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        // ---- phase 3: whole 128-byte lines wherever a word changed (fused: counted per step as
+        // stored, the words kept for the next step; the tile is stored once, behind the last step)
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+          const uint4 nv = tq[q * 64 + lane];
+          const bool ch = (nv.x ^ ws[q].x) | (nv.y ^ ws[q].y) | (nv.z ^ ws[q].z) | (nv.w ^ ws[q].w);
+          const unsigned long long bal = __ballot(ch);
+          if ((bal >> (lane & ~(kStoreLanes - 1u))) & ((1ull << kStoreLanes) - 1ull)) {
+            if constexpr (!kFused) store_chunk_nt(&gq[(wbase + (uint32_t)q * 512u + lane * 8u) / 8u], nv);
+            n_lline += 16u;
+          }
+          if constexpr (kFused) ws[q] = nv;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        if constexpr (kFused) in_lds = true;
+      }
+      {
+        const uint32_t used = 1u + seg_n, end = (used + 31u) & ~31u;
+        for (uint32_t x = used + lane; x < end; x += 64) seg32[x] = 0u;
+        if (lane == 0) {
+          seg32[0] = seg_n;
+          (kFused && s ? a.countsx[s - 1] : a.wave_counts)[seg_id] = seg_n;
+        }
+        w_line += 4u * (end - used);  // padding: line bytes only
+      }
+      wave_fired += seg_n;
+      w_bytes += 4u;  // the fired count word
+    };
+    if constexpr (!kFused) {
+      step_body(cur, 0u);
+    } else {
+#pragma nounroll
+      for (uint32_t s = 0; s < (uint32_t)kSteps; ++s) {
+        step_body(mid, s);
+        if (s + 1u < (uint32_t)kSteps) {
+          // the step's due times (and whatever else the cold path stored) have reached the L2
+          // before the next step loads any (the kernel's note on due times)
+          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
       }
-      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    }
-    {
-      const uint32_t used = 1u + seg_n, end = (used + 31u) & ~31u;
-      for (uint32_t x = used + lane; x < end; x += 64) seg32[x] = 0u;
-      if (lane == 0) {
-        seg32[0] = seg_n;
-        a.wave_counts[seg_id] = seg_n;
+      if (in_lds) {  // the tile as the last step left it: whole lines wherever a word changed
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+          const bool ch = (mid[q].x ^ cur[q].x) | (mid[q].y ^ cur[q].y) | (mid[q].z ^ cur[q].z) | (mid[q].w ^ cur[q].w);
+          const unsigned long long bal = __ballot(ch);
+          if ((bal >> (lane & ~(kStoreLanes - 1u))) & ((1ull << kStoreLanes) - 1ull))
+            store_chunk_nt(&gq[(wbase + (uint32_t)q * 512u + lane * 8u) / 8u], mid[q]);
+        }
       }
-      w_line += 4u * (end - used);  // padding: line bytes only
     }
-    wave_fired += seg_n;
-    w_bytes += 4u;  // the fired count word
     if (kPersist && kDepth == 2) issue_tile(v, tile + 2u * gridDim.x);
   };
   if constexpr (!kPersist) {
@@ -1376,7 +1488,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(Q >= 4 ?
     const unsigned int val = s_stat[threadIdx.x];
     if (val) atomicAdd(&a.cum[(uint64_t)blockIdx.x * kStatWords + threadIdx.x], (unsigned long long)val);
   }
-  if constexpr (!kPersist) {
+  if constexpr (!kPersist && !kFused) {
     if (a.tail.out) tail_handback<kWave, kSeg16>(a, tile < n_tiles ? wave_fired : 0u, lane, wave);
   }
 }
@@ -2832,12 +2944,12 @@ __global__ __launch_bounds__(kBlock) void bits_write_kernel(CompactArgs a, const
 // strong-scaling shards): each block sums the counts of every segment before its own (at most
 // 32 KB, L2-resident) instead of waiting for seg_scan_kernel, then expands its four segments as
 // compact_kernel does.  Saves one launch and its gap per step.
-template <int kRec, bool kPacked = false>
-__global__ __launch_bounds__(kBlock) void compact_small_kernel(CompactArgs a) {
+template <int kRec, bool kPacked>
+__device__ __forceinline__ void compact_small_block(const CompactArgs& a, const uint32_t block) {
   __shared__ uint32_t s_part[kWavesPerBlock];
   __shared__ uint32_t s_seg[kWavesPerBlock];
   const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const uint32_t first = blockIdx.x * kSegsPerBlock;  // the block's first segment
+  const uint32_t first = block * kSegsPerBlock;  // the block's first segment
   // the prefix as 16-byte loads (counts is 16-byte aligned, `first` a multiple of 4), eight in
   // flight per thread: one memory round trip up to 8192 segments instead of one per 256
   static_assert(kSegsPerBlock % 4 == 0, "prefix loads assume whole uint4s before the block");
@@ -2868,6 +2980,15 @@ __global__ __launch_bounds__(kBlock) void compact_small_kernel(CompactArgs a) {
     const uint2 x = rec_at<kRec>(sp, j);
     store_out<kPacked>(a, off + j, base + x.x, x.y);
   }
+}
+template <int kRec, bool kPacked = false>
+__global__ __launch_bounds__(kBlock) void compact_small_kernel(CompactArgs a) {
+  compact_small_block<kRec, kPacked>(a, blockIdx.x);
+}
+// the hand-backs of a fused launch's steps (blockIdx.y = the step), as compact16_small_multi_kernel
+template <int kRec, bool kPacked = false>
+__global__ __launch_bounds__(kBlock) void compact_small_multi_kernel(CompactArgs4 m) {
+  compact_small_block<kRec, kPacked>(m.a[blockIdx.y], blockIdx.x);
 }
 
 // sums the per-block statistics rows [0, n_blocks) (the rows any sweep grid has used)
@@ -5969,6 +6090,19 @@ static const void* sweep16_pick(bool harness, uint32_t q, bool lean, bool persis
   return (const void*)k[q == 4 ? 0 : q == 1 ? 1 : 2][harness ? 0 : 1][v];
 }
 
+// 2-byte words, the table-only kernel with one block per tile: a launch of 4 or 2 steps
+static const void* sweep16_fused_pick(bool harness, uint32_t q, uint32_t steps) {
+  // [q: 4, 1, 2][harness: on, off][4 steps, 2 steps]
+  static const SweepKernel k[3][2][2] = {
+      {{sweep16_fsm_kernel<true, 4, false, 1, 4>, sweep16_fsm_kernel<true, 4, false, 1, 2>},
+       {sweep16_fsm_kernel<false, 4, false, 1, 4>, sweep16_fsm_kernel<false, 4, false, 1, 2>}},
+      {{sweep16_fsm_kernel<true, 1, false, 1, 4>, sweep16_fsm_kernel<true, 1, false, 1, 2>},
+       {sweep16_fsm_kernel<false, 1, false, 1, 4>, sweep16_fsm_kernel<false, 1, false, 1, 2>}},
+      {{sweep16_fsm_kernel<true, 2, false, 1, 4>, sweep16_fsm_kernel<true, 2, false, 1, 2>},
+       {sweep16_fsm_kernel<false, 2, false, 1, 4>, sweep16_fsm_kernel<false, 2, false, 1, 2>}}};
+  return (const void*)k[q == 4 ? 0 : q == 1 ? 1 : 2][harness ? 0 : 1][steps == 4 ? 0 : 1];
+}
+
 // 4- / 8-byte words: the fused records, the 4-byte words, the 8-byte words; [format][harness: on, off]
 static const void* sweepw_pick(bool harness, bool dw, bool narrow) {
   static const SweepKernel k[3][2] = {{sweepw_kernel<true, 8, true>, sweepw_kernel<false, 8, true>},
@@ -6029,6 +6163,15 @@ static kwk_status launch_sweep(kwk_engine* e, int64_t now_ns, uint64_t seed, uin
     if (q16 > 1 && (e->n_active + kBlock * 8 * q16 - 1) / (kBlock * 8 * q16) < 4u * (uint32_t)e->n_cus) q16 = 1;
     K = 8 * q16;
     lean = a.fsm && e->fsm_kernel;
+    if (fuse) {  // (fuse_group: only where fuse16_ok has said so)
+      if (!lean || (steps != 2 && steps != 4)) return fail(KWK_ESTATE, "fused steps: 2 or 4, table-only 2-byte sweep");
+      for (uint32_t i = 0; i + 1 < steps; ++i) {
+        if (!e->d_firedx[i]) return fail(KWK_ESTATE, "fused steps: buffers not allocated");
+        a.firedx[i] = e->d_firedx[i];
+        a.countsx[i] = e->d_countsx[i];
+        a.nowx[i] = now_ns + (int64_t)(i + 1) * dt_ns;
+      }
+    }
   } else {  // 4- / 8-byte words: whole-line write-back word sweep
     K = dw ? (uint32_t)kQWD * 2u : (uint32_t)kQW * (nar ? 4u : 2u);
     region_shift = 2;  // log2(kWavesPerBlock): records carry tile-relative slots
@@ -6047,7 +6190,10 @@ static kwk_status launch_sweep(kwk_engine* e, int64_t now_ns, uint64_t seed, uin
     const uint32_t pg = e->persist16 ? persist_grid(e, pk, tiles) : tiles;
     const uint32_t kind = e->fmt.byte ? KWK_SWEEP_8 : lean ? KWK_SWEEP_16_FSM : KWK_SWEEP_16;
     e->last_sweep = kwk_sweep_info{kind, e->fmt.byte ? (uint32_t)kQ8 : q16, 0, 1, tiles, tiles, h ? 1u : 0u, 0};
-    if (2 * pg <= tiles) {  // else the persistent loop would run about once: one block per tile
+    if (fuse && !e->fmt.byte) {  // one block per tile (fuse16_ok)
+      if (2 * pg <= tiles) return fail(KWK_ESTATE, "fused steps: the 2-byte sweep's grid is persistent");
+      kern = sweep16_fused_pick(h, q16, steps);
+    } else if (2 * pg <= tiles) {  // else the persistent loop would run about once: one block per tile
       blocks = pg;
       e->last_sweep.persistent = 1;
       e->last_sweep.grid = pg;
@@ -6062,7 +6208,7 @@ static kwk_status launch_sweep(kwk_engine* e, int64_t now_ns, uint64_t seed, uin
       }
       kern = sweep16_pick(h, q16, lean, false, 1);
     }
-    if (e->fmt.byte) e->last_sweep.steps = steps;
+    if (e->fmt.byte || fuse) e->last_sweep.steps = steps;
   } else {
     // tiles per workgroup (the next tile's stream in flight while one is worked: 8 for the fused
     // records, 4 for the 4-byte words, r3r), but at least ~5 workgroups per CU
@@ -6370,14 +6516,31 @@ static kwk_status step_one(kwk_engine* e, int64_t now, uint64_t seed, uint64_t s
   return sweep_compact(e, now, seed, step, compact != 0, hb_fmt_of_compact(compact), ev_a);
 }
 
+// whether a 2-byte engine's steps may share a launch: the table-only kernel with one block per tile,
+// as launch_sweep will choose it (the same tile shape, tiles and persistent grid).  Grids small enough
+// for the hand-back inside the sweep (tail_handback: one launch per step) take the group too: two
+// launches per 4 steps ("Fused table steps")
+static bool fuse16_ok(kwk_engine* e) {
+  if (!e->fmt.half || e->fmt.byte || !e->fsm_kernel || e->n_active == 0) return false;
+  const bool h = e->harness.enable != 0;
+  if (e->fsm_harness != (h ? 1 : 0)) return false;
+  uint32_t q = e->q16;
+  if (q > 1 && (e->n_active + kBlock * 8 * q - 1) / (kBlock * 8 * q) < 4u * (uint32_t)e->n_cus) q = 1;
+  const uint32_t tiles = (e->n_active + kBlock * 8 * q - 1) / (kBlock * 8 * q);
+  const uint32_t pg = e->persist16 ? persist_grid(e, sweep16_pick(h, q, true, true, e->fsm_kernel), tiles) : tiles;
+  return 2 * pg > tiles;
+}
+
 // several steps in one sweep launch (KWK_TUNE_FUSE_STEPS): a 1-byte engine whose table writes no
 // due time (objects then step independently of the clock except through due times already
-// queued, which each step tests at its own now) and whose records are the 2-byte ones.  The steps
+// queued, which each step tests at its own now) and whose records are the 2-byte ones; or a 2-byte
+// engine on the table-only kernel with one block per tile (fuse16_ok; its kernel orders a step's
+// due times before the next step's tests).  The steps
 // a launch takes: 4, 2 or 1, at most the tuning's and the call's steps left, and at most one event
 // sample per launch (ev_every 2 or 3: pairs; 1: none fused)
-static uint32_t fuse_group(const kwk_engine* e, uint32_t left, uint32_t ev_every) {
-  if (e->fuse_steps < 2 || !e->fmt.byte || e->n_stages > 4 || e->fsm8_due_any || !e->loaded_table || ev_every == 1)
-    return 1;
+static uint32_t fuse_group(kwk_engine* e, uint32_t left, uint32_t ev_every) {
+  if (e->fuse_steps < 2 || !e->loaded_table || ev_every == 1 || left < 2) return 1;
+  if (e->fmt.byte ? e->n_stages > 4 || e->fsm8_due_any : !fuse16_ok(e)) return 1;
   uint32_t m = e->fuse_steps;
   while (ev_every && m > 2 && m > ev_every) m >>= 1;  // at most one event sample per launch
   while (m > left) m >>= 1;
@@ -6403,19 +6566,33 @@ static kwk_status step_group(kwk_engine* e, uint32_t m, int64_t now, int64_t dt,
   if (ev_a >= 0)
     if (kwk_status st = kwk_event_record(e, (uint32_t)ev_a + 1u)) return st;
   const uint32_t n_waves = e->last_blocks * kWavesPerBlock;
-  if (compact == KWK_COMPACT_PACKED16 && e->last_rec == kRecId8Half && n_waves) {
-    // the steps' 2-byte hand-backs in one launch (two: scan + expansion, past compact_small
-    // segments), blockIdx.y = the step, step i's list into ring slot hb_next(i + 1)
+  // the steps' hand-backs in one launch, blockIdx.y = the step, step i's list into ring slot
+  // hb_next(i + 1): the 1-byte sweep's 2-byte records (two launches, scan + expansion, past
+  // compact_small segments), and a 2-byte sweep's records as kwk_fired_rec or packed (the segmented
+  // formats fall to packed, as in enqueue_compact) up to compact_small segments
+  const bool multi16 = compact == KWK_COMPACT_PACKED16 && e->last_rec == kRecId8Half;
+  const bool multi_small = compact && e->fmt.half && !e->fmt.byte && n_waves <= e->compact_small;
+  if ((multi16 || multi_small) && n_waves) {
+    const HbFmt mode = multi16 ? HbFmt::Packed16 : hb_fmt_of_compact(compact) == HbFmt::Rec ? HbFmt::Rec : HbFmt::Packed;
     CompactArgs4 c4;
     for (uint32_t i = 0; i < m; ++i)
-      if (kwk_status st = hb_prepare(e, hb_next(e, i + 1), HbFmt::Packed16, e->stream)) return st;
+      if (kwk_status st = hb_prepare(e, hb_next(e, i + 1), mode, e->stream)) return st;
     for (uint32_t i = 0; i < m; ++i) {
       CompactArgs& a = c4.a[i];
       a.fired32 = reinterpret_cast<const uint32_t*>((i ? e->d_firedx[i - 1] : e->d_fired).get());
       a.counts = i ? e->d_countsx[i - 1] : e->d_wave_counts;
-      hb_args(e, hb_next(e, i + 1), HbFmt::Packed16, a);
+      hb_args(e, hb_next(e, i + 1), mode, a);
     }
-    if (kwk_status st = launch_compact16(e, e->stream, n_waves, c4, m)) return st;
+    if (multi16) {
+      if (kwk_status st = launch_compact16(e, e->stream, n_waves, c4, m)) return st;
+    } else {
+      const dim3 grid((n_waves + kSegsPerBlock - 1) / kSegsPerBlock, m);
+      if (mode == HbFmt::Packed)
+        hipLaunchKernelGGL((compact_small_multi_kernel<kRecSlot, true>), grid, dim3(kBlock), 0, e->stream, c4);
+      else
+        hipLaunchKernelGGL((compact_small_multi_kernel<kRecSlot>), grid, dim3(kBlock), 0, e->stream, c4);
+      HIP_TRY(hipGetLastError());
+    }
     for (uint32_t i = 1; i < m; ++i) {  // the last step's segments and counts where the engine reads them
       std::swap(e->d_fired, e->d_firedx[i - 1]);
       std::swap(e->d_wave_counts, e->d_countsx[i - 1]);
@@ -6423,8 +6600,7 @@ static kwk_status step_group(kwk_engine* e, uint32_t m, int64_t now, int64_t dt,
     const uint32_t last = hb_next(e, m);
     for (uint32_t i = 0; i < m; ++i) {
       const uint32_t slot = hb_next(e, 1);  // hb_commit advances hb_cur: slots in step order
-      if (kwk_status st = hb_commit(e, slot, step + i, HbFmt::Packed16, n_waves, (int)last, e->stream, i + 1 == m))
-        return st;
+      if (kwk_status st = hb_commit(e, slot, step + i, mode, n_waves, (int)last, e->stream, i + 1 == m)) return st;
     }
     return KWK_OK;
   }
@@ -6498,9 +6674,18 @@ kwk_status kwk_step_n_pair(kwk_engine* e, kwk_engine* other, uint32_t n, int64_t
     } else if (kwk_status st = step_one(e, now, seed, step0 + k, compact, ev_of(ev_every, j))) {
       return st;
     }
-    // the other engine's step(s) right behind (its own stream): both chains start together
-    for (uint32_t i = 0; i < m; ++i)
-      if (kwk_status st = step_one(other, now + (int64_t)i * dt_ns, seed, step0 + k + i, compact, -1)) return st;
+    // the other engine's step(s) right behind (its own stream): both chains start together.  Its m
+    // steps in fused launches of its own where it takes them (no events on its stream), else one by one
+    for (uint32_t i = 0; i < m;) {
+      const uint32_t mo = fuse_group(other, m - i, 0);
+      const int64_t now_i = now + (int64_t)i * dt_ns;
+      if (mo > 1) {
+        if (kwk_status st = step_group(other, mo, now_i, dt_ns, seed, step0 + k + i, compact, -1)) return st;
+      } else if (kwk_status st = step_one(other, now_i, seed, step0 + k + i, compact, -1)) {
+        return st;
+      }
+      i += mo;
+    }
     k += m;
   }
   return KWK_OK;
