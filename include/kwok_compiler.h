@@ -90,6 +90,16 @@ kwk_status kwk_program_patch_spec(kwk_program* p, const char* funcs_json, const 
  * shapes the host keeps: more than 15 dictionary values; a value with a byte outside
  * [A-Za-z0-9._/-] (Go's json.Marshal escaping of other bytes is pinned by no reference vector) */
 kwk_status kwk_program_finalizer_spec(kwk_program* p, const char** json);
+/* the event program, the "events" member of the patch spec (kwok_patch.h: kwk_patch_event):
+ * {"kind": the involved object's kind, "api_version": "" for the typed Pod and Node controllers
+ * (their reference carries none), the resourceRef's group/version for every other kind,
+ * "component": the recorder's EventSource component, "stages": [null | {"type", "reason",
+ * "message"}]}.  A stage is null when it has no next.event or its type is not Normal / Warning
+ * (generateEvent logs "Unsupported event type" and sends nothing).  device != 0 refuses with
+ * KWK_EINVAL, naming the cause, what a device event stream does not carry: a stage string with a
+ * byte outside 0x20..0x7E or one of " \ < > &; more than 16 KiB of stage text in total.  The
+ * host form (device = 0) renders those programs too. */
+kwk_status kwk_program_event_spec(kwk_program* p, int32_t device, const char** json);
 
 #ifdef __cplusplus
 }

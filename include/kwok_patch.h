@@ -128,6 +128,39 @@ kwk_status kwk_patch_finalizer_word(kwk_patcher* p, uint32_t n, const char* fins
  * (the message names the cause) for KWK_FIN_WORD_HOST and for an entry KWK_FIN_OTHER */
 kwk_status kwk_patch_finalizer_list(kwk_patcher* p, uint32_t word, uint32_t* n, char* out, uint64_t cap, uint64_t* len);
 
+/* ---- the Event of a fired stage (Next.Event): the first thing playStage sends for a fired object
+ * (pod_controller.go:304-352, node_controller.go:369, stage_controller.go:282), before the
+ * finalizer patch.  The recorder is NewRecorder(scheme, EventSource{Component: "kwok_controller"})
+ * (controller.go:184); the bytes are what recorder.Event hands the broadcaster, restated from
+ * client-go v0.30.2 tools/record/event.go (generateEvent, makeEvent), k8s.io/api v0.30.2
+ * core/v1/types.go (Event, ObjectReference, EventSource), apimachinery's ObjectMeta and
+ * metav1.Time.MarshalJSON, and encoding/json.  The sink-side EventCorrelator is not applied.
+ *
+ * The spec's optional "events": {"kind", "api_version", "component", "stages": [null | {"type",
+ * "reason", "message"}]} (kwok_amd/host/compiler.py: event_spec / kwk_program_event_spec).
+ *
+ * The body is one compact JSON object, keys in struct order (line breaks for reading only):
+ *   {"metadata":{"name":"<name>.<hex>","namespace":"<ref ns or default>","creationTimestamp":null},
+ *    "involvedObject":{"kind":"<Kind>"[,"namespace":"<ns>"][,"name":"<name>"][,"uid":"<uid>"][,"apiVersion":"<av>"]},
+ *    ["reason":"<reason>",]["message":"<message>",]"source":{"component":"<component>"},
+ *    "firstTimestamp":"<ts>","lastTimestamp":"<ts>","count":1,"type":"<type>","eventTime":null,
+ *    "reportingComponent":"<component>","reportingInstance":""}
+ * <hex>: now_ns as %x.  <ts>: now_ns truncated to seconds, UTC, 2006-01-02T15:04:05Z (metav1.Time).
+ * metadata.namespace is the reference's namespace, "default" when that is empty (makeEvent).  involvedObject.namespace,
+ * name, uid, apiVersion, reason and message are omitempty.  With the program's api_version "" (the typed
+ * Pod and Node controllers) there is no apiVersion key and the argument is not read, and kind Node
+ * has no involvedObject.namespace either (the Node controller passes none); every other kind
+ * carries the object's own api_version.  Strings are escaped as json.Marshal does: " and \ with a
+ * backslash, \n \r \t as those escapes, < > & as \u003c \u003e \u0026, U+2028 / U+2029 as
+ * \u2028 / \u2029, other valid UTF-8 unchanged.
+ *
+ * *len = 0 for a stage that records nothing (null).  KWK_ECAP with *len = the bytes needed when cap
+ * is too small; KWK_ESTATE without an event program; KWK_EINVAL naming the byte for a control byte
+ * other than \n \r \t or invalid UTF-8 in any string (Go's output for those is not restated here),
+ * and for now_ns < 0. */
+kwk_status kwk_patch_event(kwk_patcher* p, uint32_t stage, const char* ns, const char* name, const char* uid,
+                           const char* api_version, int64_t now_ns, char* out, uint64_t cap, uint64_t* len);
+
 #ifdef __cplusplus
 }
 #endif

@@ -36,7 +36,8 @@ COMM_SRC = [os.path.join(PKG, "csrc", "comm.cpp")]
 COMM_HDR = [os.path.join(ROOT, "include", "kwok_comm.h"), os.path.join(ROOT, "include", "kwok_engine.h"), ERR_HDR, MEM_HDR]
 COMM_OUT = os.path.join(PKG, "lib", "libkwok_comm.so")
 EMIT_SRC = [os.path.join(PKG, "csrc", "emit.hip")]
-EMIT_HDR = [os.path.join(ROOT, "include", "kwok_emit.h"), os.path.join(ROOT, "include", "kwok_engine.h"),
+EMIT_HDR = [os.path.join(ROOT, "include", "kwok_emit.h"), os.path.join(ROOT, "include", "kwok_events.h"),
+            os.path.join(ROOT, "include", "kwok_engine.h"),
             os.path.join(PKG, "csrc", "timefmt.hpp"), ERR_HDR, MEM_HDR]
 EMIT_OUT = os.path.join(PKG, "lib", "libkwok_emit.so")
 EXPO_SRC = [os.path.join(PKG, "csrc", "expo.hip")]

@@ -94,6 +94,8 @@ struct Stage {
   std::string dur_from, jit_from;
   bool has_fin = false, fin_empty = false;
   std::vector<std::string> fin_add, fin_remove;
+  bool has_event = false;  // next.event: the Event playStage records first
+  std::string ev_type, ev_reason, ev_message;
   bool del = false, immediate = false;
   std::vector<Patch> patches;
 };
@@ -179,6 +181,16 @@ Stage stage_from_v1alpha1(const JV& obj) {
     vals("add", st.fin_add);
     vals("remove", st.fin_remove);
     st.fin_empty = py_truth(f->get("empty"));
+  }
+  if (const JV* e = n->get("event"); e && e->t != JV::NUL) {
+    st.has_event = true;
+    auto text = [&](const char* key) {
+      const JV* v = e->get(key);
+      return !v || v->t == JV::NUL ? std::string() : py_str(*v);
+    };
+    st.ev_type = text("type");
+    st.ev_reason = text("reason");
+    st.ev_message = text("message");
   }
   if (const JV* ps = n->get("patches"); ps && ps->t == JV::ARR) {
     for (const JV& p : ps->a) {
@@ -997,6 +1009,51 @@ struct kwk_program {
     return o;
   }
 
+  // compiler.KindProgram.event_spec: the event program — the involved object's kind, its
+  // reference's apiVersion ("" for the typed Pod / Node controllers), the recorder's component and
+  // per stage the Event's type / reason / message, null where generateEvent sends nothing.
+  // device: refuses by name what the device stream does not carry
+  std::string event_spec(bool device) const {
+    const std::string kind = stages.empty() ? "" : stages[0].kind;
+    const std::string group = stages.empty() ? "" : stages[0].api_group;
+    PJ sl = PJ::list();
+    size_t total = 0;
+    for (const Stage& st : stages) {
+      if (!st.has_event || (st.ev_type != "Normal" && st.ev_type != "Warning")) {
+        sl.push(PJ::null());
+        continue;
+      }
+      if (device) {
+        const std::pair<const char*, const std::string*> fields[] = {
+            {"type", &st.ev_type}, {"reason", &st.ev_reason}, {"message", &st.ev_message}};
+        for (const auto& f : fields) {
+          for (const char ch : *f.second) {
+            const unsigned char b = (unsigned char)ch;
+            if (b < 0x20 || b > 0x7E || b == '"' || b == '\\' || b == '<' || b == '>' || b == '&') {
+              char hex[8];
+              snprintf(hex, sizeof hex, "0x%02x", b);
+              throw CompileError("event program not supported on the device: stage " + st.name + " " + f.first +
+                                 " has byte " + hex + " (outside 0x20..0x7E or one of \" \\ < > &); the host renders the events");
+            }
+          }
+          total += f.second->size();
+        }
+      }
+      sl.push(PJ::dict().set("type", PJ::str(st.ev_type)).set("reason", PJ::str(st.ev_reason)).set("message", PJ::str(st.ev_message)));
+    }
+    if (total > 16 * 1024)
+      throw CompileError("event program not supported on the device: " + std::to_string(total) +
+                         " bytes of stage text (more than 16384); the host renders the events");
+    const bool typed = group == "v1" && (kind == "Pod" || kind == "Node");
+    std::string o;
+    kwkpatch::pj_dump(o, PJ::dict()
+                             .set("kind", PJ::str(kind))
+                             .set("api_version", PJ::str(typed ? "" : group))
+                             .set("component", PJ::str("kwok_controller"))
+                             .set("stages", sl));
+    return o;
+  }
+
   // patchtpl.PatchProgram: the spec and (stage, patch) -> template id
   std::string patch_spec(const JV& funcs, const std::string& version, std::vector<std::vector<int>>& template_of) {
     std::map<std::string, std::pair<bool, std::string>> fmap;  // name -> (callback, const)
@@ -1221,6 +1278,18 @@ kwk_status kwk_program_finalizer_spec(kwk_program* p, const char** json) {
   if (!p || !json) return fail(KWK_EINVAL, "null argument");
   try {
     p->out_json = p->finalizer_spec();
+  } catch (const std::exception& e) {
+    return fail(KWK_EINVAL, e.what());
+  }
+  *json = p->out_json.c_str();
+  return KWK_OK;
+}
+
+kwk_status kwk_program_event_spec(kwk_program* p, int32_t device, const char** json) {
+  ErrScope es_(p ? &p->err : nullptr);
+  if (!p || !json) return fail(KWK_EINVAL, "null argument");
+  try {
+    p->out_json = p->event_spec(device != 0);
   } catch (const std::exception& e) {
     return fail(KWK_EINVAL, e.what());
   }

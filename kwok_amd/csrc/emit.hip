@@ -34,6 +34,7 @@
 #include <vector>
 
 #include "../../include/kwok_emit.h"
+#include "../../include/kwok_events.h"
 #include "errscope.hpp"
 #include "devmem.hpp"
 #include "timefmt.hpp"
@@ -1324,6 +1325,286 @@ __global__ __launch_bounds__(kBlock) void emit_fin_write_kernel(EmitArgs a, FinA
   }
 }
 
+// ---- Events (kwok_events.h; client-go generateEvent / makeEvent, restated in kwok_patch.h) ----
+// A record's Event body is fixed text around the object's name (twice), namespace (once or twice)
+// and uid: the literals every stage shares (kEvtLit*), `.<hex>","namespace":"` of this emission, and
+// the stage's tail — everything after the last inserted value, with the emission's timestamp in
+// place twice.  The passes are the other streams': emit_evt_size_kernel (per tile: items and bytes;
+// the three row lengths are gathered for event stages only), emit_scan_kernel over the event tile
+// arrays, emit_evt_write_kernel.  The writer builds the tails in LDS once per block, lists the
+// tile's items in LDS, and gives each item to a group of 16 lanes, which copies its runs and rows
+// into the LDS window of the tile's byte range a dword per lane (source and destination are not
+// aligned to each other: a funnel shift of two source dwords; the up to three bytes at either end of
+// a run are byte stores).  The block stores the window as 16-byte chunks, consecutive threads
+// consecutive chunks; the two chunks a tile shares with its neighbours leave as byte stores.
+constexpr uint32_t kEvtWin = 16384;        // bytes of a tile assembled in LDS per pass
+constexpr uint32_t kEvtTailBytes = 26624;  // the event stages' tails (LDS): KWK_EVT_MAX_TEXT + 32 stages' fixed text
+constexpr uint32_t kEvtComWords = 64;      // the shared literals (LDS)
+constexpr uint32_t kEvtGroup = 16, kEvtGroups = kBlock / kEvtGroup;
+constexpr uint32_t kEvtRowHost = 0xFFu;
+// the shared literals: A `{"metadata":{"name":"`, C `","creationTimestamp":null},"involvedObject":{"kind":"<Kind>"`,
+// D `,"namespace":"`, E1 `,"name":"`, E2 `","name":"`, F `","uid":"`, `default`
+enum : uint32_t { kEvtLitA, kEvtLitC, kEvtLitD, kEvtLitE1, kEvtLitE2, kEvtLitF, kEvtLitDefault, kEvtLits };
+
+struct EvtArgs {
+  const uint4* stages;    // per stage: x = byte offset of its tail in `tails` (4-aligned), y = its length (0: no
+                          // event), z / w = the offsets of its two timestamps
+  const uint32_t* tails;  // the tails' bytes as dwords
+  const uint32_t* com;    // the shared literals' bytes as dwords
+  uint32_t com_ent[kEvtLits];  // byte offset (4-aligned) | length << 16
+  uint32_t n_tail_words, n_com_words, n_stages;
+  uint32_t base_bytes;    // A + C + E1 (+ this emission's `.<hex>","namespace":"`): every body has them
+  const uint8_t* rows[3];  // name, namespace (null: none), uid
+  uint32_t stride[3];
+  uint32_t* tile_items;
+  unsigned long long* tile_bytes;
+  unsigned long long* totals;  // the event stream's (EmitArgs::totals' layout)
+  kwk_evt_item* items;
+  uint64_t* offsets;
+  char* out;
+  unsigned long long cap_items, cap_bytes;
+  uint32_t b_len;
+  char b[36];   // `.<hex>","namespace":"`
+  char ts[20];  // 2006-01-02T15:04:05Z
+};
+
+struct EvtRec {
+  uint32_t has;  // 0: no item, 1: an item with bytes, 2: an item for the host
+  uint32_t by, ln, lns, lu;
+};
+
+// s_tl: the stages' tail lengths (LDS)
+__device__ __forceinline__ EvtRec evt_rec(const EvtArgs& e, const Rec& x, const uint32_t* s_tl) {
+  EvtRec v{0u, 0u, 0u, 0u, 0u};
+  if (x.stage >= e.n_stages) return v;
+  const uint32_t tl = s_tl[x.stage];
+  if (!tl) return v;
+  v.has = 2u;
+  if (!x.valid) return v;
+  v.ln = e.rows[0][(size_t)x.slot * e.stride[0]];
+  v.lns = e.rows[1] ? e.rows[1][(size_t)x.slot * e.stride[1]] : 0u;
+  v.lu = e.rows[2][(size_t)x.slot * e.stride[2]];
+  // (an empty name is the host's too: ObjectReference.Name is omitempty, the key goes)
+  if (v.ln == kEvtRowHost || v.ln == 0u || v.lns == kEvtRowHost || v.lu == kEvtRowHost) return v;
+  v.has = 1u;
+  v.by = e.base_bytes + tl + 2u * v.ln + (v.lns ? 2u * v.lns + (e.com_ent[kEvtLitD] >> 16) + 1u : 7u) +
+         (v.lu ? (e.com_ent[kEvtLitF] >> 16) + v.lu : 0u);
+  return v;
+}
+
+template <uint32_t kSrc>
+__global__ __launch_bounds__(kBlock) void emit_evt_size_kernel(EmitArgs a, EvtArgs e) {
+  __shared__ uint32_t s_tl[KWK_MAX_STAGES];
+  __shared__ uint32_t s_i[kWaves];
+  __shared__ unsigned long long s_b[kWaves];
+  if (*a.sticky) return;  // this emission's other streams or an earlier emission exceeded a set
+  if (threadIdx.x < KWK_MAX_STAGES) s_tl[threadIdx.x] = threadIdx.x < e.n_stages ? e.stages[threadIdx.x].y : 0u;
+  __syncthreads();
+  const uint32_t n = list_len<kSrc>(a), n_tiles = (n + kTile - 1) / kTile;
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  uint32_t* s_win = nullptr;
+  if constexpr (kSrc == kSrc16) s_win = seg_win_lds();
+  for (uint32_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+    uint32_t it = 0;
+    unsigned long long by = 0;
+    const uint32_t r = t * kTile + threadIdx.x;
+    SegWin sw{};
+    if constexpr (kSrc == kSrc16) sw = tile_segs(a, t, n, s_win);
+    if (r < n) {
+      Rec x;
+      if constexpr (kSrc == kSrc16) x = fetch16(a, r, sw, s_win);
+      else x = fetch(a, r);
+      const EvtRec v = evt_rec(e, x, s_tl);
+      it = v.has ? 1u : 0u;
+      by = v.by;
+    }
+    it = wave_sum(it);
+    by = wave_sum(by);
+    if (lane == 0) {
+      s_i[wave] = it;
+      s_b[wave] = by;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      uint32_t ti = 0;
+      unsigned long long tb = 0;
+      for (uint32_t w = 0; w < kWaves; ++w) {
+        ti += s_i[w];
+        tb += s_b[w];
+      }
+      e.tile_items[t] = ti;
+      e.tile_bytes[t] = tb;
+    }
+    __syncthreads();
+  }
+}
+
+// `len` bytes from byte `so` of the dword array `src` to window position q (it may start before the
+// window or end after it: clipped), by lane gl of a group of kEvtGroup.  Whole destination dwords are
+// stored as dwords, the bytes of the run's first and last partial dword as bytes: no byte of
+// another run is written.  Reads at most one dword past the run's last (the sources are padded).
+template <typename P>
+__device__ __forceinline__ void evt_copy(uint8_t* win, int32_t q, P src, uint32_t so, uint32_t len, int32_t gl) {
+  const int32_t lo = max(q, 0), hi = min(q + (int32_t)len, (int32_t)kEvtWin);
+  if (lo >= hi) return;
+  auto byte_at = [&](int32_t b) __attribute__((always_inline)) {
+    const uint32_t s = so + (uint32_t)(b - q);
+    return (uint8_t)(src[s >> 2] >> (8u * (s & 3u)));
+  };
+  const int32_t d0 = (lo + 3) >> 2, d1 = hi >> 2;
+  if (d0 >= d1) {
+    for (int32_t b = lo + gl; b < hi; b += (int32_t)kEvtGroup) win[b] = byte_at(b);
+    return;
+  }
+  const int32_t nh = 4 * d0 - lo, nt = hi - 4 * d1;  // 0..3 each
+  if (gl < nh) win[lo + gl] = byte_at(lo + gl);
+  else if (gl >= 8 && gl - 8 < nt) win[4 * d1 + gl - 8] = byte_at(4 * d1 + gl - 8);
+  uint32_t* const w32 = reinterpret_cast<uint32_t*>(win);
+  for (int32_t d = d0 + gl; d < d1; d += (int32_t)kEvtGroup) {
+    const uint32_t s = so + (uint32_t)(4 * d - q), sh = 8u * (s & 3u);
+    const uint32_t w0 = src[s >> 2];
+    w32[d] = sh ? (w0 >> sh) | (src[(s >> 2) + 1u] << (32u - sh)) : w0;
+  }
+}
+
+template <uint32_t kSrc>
+__global__ __launch_bounds__(kBlock) void emit_evt_write_kernel(EmitArgs a, EvtArgs e) {
+  __shared__ uint4 s_stage[KWK_MAX_STAGES];
+  __shared__ uint32_t s_tl[KWK_MAX_STAGES];
+  __shared__ uint32_t s_tails[kEvtTailBytes / 4 + 4];
+  __shared__ uint32_t s_com[kEvtComWords + 4];
+  __shared__ uint32_t s_b[12];
+  __shared__ uint4 s_desc[kTile];  // the tile's items: slot, stage | lengths, start in the tile, bytes
+  __shared__ __attribute__((aligned(16))) uint4 s_out[kEvtWin / 16];
+  __shared__ uint32_t s_wi[kWaves], s_wb[kWaves];
+  __shared__ uint32_t s_tend, s_nit;
+  if (*a.sticky) return;  // an emission in flight (this one included) exceeded a set: nothing is written
+  if (a.totals[0] > a.cap_items || a.totals[1] > a.cap_bytes || a.totals[2]) return;  // the merge patches did
+  const unsigned long long tot_i = e.totals[0], tot_b = e.totals[1];
+  if (tot_i > e.cap_items || tot_b > e.cap_bytes) return;
+  for (uint32_t j = threadIdx.x; j < KWK_MAX_STAGES; j += blockDim.x) {
+    const uint4 S = j < e.n_stages ? e.stages[j] : make_uint4(0u, 0u, 0u, 0u);
+    s_stage[j] = S;
+    s_tl[j] = S.y;
+  }
+  for (uint32_t j = threadIdx.x; j < e.n_tail_words && j < kEvtTailBytes / 4; j += blockDim.x) s_tails[j] = e.tails[j];
+  for (uint32_t j = threadIdx.x; j < e.n_com_words && j < kEvtComWords; j += blockDim.x) s_com[j] = e.com[j];
+  if (threadIdx.x < 9u) {
+    uint32_t w = 0;
+    for (uint32_t b = 0; b < 4u; ++b) w |= (uint32_t)(uint8_t)e.b[4u * threadIdx.x + b] << (8u * b);
+    s_b[threadIdx.x] = w;
+  }
+  __syncthreads();
+  {  // this emission's timestamp into every tail, twice
+    uint8_t* const tb8 = reinterpret_cast<uint8_t*>(s_tails);
+    for (uint32_t j = threadIdx.x; j < e.n_stages * 40u; j += blockDim.x) {
+      const uint4 S = s_stage[j / 40u];
+      const uint32_t k = j % 40u;
+      if (S.y) tb8[(k < 20u ? S.z : S.w) + k % 20u] = (uint8_t)e.ts[k % 20u];
+    }
+  }
+  __syncthreads();
+  const uint32_t n = list_len<kSrc>(a), n_tiles = (n + kTile - 1) / kTile;
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint32_t grp = threadIdx.x / kEvtGroup;
+  const int32_t gl = (int32_t)(threadIdx.x % kEvtGroup);
+  uint32_t* s_win = nullptr;
+  if constexpr (kSrc == kSrc16) s_win = seg_win_lds();
+  if (blockIdx.x == 0 && threadIdx.x == 0) e.offsets[tot_i] = tot_b;
+  uint8_t* const sb = reinterpret_cast<uint8_t*>(s_out);
+  const uint32_t lenD = e.com_ent[kEvtLitD] >> 16, lenF = e.com_ent[kEvtLitF] >> 16;
+  for (uint32_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+    const uint32_t lr = threadIdx.x, r = t * kTile + lr;
+    Rec x{0u, 0xFFFFFFFFu, false};
+    EvtRec v{0u, 0u, 0u, 0u, 0u};
+    SegWin sw{};
+    if constexpr (kSrc == kSrc16) sw = tile_segs(a, t, n, s_win);
+    if (r < n) {
+      if constexpr (kSrc == kSrc16) x = fetch16(a, r, sw, s_win);
+      else x = fetch(a, r);
+      v = evt_rec(e, x, s_tl);
+    }
+    const uint32_t has = v.has ? 1u : 0u, by = v.by;
+    const uint32_t ii = wave_incl(has, lane), ib = wave_incl(by, lane);
+    if (lane == 63) {
+      s_wi[wave] = ii;
+      s_wb[wave] = ib;
+    }
+    __syncthreads();
+    const unsigned long long tb = e.tile_bytes[t];
+    const uint32_t head = (uint32_t)(tb & 15ull);  // positions below are relative to the tile's 16-byte aligned base
+    uint32_t li = ii - has, g0 = head + ib - by;
+    for (uint32_t u = 0; u < wave; ++u) {
+      li += s_wi[u];
+      g0 += s_wb[u];
+    }
+    if (lr == kTile - 1u) {
+      s_tend = g0 + by;
+      s_nit = li + has;
+    }
+    if (has) {
+      const uint32_t item = e.tile_items[t] + li;
+      e.items[item] = kwk_evt_item{r, (uint8_t)(v.has == 2u ? KWK_EMIT_HOST : KWK_EMIT_OK), {0, 0, 0}};
+      e.offsets[item] = (tb & ~15ull) + g0;
+      s_desc[li] = make_uint4(x.slot, x.stage | v.ln << 8 | v.lns << 16 | v.lu << 24, g0, by);
+    }
+    __syncthreads();  // s_tend, s_nit, s_desc
+    const uint32_t tend = s_tend, nit = s_nit;
+    char* const base = e.out + (tb & ~15ull);
+    for (uint32_t W = 0; W < tend; W += kEvtWin) {  // (block-uniform)
+      for (uint32_t k = grp; k < nit; k += kEvtGroups) {
+        const uint4 D = s_desc[k];
+        if (!D.w || D.z + D.w <= W || D.z >= W + kEvtWin) continue;  // no bytes, or none inside the window
+        const uint32_t stage = D.y & 0xFFu, ln = (D.y >> 8) & 0xFFu, lns = (D.y >> 16) & 0xFFu, lu = D.y >> 24;
+        int32_t q = (int32_t)D.z - (int32_t)W;
+        auto lit = [&](uint32_t id) __attribute__((always_inline)) {
+          const uint32_t ent = e.com_ent[id];
+          evt_copy(sb, q, (const uint32_t*)s_com, ent & 0xFFFFu, ent >> 16, gl);
+          q += (int32_t)(ent >> 16);
+        };
+        auto row = [&](uint32_t c, uint32_t len) __attribute__((always_inline)) {
+          const uint32_t* p = reinterpret_cast<const uint32_t*>(e.rows[c] + (size_t)D.x * e.stride[c]);
+          evt_copy(sb, q, p, 1u, len, gl);
+          q += (int32_t)len;
+        };
+        lit(kEvtLitA);
+        row(0u, ln);
+        evt_copy(sb, q, (const uint32_t*)s_b, 0u, e.b_len, gl);
+        q += (int32_t)e.b_len;
+        if (lns) row(1u, lns);
+        else lit(kEvtLitDefault);
+        lit(kEvtLitC);
+        if (lns) {
+          lit(kEvtLitD);
+          row(1u, lns);
+          lit(kEvtLitE2);
+        } else {
+          lit(kEvtLitE1);
+        }
+        row(0u, ln);
+        if (lu) {
+          lit(kEvtLitF);
+          row(2u, lu);
+        }
+        const uint4 S = s_stage[stage];
+        evt_copy(sb, q, (const uint32_t*)s_tails, S.x, S.y, gl);
+      }
+      __syncthreads();
+      for (uint32_t c = threadIdx.x; c < kEvtWin / 16u; c += kBlock) {
+        const uint32_t P = W + 16u * c;
+        const uint32_t lo = max(P, head), hi = min(P + 16u, tend);
+        if (lo >= hi) continue;
+        if (hi - lo == 16u) {
+          *reinterpret_cast<uint4*>(base + P) = s_out[c];
+        } else {  // a chunk shared with the neighbouring tile: this tile's bytes only
+          for (uint32_t b = lo; b < hi; ++b) base[b] = (char)sb[b - W];
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
 }  // namespace
 
 struct kwk_emitter {
@@ -1366,6 +1647,12 @@ struct kwk_emitter {
     DevBuf<uint64_t> d_fin_offsets;
     DevBuf<char> d_fin_out;
     uint64_t fin_cap_items = 0, fin_cap_bytes = 0;
+    // the event stream (kwk_evt_load)
+    unsigned long long* d_evt_totals = nullptr;  // 8 words of d_evt_totals_all (an alias, not owned)
+    DevBuf<kwk_evt_item> d_evt_items;
+    DevBuf<uint64_t> d_evt_offsets;
+    DevBuf<char> d_evt_out;
+    uint64_t evt_cap_items = 0, evt_cap_bytes = 0;
   };
   std::vector<OutSet> sets;
   uint32_t cur = 0;               // the set of the last emission
@@ -1391,6 +1678,18 @@ struct kwk_emitter {
   } fm;
   DevBuf<unsigned long long> d_fin_totals_all;
   uint64_t fin_req_items = 0, fin_req_bytes = 0;  // kwk_emit_reserve_fin's room, given to every set
+  bool evt = false;               // an event program is loaded: every emission also emits its stream
+  bool evt_any = false;           // ... and some stage of it records an Event (else its launches are skipped)
+  EvtArgs e{};                    // the kernels' view of it: its pointers alias `evm`
+  struct EvtMem {                 // its device tables, identity columns and tile arrays
+    DevBuf<uint4> stages;
+    DevBuf<uint32_t> tails, com, tile_items;
+    DevBuf<uint8_t> rows[3];
+    DevBuf<unsigned long long> tile_bytes;
+  } evm;
+  uint32_t evt_fixed = 0;         // bytes of the literals every body has, without `.<hex>","namespace":"`
+  DevBuf<unsigned long long> d_evt_totals_all;
+  uint64_t evt_req_items = 0, evt_req_bytes = 0;  // kwk_evt_reserve's room, given to every set
   uint64_t tpl_lits = 0;          // literal bytes of every skeleton's pieces
   uint32_t tpl_now_slots = 0;     // Now slots of every skeleton's pieces
 
@@ -1450,6 +1749,7 @@ kwk_status make_sets(kwk_emitter* em, uint32_t n) {
   for (uint32_t i = 0; i < n; ++i) {
     em->sets[i].d_totals = em->d_totals_all + 8u * i;
     em->sets[i].d_fin_totals = em->d_fin_totals_all ? em->d_fin_totals_all + 8u * i : nullptr;
+    em->sets[i].d_evt_totals = em->d_evt_totals_all ? em->d_evt_totals_all + 8u * i : nullptr;
     HIP_TRY(em->sets[i].ev0.create(hipEventDefault));
     HIP_TRY(em->sets[i].ev1.create(hipEventDefault));
   }
@@ -1681,6 +1981,23 @@ kwk_status reserve_sets(kwk_emitter* em, uint32_t n_sets, uint32_t max_items, ui
       }
     }
   }
+  if (em->evt) {  // the event stream's room, in every set
+    for (kwk_emitter::OutSet& o : em->sets) {
+      if (em->evt_req_items > o.evt_cap_items || !o.d_evt_offsets) {
+        o.evt_cap_items = 0;
+        const size_t ni = (size_t)std::max<uint64_t>(1, em->evt_req_items);
+        HIP_TRY(o.d_evt_items.alloc(ni));
+        HIP_TRY(o.d_evt_offsets.alloc(ni + 1));
+        o.evt_cap_items = ni;
+      }
+      if (em->evt_req_bytes > o.evt_cap_bytes || !o.d_evt_out) {
+        o.evt_cap_bytes = 0;
+        const size_t nb = (size_t)std::max<uint64_t>(1, em->evt_req_bytes);
+        HIP_TRY(o.d_evt_out.alloc(nb + 16));
+        o.evt_cap_bytes = nb;
+      }
+    }
+  }
   if (em->sticky_armed) {  // the host reserves again: later emissions run
     if (kwk_status st = fill(em, em->d_sticky, 0, 4)) return st;
     em->sticky_armed = false;
@@ -1697,6 +2014,9 @@ kwk_status enqueue_emission(kwk_emitter* em, EmitArgs& a, int64_t now_ns) {
     if (kwk_status st = reserve_sets(em, (uint32_t)em->sets.size(), 1, 1)) return st;
   if (em->fin && !em->sets[0].d_fin_offsets)
     if (kwk_status st = reserve_sets(em, (uint32_t)em->sets.size(), 0, 0)) return st;
+  if (em->evt && !em->sets[0].d_evt_offsets)
+    if (kwk_status st = reserve_sets(em, (uint32_t)em->sets.size(), 0, 0)) return st;
+  if (em->evt && now_ns < 0) return fail(KWK_EINVAL, "an event program is loaded: now_ns < 0");
   const bool src16 = a.p16 != nullptr;
   if (src16) HIP_TRY(em->d_seg_base.grow((size_t)a.n_segs + 1u));  // (its free synchronises the device: no kernel still reads it)
   const uint32_t n_sets = (uint32_t)em->sets.size();
@@ -1724,12 +2044,12 @@ kwk_status enqueue_emission(kwk_emitter* em, EmitArgs& a, int64_t now_ns) {
   a.now_len = (uint32_t)now.size();
   // (one set with a finalizer program: the flag only joins the emission's two streams — a finalizer
   // overflow stops its merge-patch writer — and every emission stands alone, so it starts cleared)
-  if ((em->saw_cap || (em->fin && n_sets == 1u)) && em->sticky_armed) {  // the host has seen the overflow and emits again
+  if ((em->saw_cap || ((em->fin || em->evt) && n_sets == 1u)) && em->sticky_armed) {  // the host has seen the overflow and emits again
     HIP_TRY(hipMemsetAsync(em->d_sticky, 0, 4, em->stream));
     em->sticky_armed = false;
   }
   em->saw_cap = false;
-  if (a.sticky_on || em->fin) em->sticky_armed = true;
+  if (a.sticky_on || em->fin || em->evt) em->sticky_armed = true;
   FinArgs f = em->f;
   EmitArgs fa = a;  // emit_scan_kernel over the finalizer stream's tile arrays and totals
   if (em->fin) {
@@ -1745,6 +2065,32 @@ kwk_status enqueue_emission(kwk_emitter* em, EmitArgs& a, int64_t now_ns) {
     fa.cap_items = f.cap_items;
     fa.cap_bytes = f.cap_bytes;
     fa.sticky_on = 1u;
+  }
+  EvtArgs e = em->e;
+  EmitArgs ea = a;  // emit_scan_kernel over the event stream's tile arrays and totals
+  if (em->evt) {
+    e.totals = o.d_evt_totals;
+    e.items = o.d_evt_items;
+    e.offsets = o.d_evt_offsets;
+    e.out = o.d_evt_out;
+    e.cap_items = o.evt_cap_items;
+    e.cap_bytes = o.evt_cap_bytes;
+    char hex[24];
+    const int hn = snprintf(hex, sizeof hex, ".%llx", (unsigned long long)now_ns);
+    const std::string b = std::string(hex, (size_t)hn) + "\",\"namespace\":\"";
+    memset(e.b, 0, sizeof e.b);
+    memcpy(e.b, b.data(), b.size());  // (at most 1 + 16 + 15 bytes)
+    e.b_len = (uint32_t)b.size();
+    e.base_bytes = em->evt_fixed + e.b_len;
+    // metav1.Time: whole seconds (20 bytes for every now_ns >= 0 an int64_t holds: the year is at most 2262)
+    const std::string ts = kwkfmt::rfc3339nano(now_ns / 1000000000 * 1000000000);
+    memcpy(e.ts, ts.data(), std::min(ts.size(), sizeof e.ts));
+    ea.tile_items = e.tile_items;
+    ea.tile_bytes = e.tile_bytes;
+    ea.totals = e.totals;
+    ea.cap_items = e.cap_items;
+    ea.cap_bytes = e.cap_bytes;
+    ea.sticky_on = 1u;
   }
   // the list's count lives on the device: every tile loop reads it; the grid covers the capacity
   HIP_TRY(hipEventRecord(o.ev0, em->stream));
@@ -1778,6 +2124,15 @@ kwk_status enqueue_emission(kwk_emitter* em, EmitArgs& a, int64_t now_ns) {
     hipLaunchKernelGGL(emit_scan_kernel, dim3(1), dim3(kScanBlock), 0, em->stream, fa);
     HIP_TRY(hipGetLastError());
   }
+  if (em->evt && !em->evt_any) {  // no stage records an Event: an empty stream, no launch
+    HIP_TRY(hipMemsetAsync(e.totals, 0, 5 * 8, em->stream));
+  } else if (em->evt) {  // sized and scanned before any writer runs: an overflow of one stream stops all three
+    if (src16) hipLaunchKernelGGL(emit_evt_size_kernel<kSrc16>, dim3(em->grid), dim3(kBlock), 0, em->stream, a, e);
+    else hipLaunchKernelGGL(emit_evt_size_kernel<kSrc32>, dim3(em->grid), dim3(kBlock), 0, em->stream, a, e);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(emit_scan_kernel, dim3(1), dim3(kScanBlock), 0, em->stream, ea);
+    HIP_TRY(hipGetLastError());
+  }
   const bool wl = lds && vals16;  // the write kernel's LDS path also stages the value rows
   // the chunk writer: templates (literals + Now per slot) within kTplBytes, pieces in skeleton order
   const bool chunk = wl && em->chunk_ok && em->tpl_lits + (uint64_t)em->tpl_now_slots * a.now_len + 16u <= kTplBytes;
@@ -1801,6 +2156,11 @@ kwk_status enqueue_emission(kwk_emitter* em, EmitArgs& a, int64_t now_ns) {
   if (em->fin && em->fin_any) {
     if (src16) hipLaunchKernelGGL(emit_fin_write_kernel<kSrc16>, dim3(em->grid), dim3(kBlock), 0, em->stream, a, f);
     else hipLaunchKernelGGL(emit_fin_write_kernel<kSrc32>, dim3(em->grid), dim3(kBlock), 0, em->stream, a, f);
+    HIP_TRY(hipGetLastError());
+  }
+  if (em->evt && em->evt_any) {
+    if (src16) hipLaunchKernelGGL(emit_evt_write_kernel<kSrc16>, dim3(em->grid), dim3(kBlock), 0, em->stream, a, e);
+    else hipLaunchKernelGGL(emit_evt_write_kernel<kSrc32>, dim3(em->grid), dim3(kBlock), 0, em->stream, a, e);
     HIP_TRY(hipGetLastError());
   }
   HIP_TRY(hipEventRecord(o.ev1, em->stream));
@@ -1920,6 +2280,15 @@ kwk_status kwk_emit_result(kwk_emitter* em, uint32_t* n_items, uint64_t* n_bytes
       em->saw_cap = true;
       return fail(KWK_ECAP, "the emission's finalizer patches exceed their reservation: kwk_emit_reserve_fin(" +
                                 std::to_string(ft[0]) + ", " + std::to_string(ft[1]) + ") and emit again");
+    }
+  }
+  if (em->evt && o.d_evt_totals) {
+    unsigned long long et[2];
+    if (kwk_status st = copy_out(em, et, o.d_evt_totals, sizeof et)) return st;
+    if (et[0] > o.evt_cap_items || et[1] > o.evt_cap_bytes) {
+      em->saw_cap = true;
+      return fail(KWK_ECAP, "the emission's events exceed their reservation: kwk_evt_reserve(" + std::to_string(et[0]) +
+                                ", " + std::to_string(et[1]) + ") and emit again");
     }
   }
   return KWK_OK;
@@ -2129,6 +2498,253 @@ kwk_status kwk_emit_fin_copy(kwk_emitter* em, kwk_emit_fin_item* items, uint64_t
     offsets[0] = 0;
   }
   if (kwk_status st = copy_out(em, bytes, o.d_fin_out, (size_t)nb)) return st;
+  return KWK_OK;
+}
+
+// ---- Events (kwok_events.h)
+
+// a kwk_evt_program checked and turned into the kernels' tables (no emitter, no device)
+struct EvtBuilt {
+  EvtArgs e{};
+  std::vector<uint4> stages;
+  std::vector<uint32_t> tw, cw;  // the tails' and the shared literals' bytes as dwords
+  std::string tails;
+  bool any = false, use_ns = false;
+  uint32_t strides[3] = {0, 0, 0};
+  uint32_t fixed = 0;
+};
+
+static kwk_status evt_build(const kwk_evt_program* g, EvtBuilt& out) {
+  if (!g->kind || !g->api_version || !g->component || (g->n_stages && (!g->stage_flags || !g->text_off || !g->text)))
+    return fail(KWK_EINVAL, "event program: null pointer");
+  if (g->n_stages > KWK_MAX_STAGES)  // (the kernels' per-stage LDS tables hold KWK_MAX_STAGES entries)
+    return fail(KWK_EINVAL, "event program: " + std::to_string(g->n_stages) + " stages (more than " +
+                                std::to_string(KWK_MAX_STAGES) + ")");
+  // only text that json.Marshal writes unchanged: printable ASCII without " \\ < > &
+  auto plain = [](const std::string& v, const char* what, std::string& bad) {
+    for (const char ch : v) {
+      const unsigned char b = (unsigned char)ch;
+      if (b < 0x20 || b > 0x7E || b == '"' || b == '\\' || b == '<' || b == '>' || b == '&') {
+        char hex[8];
+        snprintf(hex, sizeof hex, "0x%02x", b);
+        bad = std::string("event program: ") + what + " has byte " + hex + " (outside 0x20..0x7E or one of \" \\ < > &)";
+        return false;
+      }
+    }
+    return true;
+  };
+  std::string bad;
+  const std::string kind = g->kind, av = g->api_version, comp = g->component;
+  if (!plain(kind, "kind", bad) || !plain(av, "api_version", bad) || !plain(comp, "component", bad)) return fail(KWK_EINVAL, bad);
+  if (kind.size() > 63) return fail(KWK_EINVAL, "event program: kind longer than 63 bytes");
+  const uint32_t strides[3] = {g->stride_name, g->stride_namespace, g->stride_uid};
+  const char* const cols[3] = {"name", "namespace", "uid"};
+  for (int c = 0; c < 3; ++c) {
+    if (c == 1 && strides[c] == 0) continue;  // a cluster-scoped kind: no column
+    if (strides[c] < 4 || strides[c] > 256 || strides[c] % 4)
+      return fail(KWK_EINVAL, std::string("event program: the ") + cols[c] + " stride must be a multiple of 4 in 4..256");
+  }
+  // the typed Node controller passes no namespace (node_controller.go:369): the column is not read
+  out.use_ns = strides[1] != 0 && !(av.empty() && kind == "Node");
+  // the shared literals, each at a 4-byte aligned offset
+  std::string lits[kEvtLits];
+  lits[kEvtLitA] = "{\"metadata\":{\"name\":\"";
+  lits[kEvtLitC] = "\",\"creationTimestamp\":null},\"involvedObject\":{\"kind\":\"" + kind + "\"";
+  lits[kEvtLitD] = ",\"namespace\":\"";
+  lits[kEvtLitE1] = ",\"name\":\"";
+  lits[kEvtLitE2] = "\",\"name\":\"";
+  lits[kEvtLitF] = "\",\"uid\":\"";
+  lits[kEvtLitDefault] = "default";
+  EvtArgs& e = out.e;
+  std::string com;
+  for (uint32_t i = 0; i < kEvtLits; ++i) {
+    e.com_ent[i] = (uint32_t)com.size() | (uint32_t)lits[i].size() << 16;
+    com += lits[i];
+    com.resize((com.size() + 3u) & ~size_t(3), '\0');
+  }
+  if (com.size() > kEvtComWords * 4) return fail(KWK_EINVAL, "event program: the shared literals do not fit");
+  // the stages' tails: everything after the last inserted value, the timestamp's 20 bytes left blank twice
+  std::vector<uint4>& stages = out.stages;
+  stages.assign(std::max(1u, g->n_stages), make_uint4(0u, 0u, 0u, 0u));
+  std::string& tails = out.tails;
+  uint64_t text = 0;
+  bool& any = out.any;
+  any = false;
+  for (uint32_t s = 0; s < g->n_stages; ++s) {
+    if (!(g->stage_flags[s] & KWK_EVT_STAGE_EVENT)) continue;
+    std::string f[3];
+    static const char* const names[3] = {"type", "reason", "message"};
+    for (int k = 0; k < 3; ++k) {
+      const uint32_t o0 = g->text_off[3 * s + k], o1 = g->text_off[3 * s + k + 1];
+      if (o1 < o0) return fail(KWK_EINVAL, "event program: text offsets");
+      f[k].assign(g->text + o0, o1 - o0);
+      if (!plain(f[k], names[k], bad)) return fail(KWK_EINVAL, bad + " (stage " + std::to_string(s) + ")");
+      text += f[k].size();
+    }
+    if (f[0] != "Normal" && f[0] != "Warning")
+      return fail(KWK_EINVAL, "event program: stage " + std::to_string(s) + " has type \"" + f[0] + "\" (generateEvent sends nothing)");
+    std::string t = "\"";
+    if (!av.empty()) t += ",\"apiVersion\":\"" + av + "\"";
+    t += "},";
+    if (!f[1].empty()) t += "\"reason\":\"" + f[1] + "\",";
+    if (!f[2].empty()) t += "\"message\":\"" + f[2] + "\",";
+    t += "\"source\":{\"component\":\"" + comp + "\"},\"firstTimestamp\":\"";
+    const uint32_t off = (uint32_t)tails.size();
+    const uint32_t t1 = off + (uint32_t)t.size();
+    t += std::string(20, ' ') + "\",\"lastTimestamp\":\"";
+    const uint32_t t2 = off + (uint32_t)t.size();
+    t += std::string(20, ' ') + "\",\"count\":1,\"type\":\"" + f[0] + "\",\"eventTime\":null,\"reportingComponent\":\"" + comp +
+         "\",\"reportingInstance\":\"\"}";
+    stages[s] = make_uint4(off, (uint32_t)t.size(), t1, t2);
+    tails += t;
+    tails.resize((tails.size() + 3u) & ~size_t(3), '\0');
+    any = true;
+  }
+  if (text > KWK_EVT_MAX_TEXT)
+    return fail(KWK_EINVAL, "event program: " + std::to_string(text) + " bytes of stage text (more than " +
+                                std::to_string(KWK_EVT_MAX_TEXT) + ")");
+  if (tails.size() > kEvtTailBytes)
+    return fail(KWK_EINVAL, "event program: " + std::to_string(tails.size()) + " bytes of stage tails (more than " +
+                                std::to_string(kEvtTailBytes) + ")");
+  out.tw.assign(std::max<size_t>(1, tails.size() / 4), 0u);
+  out.cw.assign(com.size() / 4, 0u);
+  memcpy(out.tw.data(), tails.data(), tails.size());
+  memcpy(out.cw.data(), com.data(), com.size());
+  for (int c = 0; c < 3; ++c) out.strides[c] = strides[c];
+  out.fixed = (uint32_t)(lits[kEvtLitA].size() + lits[kEvtLitC].size() + lits[kEvtLitE1].size());
+  return KWK_OK;
+}
+
+kwk_status kwk_evt_check(const kwk_evt_program* g) {
+  ErrScope es_(nullptr);
+  if (!g) return fail(KWK_EINVAL, "null argument");
+  EvtBuilt b;
+  return evt_build(g, b);
+}
+
+kwk_status kwk_evt_load(kwk_emitter* em, const kwk_evt_program* g) {
+  ErrScope es_(em ? &em->err : nullptr);
+  if (!em || !g) return fail(KWK_EINVAL, "null argument");
+  if (em->evt) return fail(KWK_ESTATE, "kwk_evt_load: the emitter has an event program");
+  EvtBuilt b;
+  if (kwk_status st = evt_build(g, b)) return st;
+  if (g->n_stages != em->p.n_stages)
+    return fail(KWK_EINVAL, "event program: " + std::to_string(g->n_stages) + " stages, the emit program has " +
+                                std::to_string(em->p.n_stages));
+  EvtArgs e = b.e;
+  const std::vector<uint4>& stages = b.stages;
+  const std::vector<uint32_t>&tw = b.tw, &cw = b.cw;
+  const std::string& tails = b.tails;
+  const uint32_t* strides = b.strides;
+  const bool use_ns = b.use_ns, any = b.any;
+  if (kwk_status st = bind(em)) return st;
+  HIP_TRY(hipStreamSynchronize(em->stream));
+  em->evm = kwk_emitter::EvtMem{};  // (what an earlier, failed load left: the stream is idle)
+  if (kwk_status st = upload(em, em->evm.stages, &e.stages, stages.data(), stages.size())) return st;
+  if (kwk_status st = upload(em, em->evm.tails, &e.tails, tw.data(), tw.size())) return st;
+  if (kwk_status st = upload(em, em->evm.com, &e.com, cw.data(), cw.size())) return st;
+  e.n_tail_words = (uint32_t)(tails.size() / 4);
+  e.n_com_words = (uint32_t)cw.size();
+  e.n_stages = g->n_stages;
+  for (int c = 0; c < 3; ++c) {
+    e.stride[c] = strides[c];
+    e.rows[c] = nullptr;
+    if (c == 1 && !use_ns) continue;
+    // (16 bytes more: the writer's dword reads may run one dword past the last row's text)
+    const size_t bytes = (size_t)std::max(1u, em->capacity) * strides[c] + 16;
+    HIP_TRY(em->evm.rows[c].alloc(bytes));
+    if (kwk_status st = fill(em, em->evm.rows[c], 0xFF, bytes)) return st;  // every row unusable until set
+    e.rows[c] = em->evm.rows[c];
+  }
+  HIP_TRY(em->evm.tile_items.alloc(em->max_tiles));
+  e.tile_items = em->evm.tile_items;
+  HIP_TRY(em->evm.tile_bytes.alloc(em->max_tiles));
+  e.tile_bytes = em->evm.tile_bytes;
+  DevBuf<unsigned long long> totals;  // the emitter's once it is zeroed (make_sets looks at d_evt_totals_all)
+  HIP_TRY(totals.alloc(kMaxSets * 8));
+  if (kwk_status st = fill(em, totals, 0, kMaxSets * 8 * 8)) return st;
+  em->d_evt_totals_all = std::move(totals);
+  for (size_t i = 0; i < em->sets.size(); ++i) em->sets[i].d_evt_totals = em->d_evt_totals_all + 8u * i;
+  em->evt_fixed = b.fixed;
+  em->e = e;
+  em->evt = true;
+  em->evt_any = any;
+  return KWK_OK;
+}
+
+kwk_status kwk_evt_set_rows(kwk_emitter* em, uint32_t column, uint32_t first, uint32_t n, const uint8_t* data) {
+  ErrScope es_(em ? &em->err : nullptr);
+  if (!em || (n && !data)) return fail(KWK_EINVAL, "null argument");
+  if (!em->evt) return fail(KWK_ESTATE, "kwk_evt_load must come first");
+  if (column > KWK_EVT_COL_UID) return fail(KWK_EINVAL, "kwk_evt_set_rows: column must be KWK_EVT_COL_NAME, _NAMESPACE or _UID");
+  if ((uint64_t)first + n > em->capacity) return fail(KWK_EINVAL, "rows beyond the capacity");
+  if (!em->e.rows[column]) {
+    if (column == KWK_EVT_COL_NAMESPACE && em->e.stride[column]) return KWK_OK;  // the typed Node reference has no namespace
+    return fail(KWK_EINVAL, "kwk_evt_set_rows: the program has no namespace column (stride 0)");
+  }
+  const uint32_t stride = em->e.stride[column];
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint8_t len = data[(size_t)i * stride];
+    if (len != KWK_EVT_ROW_UNUSABLE && len > stride - 1u)
+      return fail(KWK_EINVAL, "kwk_evt_set_rows: row " + std::to_string(first + i) + " has length " + std::to_string(len) +
+                                  ", the stride holds " + std::to_string(stride - 1u));
+  }
+  if (kwk_status st = bind(em)) return st;
+  return copy_in(em, em->evm.rows[column].get() + (size_t)first * stride, data, (size_t)n * stride);
+}
+
+kwk_status kwk_evt_reserve(kwk_emitter* em, uint32_t max_items, uint64_t max_bytes) {
+  ErrScope es_(em ? &em->err : nullptr);
+  if (!em) return fail(KWK_EINVAL, "null emitter");
+  if (!em->evt) return fail(KWK_ESTATE, "kwk_evt_load must come first");
+  em->evt_req_items = max_items;  // (a set keeps the room it has; sets made later get this)
+  em->evt_req_bytes = max_bytes;
+  return reserve_sets(em, (uint32_t)em->sets.size(), 0, 0);
+}
+
+kwk_status kwk_evt_result(kwk_emitter* em, uint32_t* n_items, uint64_t* n_bytes, uint32_t* launched) {
+  ErrScope es_(em ? &em->err : nullptr);
+  if (!em || !n_items || !n_bytes) return fail(KWK_EINVAL, "null argument");
+  if (!em->evt) return fail(KWK_ESTATE, "kwk_evt_load must come first");
+  uint32_t mi = 0;
+  uint64_t mb = 0;
+  const kwk_status st = kwk_emit_result(em, &mi, &mb);
+  if (st != KWK_OK && st != KWK_ECAP) return st;
+  unsigned long long et[2] = {0, 0};
+  const std::string msg = em->err;
+  if (em->selected().d_evt_totals)
+    if (kwk_status s2 = copy_out(em, et, em->selected().d_evt_totals, sizeof et)) return s2;
+  *n_items = (uint32_t)et[0];
+  *n_bytes = et[1];
+  if (launched) *launched = em->evt_any ? 1u : 0u;
+  return st == KWK_OK ? KWK_OK : fail(st, msg);
+}
+
+kwk_status kwk_evt_device(kwk_emitter* em, const kwk_evt_item** items, const uint64_t** offsets, const char** bytes) {
+  ErrScope es_(em ? &em->err : nullptr);
+  if (!em) return fail(KWK_EINVAL, "null emitter");
+  if (!em->evt) return fail(KWK_ESTATE, "kwk_evt_load must come first");
+  const kwk_emitter::OutSet& o = em->selected();
+  if (items) *items = o.d_evt_items;
+  if (offsets) *offsets = o.d_evt_offsets;
+  if (bytes) *bytes = o.d_evt_out;
+  return KWK_OK;
+}
+
+kwk_status kwk_evt_copy(kwk_emitter* em, kwk_evt_item* items, uint64_t* offsets, char* bytes) {
+  ErrScope es_(em ? &em->err : nullptr);
+  uint32_t ni = 0;
+  uint64_t nb = 0;
+  if (kwk_status st = kwk_evt_result(em, &ni, &nb, nullptr)) return st;
+  if ((ni && !items) || (nb && !bytes) || !offsets) return fail(KWK_EINVAL, "null argument");
+  const kwk_emitter::OutSet& o = em->selected();
+  if (ni) {
+    if (kwk_status st = copy_out(em, items, o.d_evt_items, (size_t)ni * sizeof(kwk_evt_item))) return st;
+    if (kwk_status st = copy_out(em, offsets, o.d_evt_offsets, ((size_t)ni + 1) * 8)) return st;
+  } else {
+    offsets[0] = 0;
+  }
+  if (kwk_status st = copy_out(em, bytes, o.d_evt_out, (size_t)nb)) return st;
   return KWK_OK;
 }
 

@@ -240,6 +240,15 @@ struct kwk_patcher {
   bool has_fin = false;
   std::vector<std::string> fin_values;
   std::vector<FinStage> fin_stages;
+  // the event program (the spec's optional "events"): per stage the Event's constant strings,
+  // has = false for a stage that records nothing
+  struct EvStage {
+    bool has = false;
+    std::string type, reason, message;
+  };
+  bool has_events = false;
+  std::string ev_kind, ev_api_version, ev_component;
+  std::vector<EvStage> ev_stages;
 };
 
 namespace {
@@ -1068,6 +1077,22 @@ kwk_status kwk_patcher_create(const char* spec_json, kwk_patcher** out) {
       }
       p->has_fin = true;
     }
+    if (const JV* ej = spec.get("events"); ej && ej->t == JV::OBJ) {
+      p->ev_kind = str(member(*ej, "kind"));
+      p->ev_api_version = str(member(*ej, "api_version"));
+      p->ev_component = str(member(*ej, "component"));
+      for (const JV& sj : member(*ej, "stages").a) {
+        kwk_patcher::EvStage es;
+        if (sj.t != JV::NUL) {
+          es.has = true;
+          es.type = str(member(sj, "type"));
+          es.reason = str(member(sj, "reason"));
+          es.message = str(member(sj, "message"));
+        }
+        p->ev_stages.push_back(std::move(es));
+      }
+      p->has_events = true;
+    }
   } catch (const BadSpec& b) {
     return fail(KWK_EINVAL, "patch spec: " + b.what);
   }
@@ -1460,6 +1485,109 @@ kwk_status kwk_patch_finalizer_list(kwk_patcher* p, uint32_t word, uint32_t* n, 
   *len = o.size();
   if (o.size() > cap) return fail(KWK_ECAP, "kwk_patch_finalizer_list: " + std::to_string(o.size()) + " bytes needed");
   if (!o.empty()) memcpy(out, o.data(), o.size());
+  return KWK_OK;
+}
+
+// ---- the Event of a fired stage (client-go tools/record/event.go generateEvent / makeEvent; the
+// bytes are json.Marshal(*v1.Event), restated in kwok_patch.h)
+
+namespace {
+
+// encoding/json's string encoding (escapeHTML on) appended to o; false with `bad` set for what this
+// renderer refuses: a control byte other than \n \r \t, or invalid UTF-8
+bool ev_escape(std::string& o, const char* s, const char* what, std::string& bad) {
+  static const char hex[] = "0123456789abcdef";
+  const unsigned char* b = reinterpret_cast<const unsigned char*>(s);
+  const size_t n = strlen(s);
+  auto refuse = [&](const char* why, size_t i) {
+    char buf[96];
+    snprintf(buf, sizeof buf, "%s: %s 0x%02x at offset %zu", what, why, b[i], i);
+    bad = buf;
+    return false;
+  };
+  o += '"';
+  for (size_t i = 0; i < n;) {
+    const unsigned char c = b[i];
+    if (c < 0x80) {
+      if (c == '"' || c == '\\') { o += '\\'; o += (char)c; }
+      else if (c == '\n') o += "\\n";
+      else if (c == '\r') o += "\\r";
+      else if (c == '\t') o += "\\t";
+      else if (c == '<' || c == '>' || c == '&') { o += "\\u00"; o += hex[c >> 4]; o += hex[c & 15]; }
+      else if (c < 0x20) return refuse("control byte", i);
+      else o += (char)c;
+      ++i;
+      continue;
+    }
+    // one UTF-8 sequence, as utf8.DecodeRune accepts it (no overlong form, surrogate or > U+10FFFF)
+    size_t len = 0;
+    unsigned char lo = 0x80, hi = 0xBF;
+    if (c >= 0xC2 && c <= 0xDF) len = 2;
+    else if (c >= 0xE0 && c <= 0xEF) { len = 3; if (c == 0xE0) lo = 0xA0; if (c == 0xED) hi = 0x9F; }
+    else if (c >= 0xF0 && c <= 0xF4) { len = 4; if (c == 0xF0) lo = 0x90; if (c == 0xF4) hi = 0x8F; }
+    else return refuse("invalid UTF-8 byte", i);
+    if (i + len > n) return refuse("invalid UTF-8 byte", i);
+    if (b[i + 1] < lo || b[i + 1] > hi) return refuse("invalid UTF-8 byte", i);
+    for (size_t k = 2; k < len; ++k)
+      if (b[i + k] < 0x80 || b[i + k] > 0xBF) return refuse("invalid UTF-8 byte", i);
+    if (len == 3 && c == 0xE2 && b[i + 1] == 0x80 && (b[i + 2] == 0xA8 || b[i + 2] == 0xA9)) {
+      o += "\\u202";
+      o += hex[b[i + 2] & 15];
+    } else {
+      o.append(s + i, len);
+    }
+    i += len;
+  }
+  o += '"';
+  return true;
+}
+
+}  // namespace
+
+kwk_status kwk_patch_event(kwk_patcher* p, uint32_t stage, const char* ns, const char* name, const char* uid,
+                           const char* api_version, int64_t now_ns, char* out, uint64_t cap, uint64_t* len) {
+  ErrScope es_(p ? &p->err : nullptr);
+  if (!p || !len || !ns || !name || !uid || !api_version || (cap && !out)) return fail(KWK_EINVAL, "null argument");
+  if (!p->has_events) return fail(KWK_ESTATE, "the patch spec has no event program");
+  if (now_ns < 0) return fail(KWK_EINVAL, "kwk_patch_event: now_ns < 0");
+  if (stage >= p->ev_stages.size()) return fail(KWK_EINVAL, "stage out of range");
+  const kwk_patcher::EvStage& S = p->ev_stages[stage];
+  *len = 0;
+  if (!S.has) return KWK_OK;
+  // the typed Pod / Node controllers' references carry no apiVersion, the Node's no namespace;
+  // every other kind's is the object's own
+  const bool typed = p->ev_api_version.empty();
+  const char* ref_ns = typed && p->ev_kind == "Node" ? "" : ns;
+  const char* ref_av = typed ? "" : api_version;
+  char hex[24];
+  snprintf(hex, sizeof hex, ".%llx", (unsigned long long)now_ns);
+  const std::string ev_name = std::string(name) + hex;
+  const std::string ts = kwkfmt::rfc3339nano(now_ns / 1000000000 * 1000000000);  // metav1.Time: whole seconds
+  std::string o, bad;
+  bool ok = true;
+  auto put = [&](const char* key, const char* v, const char* what) {
+    o += key;
+    ok = ok && ev_escape(o, v, what, bad);
+  };
+  put("{\"metadata\":{\"name\":", ev_name.c_str(), "name");
+  put(",\"namespace\":", *ref_ns ? ref_ns : "default", "namespace");  // makeEvent: the reference's, or default
+  put(",\"creationTimestamp\":null},\"involvedObject\":{\"kind\":", p->ev_kind.c_str(), "kind");
+  if (*ref_ns) put(",\"namespace\":", ref_ns, "namespace");
+  if (*name) put(",\"name\":", name, "name");
+  if (*uid) put(",\"uid\":", uid, "uid");
+  if (*ref_av) put(",\"apiVersion\":", ref_av, "apiVersion");
+  o += "},";
+  if (!S.reason.empty()) { put("\"reason\":", S.reason.c_str(), "reason"); o += ','; }
+  if (!S.message.empty()) { put("\"message\":", S.message.c_str(), "message"); o += ','; }
+  put("\"source\":{\"component\":", p->ev_component.c_str(), "component");
+  o += "},\"firstTimestamp\":\"" + ts + "\",\"lastTimestamp\":\"" + ts + "\",\"count\":1,";
+  put("\"type\":", S.type.c_str(), "type");
+  put(",\"eventTime\":null,\"reportingComponent\":", p->ev_component.c_str(), "component");
+  o += ",\"reportingInstance\":\"\"}";
+  if (!ok) return fail(KWK_EINVAL, "kwk_patch_event: " + bad);
+  *len = o.size();
+  if (o.size() > cap) return fail(KWK_ECAP, "kwk_patch_event: " + std::to_string(o.size()) + " bytes needed");
+  memcpy(out, o.data(), o.size());
   return KWK_OK;
 }
 

@@ -47,6 +47,13 @@ class CompileError(ValueError):
     pass
 
 
+# the Events of fired stages (KindProgram.event_spec): the types generateEvent accepts, the
+# recorder's EventSource component (controller.go:184) and the device program's literal budget
+EVENT_TYPES = ("Normal", "Warning")
+EVENT_COMPONENT = "kwok_controller"
+EVENT_MAX_TEXT = 16 * 1024
+
+
 _NORM = re.compile(r'"(?:[^"\\]|\\.)*"|\s+')
 
 
@@ -665,6 +672,39 @@ class KindProgram:
             stages.append({"flags": d.flags & keep, "add": [ids[v] for v in f.add] if f is not None else [],
                            "remove": sorted({ids[v] for v in f.remove}) if f is not None else []})
         return json.dumps({"values": values, "stages": stages})
+
+    def event_spec(self, device: bool = False) -> str:
+        """The event program (kwok_patch.h "events", kwok_events.h): the involved object's kind, the
+        apiVersion of its reference ("" for the typed Pod and Node controllers, which set none;
+        the resourceRef's group/version for every other kind), the recorder's component and, per
+        stage, the Event's type / reason / message, or null where the stage has no event or its
+        type is not Normal / Warning (generateEvent logs and sends nothing).
+        device=True refuses by name what the device stream does not carry: a stage string with a
+        byte outside 0x20..0x7E or one of " \\ < > &, and more than 16 KiB of stage text."""
+        kind = self.stages[0].kind if self.stages else ""
+        group = self.stages[0].api_group if self.stages else ""
+        stages, total = [], 0
+        for st in self.stages:
+            e = st.next.event
+            f = [x if isinstance(x, str) else "" if x is None else str(x)
+                 for x in ((e.type, e.reason, e.message) if e is not None else ())]
+            if e is None or f[0] not in EVENT_TYPES:
+                stages.append(None)
+                continue
+            if device:
+                for what, v in zip(("type", "reason", "message"), f):
+                    for b in v.encode("utf-8", "surrogatepass"):
+                        if b < 0x20 or b > 0x7E or b in b'"\\<>&':
+                            raise CompileError(f"event program not supported on the device: stage {st.name} {what} has "
+                                               f"byte 0x{b:02x} (outside 0x20..0x7E or one of \" \\ < > &); the host "
+                                               "renders the events")
+                total += sum(len(v) for v in f)
+            stages.append({"type": f[0], "reason": f[1], "message": f[2]})
+        if total > EVENT_MAX_TEXT:
+            raise CompileError(f"event program not supported on the device: {total} bytes of stage text (more than "
+                               f"{EVENT_MAX_TEXT}); the host renders the events")
+        return json.dumps({"kind": kind, "api_version": "" if group == "v1" and kind in ("Pod", "Node") else group,
+                           "component": EVENT_COMPONENT, "stages": stages})
 
     def describe(self) -> dict:
         feats = []

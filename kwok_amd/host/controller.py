@@ -29,6 +29,7 @@ import numpy as np
 from . import abi
 from .compiler import KindProgram, exploration_funcs
 from .engine import Engine, Ingest
+from .events import render_event
 from .gotpl import Renderer, rfc3339nano
 from .nextstate import apply_next, prune_empty
 
@@ -48,6 +49,11 @@ class KindController:
         self.last_patches = {}    # (slot, patch index) -> the patch bytes the last step applied (native)
         self.last_fin_patches = {}  # slot -> the finalizer JSON patch bytes the last step sent first (native)
         self.fin_refused = None   # why kwk_patch_finalizers is not used (the host mirror renders the ops)
+        self.last_events = {}     # slot -> the Event body the last step recorded first (stages with next.event)
+        self.event_errors = {}    # slot -> why the last step's Event of that slot could not be rendered
+        self.event_spec = program.event_spec() if hasattr(program, "event_spec") else None
+        self._event_spec_dict = json.loads(self.event_spec) if self.event_spec is not None else None
+        self._event_stages = self._event_spec_dict["stages"] if self.event_spec is not None else None
         if native:
             from .encoder import NativeIngest
             from .patchtpl import PatchProgram
@@ -59,7 +65,7 @@ class KindController:
             except ValueError as e:  # a shape the native program refuses by name: the Python mirror renders
                 self.fin_refused = str(e)
             self.patcher = PatchProgram(program.stages, self.funcs, n_threads=n_threads, program=native_prog,
-                                        finalizers=fin)
+                                        finalizers=fin, events=self.event_spec)
 
     def close(self):
         if self.native:
@@ -139,10 +145,33 @@ class KindController:
         self.handle(fired, now_ns)
         return fired
 
+    def _events(self, fired, now_ns: int):
+        """playStage's first send: the Event of every fired record whose stage has one, from the
+        objects as they are before the finalizer ops (kwk_patch_event natively, else its mirror)."""
+        self.last_events, self.event_errors = {}, {}
+        if self.event_spec is None:
+            return
+        for rec in fired:
+            i, s = int(rec["slot"]), int(rec["stage"])
+            if self._event_stages[s] is None or self.objs[i] is None:
+                continue
+            try:
+                if self.native:
+                    meta = self.objs[i].get("metadata") or {}
+                    b = self.patcher.event(s, meta.get("namespace") or "", meta.get("name") or "", meta.get("uid") or "",
+                                           self.objs[i].get("apiVersion") or "", now_ns)
+                else:
+                    b = render_event(self._event_spec_dict, s, self.objs[i], now_ns)
+            except (abi.EngineError, ValueError) as e:  # a string the renderer refuses: the step goes on
+                self.event_errors[i] = str(e)
+                continue
+            self.last_events[i] = b
+
     def handle(self, fired, now_ns: int):
-        """The hand-back of one step's fired list (kwk_fired_rec records): patches applied to the
-        cache, the DELTA_UNKNOWN rows written back."""
+        """The hand-back of one step's fired list (kwk_fired_rec records): the Events recorded,
+        patches applied to the cache, the DELTA_UNKNOWN rows written back."""
         slots, rows = [], []
+        self._events(fired, now_ns)
         if self.native:
             applied = self._apply_native(fired, now_ns)
             for i, new, _ in applied:

@@ -360,6 +360,8 @@ def lib():
         for n in EXPORTS:
             if n != "kwk_emit_last_error":
                 getattr(L, n).restype = C.c_int32
+        from . import events
+        events.bind(L)  # kwok_events.h's entry points, in the same library
         _lib = L
     return _lib
 
@@ -540,6 +542,41 @@ class Emitter:
         out = np.zeros(max(nb, 1), dtype=np.uint8)
         self._check(lib().kwk_emit_fin_copy(self.h, abi.ptr(items) if ni else None, abi.ptr(offs), abi.ptr(out)),
                     "kwk_emit_fin_copy")
+        return items, offs, out[:nb].tobytes()
+
+    # -- events (kwok_events.h)
+    def load_events(self, prog):
+        """kwk_evt_load: every later emission also emits its list's Events (prog: events.EventProgram)."""
+        self.event_program = prog
+        self._check(lib().kwk_evt_load(self.h, C.byref(prog.struct)), "kwk_evt_load")
+
+    def set_event_rows(self, first: int, cols: Dict[int, np.ndarray]):
+        """kwk_evt_set_rows: identity rows from slot `first` on (cols: EventProgram.rows(objs))."""
+        for c, rows in cols.items():
+            r = np.ascontiguousarray(rows, dtype=np.uint8)
+            self._check(lib().kwk_evt_set_rows(self.h, int(c), int(first), len(r), abi.ptr(r)), "kwk_evt_set_rows")
+
+    def reserve_events(self, items: int, nbytes: int):
+        self._check(lib().kwk_evt_reserve(self.h, int(items), int(nbytes)), "kwk_evt_reserve")
+
+    def event_result(self) -> Tuple[int, int, int, int]:
+        """(status, items, bytes, launched) of the selected emission's event stream; status
+        abi.KWK_ECAP exactly when the emission's readers return it."""
+        ni, nb, la = C.c_uint32(), C.c_uint64(), C.c_uint32()
+        st = lib().kwk_evt_result(self.h, C.byref(ni), C.byref(nb), C.byref(la))
+        if st != abi.KWK_ECAP:
+            self._check(st, "kwk_evt_result")
+        return int(st), int(ni.value), int(nb.value), int(la.value)
+
+    def collect_events(self):
+        """The selected emission's event stream -> (items structured array, offsets, bytes)."""
+        from .events import EVT_ITEM_DTYPE
+        st, ni, nb, _ = self.event_result()
+        self._check(st, "kwk_evt_result")
+        items = np.zeros(ni, dtype=EVT_ITEM_DTYPE)
+        offs = np.zeros(ni + 1, dtype=np.uint64)
+        out = np.zeros(max(nb, 1), dtype=np.uint8)
+        self._check(lib().kwk_evt_copy(self.h, abi.ptr(items) if ni else None, abi.ptr(offs), abi.ptr(out)), "kwk_evt_copy")
         return items, offs, out[:nb].tobytes()
 
     def elapsed_ms(self) -> float:

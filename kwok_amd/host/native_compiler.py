@@ -45,6 +45,8 @@ def lib():
                   "kwk_program_finalizer_spec"):
             getattr(L, n).argtypes = [C.c_void_p, C.POINTER(C.c_char_p)]
         L.kwk_program_finalizer_spec.restype = C.c_int32
+        L.kwk_program_event_spec.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p)]
+        L.kwk_program_event_spec.restype = C.c_int32
         L.kwk_program_patch_spec.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), C.c_void_p,
                                              C.c_uint32]
         for n in ("kwk_compile_stages", "kwk_program_destroy", "kwk_program_explore", "kwk_program_class",
@@ -173,6 +175,12 @@ class NativeProgram:
     def finalizer_spec(self) -> str:
         """kwk_program_finalizer_spec: KindProgram.finalizer_spec's JSON (CompileError names a refusal)."""
         return self._json(lib().kwk_program_finalizer_spec)
+
+    def event_spec(self, device: bool = False) -> str:
+        """kwk_program_event_spec: KindProgram.event_spec's JSON (CompileError names a device refusal)."""
+        p = C.c_char_p()
+        self._check(lib().kwk_program_event_spec(self.h, 1 if device else 0, C.byref(p)), "kwk_program_event_spec")
+        return p.value.decode()
 
     def patch_spec(self, funcs: Optional[Dict[str, object]] = None, version: str = "v0.6.0"):
         """-> (spec JSON for kwk_patcher_create, {(stage, patch): template id}) — PatchProgram's

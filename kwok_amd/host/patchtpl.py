@@ -543,9 +543,11 @@ def lib():
         L.kwk_patch_finalizer_word.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint32)]
         L.kwk_patch_finalizer_list.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p, C.c_uint64,
                                                C.POINTER(C.c_uint64)]
+        L.kwk_patch_event.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int64,
+                                      C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         for n in ("kwk_patcher_create", "kwk_patcher_destroy", "kwk_patch_render", "kwk_patch_skeleton",
                   "kwk_patch_object_values", "kwk_patch_finalizers", "kwk_patch_finalizer_word",
-                  "kwk_patch_finalizer_list"):
+                  "kwk_patch_finalizer_list", "kwk_patch_event"):
             getattr(L, n).restype = C.c_int32
         _lib = L
     return _lib
@@ -577,12 +579,15 @@ class PatchProgram:
     """
 
     def __init__(self, stages, funcs: Optional[Dict[str, object]] = None, version: str = "v0.6.0",
-                 n_threads: int = 1, program=None, finalizers: Optional[str] = None):
+                 n_threads: int = 1, program=None, finalizers: Optional[str] = None, events: Optional[str] = None):
         """program: a native_compiler.NativeProgram — the spec and template ids come from
         libkwok_compiler (kwk_program_patch_spec) instead of this module's compiler.
         finalizers: the finalizer program (KindProgram.finalizer_spec() / kwk_program_finalizer_spec),
-        the spec's "finalizers": kwk_patch_finalizers and the order-word helpers need it."""
+        the spec's "finalizers": kwk_patch_finalizers and the order-word helpers need it.
+        events: the event program (KindProgram.event_spec() / kwk_program_event_spec), the spec's
+        "events": kwk_patch_event needs it.  Neither changes the patch spec's own members."""
         self.has_finalizers = finalizers is not None
+        self.has_events = events is not None
         funcs = dict(funcs or {})
         self.n_threads = n_threads
         self.callbacks: Dict[int, Callable] = {}
@@ -608,6 +613,8 @@ class PatchProgram:
                         self.unsupported[(si, pi)] = "not compiled by libkwok_compiler"
             if finalizers is not None:
                 self.spec = json.dumps(dict(json.loads(self.spec), finalizers=json.loads(finalizers)))
+            if events is not None:
+                self.spec = json.dumps(dict(json.loads(self.spec), events=json.loads(events)))
             self.h = C.c_void_p()
             _check(lib().kwk_patcher_create(self.spec.encode(), C.byref(self.h)), "kwk_patcher_create")
             self._fn = _FN(self._callback)
@@ -627,6 +634,8 @@ class PatchProgram:
         spec = {"templates": self.templates, "funcs": fspec, "consts": consts}
         if finalizers is not None:
             spec["finalizers"] = json.loads(finalizers)
+        if events is not None:
+            spec["events"] = json.loads(events)
         self.spec = json.dumps(spec)
         self.h = C.c_void_p()
         _check(lib().kwk_patcher_create(self.spec.encode(), C.byref(self.h)), "kwk_patcher_create")
@@ -690,6 +699,21 @@ class PatchProgram:
             out = C.create_string_buffer(n.value)
             st = lib().kwk_patch_finalizers(self.h, int(stage), len(fins or []), b, len(b), out, len(out), C.byref(n))
         _check(st, "kwk_patch_finalizers", self.h)
+        return out.raw[:n.value]
+
+    def event(self, stage: int, ns: str, name: str, uid: str, api_version: str, now_ns: int) -> bytes:
+        """kwk_patch_event: the Event body playStage records first for an object fired by `stage`
+        (b"" = the stage records nothing).  Strings may be str or the raw bytes."""
+        if not -2**63 <= int(now_ns) < 2**63:
+            raise ValueError(f"kwk_patch_event: now_ns {now_ns} does not fit int64_t")
+        a = [x if isinstance(x, bytes) else x.encode("utf-8", "surrogatepass") for x in (ns, name, uid, api_version)]
+        n = C.c_uint64()
+        out = C.create_string_buffer(768)
+        st = lib().kwk_patch_event(self.h, int(stage), *a, int(now_ns), out, len(out), C.byref(n))
+        if st == abi.KWK_ECAP:
+            out = C.create_string_buffer(n.value)
+            st = lib().kwk_patch_event(self.h, int(stage), *a, int(now_ns), out, len(out), C.byref(n))
+        _check(st, "kwk_patch_event", self.h)
         return out.raw[:n.value]
 
     def finalizer_word(self, fins: Optional[Sequence[str]]) -> int:
