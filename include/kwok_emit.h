@@ -97,7 +97,14 @@ typedef struct {
  * the lane-per-record writer; any other bit of source is KWK_EINVAL) */
 
 const char* kwk_emit_last_error(const kwk_emitter* em);
-/* an emitter for `eng`'s fired lists over slots [0, capacity), on the engine's stream */
+/* an emitter for `eng`'s fired lists over slots [0, capacity), on the engine's stream.
+ * Its words, order words, value columns and event rows are per slot, for the engine's slot layout
+ * at create (kwk_layout_epoch): after a kwk_relayout they belong to other objects, so kwk_emit and
+ * kwk_emit_step return KWK_ESTATE ("create an emitter for the new layout (kwk_emitter_create) and
+ * set its words and columns") instead of emitting from them.  The old emitter's words stay readable
+ * (kwk_emit_get_words / _get_fin_words carry the guard bits earlier emissions set): the host
+ * permutes them by the relayout's runs for the new emitter.  A device-side move of the columns is
+ * not provided. */
 kwk_status kwk_emitter_create(kwk_engine* eng, uint32_t capacity, const kwk_emit_program* prog, kwk_emitter** out);
 kwk_status kwk_emitter_destroy(kwk_emitter* em);
 kwk_status kwk_emit_set_words(kwk_emitter* em, uint32_t first, uint32_t n, const uint64_t* words);

@@ -795,6 +795,68 @@ kwk_status kwk_aggregate(kwk_engine* eng, uint32_t n_masks, const uint32_t* mask
  * (synchronises): n doubles */
 kwk_status kwk_aggregate_read(kwk_engine* eng, double* host_out, uint32_t n);
 
+/* ------------------------------------------------------------------ slot layout */
+/* kwk_relayout moves whole runs of slots on the engine's stream and replaces the node layout of
+ * kwk_usage_config, so a running engine follows a live cluster: a node is added (its range is
+ * appended), a full node range gets room (every later slot shifts), a scale-down is compacted (the
+ * sweeps then stream n_active ids, not the old count).  Nothing crosses PCIe but the run lists and
+ * the new node_ptr; no integrator is lost.  Choosing when to call it is the host's policy
+ * (kwok_amd/host/layout.py plan_layout is the mechanism).
+ *
+ * Moved slots: destination slot dst + i of a run holds afterwards everything source slot src + i
+ * held: the state word (in whichever format the engine is in; the 1-byte dictionary, the fused
+ * records' epoch and the transition tables are engine-wide and stay), its due column entry,
+ * deletion_s, rec_idx (the value records stay where they are), on a node engine the 32-byte lease
+ * record; of the usage configuration the usage key (4-byte and 1-byte columns), the pointer to a
+ * mixed pod's integrator range (the range itself stays where it lies), the time of the pod's last
+ * evaluation, its unit integrator and kept program values, its last per-pod outputs, and its
+ * creation time of kwk_metrics_inputs.  A run with dst == src moves no bytes where a prefix of such
+ * runs starts the list; a call whose runs are all identities, with n_active and the node count
+ * unchanged, launches nothing.
+ * Fresh slots: a destination slot no run covers reads as one loaded by kwk_load from an all-zero
+ * kwk_hot row — not alive, nothing pending, no record, class 0, deletion unset — with usage key
+ * fresh_usage_key, integrators zero, last evaluation and creation time unset.
+ * Dropped slots: a source slot no run names is gone, as after kwk_delete and a KWK_USAGE_ROW_RESET
+ * row; a dropped mixed pod's integrator range is abandoned (as kwk_usage_set_rows abandons ranges).
+ * Nodes: node_moves does the same for the per-node arrays (usage integrators, last evaluation,
+ * last outputs, creation time, StartedContainersTotal); a node no run names is fresh: zero, unset.
+ * node_ptr replaces the old one; the usage chunks are rebuilt from it, cptr lazily.  A
+ * kwk_tick_bind binding is dropped (kwk_tick* answer as before any bind: bind again with the new
+ * node_ptr).  On an engine without kwk_usage_config, n_nodes / n_node_moves are 0 and node_ptr NULL.
+ * With a usage configuration the engine's objects are its pods: n_active must have been
+ * node_ptr[n_nodes] before the call too (KWK_ESTATE otherwise).
+ * Checked on the host before anything changes (KWK_EINVAL naming the run or node): a run outside
+ * [0, old n_active) or [0, to->n_active); runs not sorted by dst, or overlapping in dst or in src;
+ * node_ptr not starting at 0 or decreasing; node_ptr[n_nodes] != n_active; fresh_usage_key with a
+ * value id outside the tables or a 0 container count (a mixed key); n_active > capacity (capacity
+ * does not grow).  A HIP error after the checks (a failed allocation or copy, KWK_EHIP) can leave
+ * the columns and the host mirrors partly in the new layout: the engine is then undefined until it
+ * is loaded and configured again (as kwk_usage_set_rows says of its own KWK_EHIP).
+ * The call is ordered on the engine's stream; it synchronises only where a column, the scratch
+ * buffer or a staging buffer has to grow (or a buffer is released).  The hand-back ring is
+ * emptied: kwk_fired_fetch / kwk_ring_view of an earlier step return KWK_ESTATE, and the last
+ * step's list is gone.  Device pointers handed out earlier (kwk_device_ptrs, kwk_fired_device,
+ * kwk_metrics_series_device, kwk_metrics_eval_device) are invalid after the call.  The cumulative
+ * statistics stay.  The Philox counter is the global slot: a moved object draws from its new slot's
+ * stream afterwards, exactly as an engine loaded in the new layout would.
+ * Libraries with per-slot state of their own do not follow by themselves, and refuse to serve an
+ * older layout (KWK_ESTATE naming the call to make): a patch emitter is created again and given the
+ * permuted words and columns (kwok_emit.h), an exposition writer is created again for the new node
+ * count and given the rows of the new layout and a full commit (kwok_expo.h).  kwk_layout_epoch is
+ * what they compare.
+ * Out of scope: growing capacity; a device-side move of the emitter's columns; an incremental
+ * exposition relayout; moving objects between engines or GPUs. */
+typedef struct { uint32_t dst, src, n; } kwk_move;   /* [src, src+n) -> [dst, dst+n) */
+typedef struct {
+  uint32_t n_active;                       /* slots after the call, <= capacity */
+  uint32_t n_moves;      const kwk_move* moves;       /* slot runs: sorted by dst, disjoint in dst and in src */
+  uint32_t n_nodes;      const uint32_t* node_ptr;    /* new layout (n_nodes + 1); NULL / 0 on an engine without kwk_usage_config */
+  uint32_t n_node_moves; const kwk_move* node_moves;  /* node-index runs, same rules */
+  uint32_t fresh_usage_key;                /* the uniform key of slots no run covers */
+} kwk_layout;
+kwk_status kwk_relayout(kwk_engine* eng, const kwk_layout* to);
+uint64_t kwk_layout_epoch(const kwk_engine* eng);     /* 0 at create, +1 per successful kwk_relayout */
+
 /* raw device pointers for in-process consumers (RCCL aggregates, profiling): state = the
  * state stream (kwk_step_stats.state_bytes per slot); fired / wave_counts = the sweep's
  * internal fired segments and per-segment counts (valid after kwk_fired_read) */

@@ -71,7 +71,13 @@ kwk_status kwk_expo_set_labels(kwk_expo* ex, uint32_t group, uint32_t first, uin
 /* stable-sorts every node's rows of each group by key (bytewise; ties keep row order: the order of
  * exposition()'s sorted(series, key=label values)) and uploads blocks, keys and permutations, packed
  * (it compacts what kwk_expo_commit_rows appended).  Re-reads the engine's node_ptr / container
- * layout; synchronises the stream; clears the dirty rows. */
+ * layout; synchronises the stream; clears the dirty rows.
+ * A writer is for one slot layout (the engine's kwk_layout_epoch at kwk_expo_create): its node
+ * count is fixed at create and its rows are placed by that layout's node_ptr.  After a kwk_relayout
+ * (nodes added or removed, series moved) kwk_expo_set_labels, kwk_expo_commit, kwk_expo_commit_rows
+ * and kwk_expo_scrape return KWK_ESTATE ("create a writer for the new layout (kwk_expo_create), set
+ * the rows of the new layout and kwk_expo_commit").  There is no incremental relayout: a relayout
+ * costs the exposition a new writer, every row set and a full commit. */
 kwk_status kwk_expo_commit(kwk_expo* ex);
 /* The commit of a live cluster: brings only the rows given to kwk_expo_set_labels since the last
  * commit (of either kind) up to date, at a cost that follows those rows.  After KWK_OK every later

@@ -14,7 +14,7 @@ SRC = [os.path.join(PKG, "csrc", "engine.hip")]
 ERR_HDR = os.path.join(PKG, "csrc", "errscope.hpp")  # the error scope every library includes
 MEM_HDR = os.path.join(PKG, "csrc", "devmem.hpp")    # the owners of device memory and events of the HIP libraries
 HDR = [os.path.join(ROOT, "include", "kwok_engine.h"), os.path.join(PKG, "csrc", "id8_compose.hpp"),
-       os.path.join(PKG, "csrc", "usage_rows.hpp"), ERR_HDR, MEM_HDR]
+       os.path.join(PKG, "csrc", "usage_rows.hpp"), os.path.join(PKG, "csrc", "relayout.hpp"), ERR_HDR, MEM_HDR]
 OUT = os.path.join(PKG, "lib", "libkwok_engine.so")
 DOM_HDR = os.path.join(PKG, "csrc", "json_dom.hpp")
 ENC_SRC = [os.path.join(PKG, "csrc", "encoder.cpp")]

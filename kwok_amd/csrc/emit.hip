@@ -1610,6 +1610,7 @@ __global__ __launch_bounds__(kBlock) void emit_evt_write_kernel(EmitArgs a, EvtA
 struct kwk_emitter {
   std::string err;
   kwk_engine* eng = nullptr;  // must outlive the emitter
+  uint64_t layout_epoch = 0;  // the engine's kwk_layout_epoch at create: the slot layout the per-slot words and columns are for
   hipStream_t stream = nullptr;  // the engine's stream as of the current call (kwk_stream at every entry:
                                  // KWK_TUNE_STREAM_PRIORITY re-creates it, so it is never cached across calls)
   int device = 0;
@@ -1891,6 +1892,7 @@ kwk_status kwk_emitter_create(kwk_engine* eng, uint32_t capacity, const kwk_emit
   em->eng = eng;
   em->stream = static_cast<hipStream_t>(s);
   em->capacity = capacity;
+  em->layout_epoch = kwk_layout_epoch(eng);
   hipError_t e = hipStreamGetDevice(em->stream, &em->device);
   if (e != hipSuccess) {
     delete em;
@@ -2199,9 +2201,20 @@ kwk_status kwk_emit_select(kwk_emitter* em, uint32_t back) {
   return KWK_OK;
 }
 
+// the words, order words, value columns and event rows are per slot: after a kwk_relayout they
+// belong to other objects, so nothing is emitted from them (reading them back stays allowed: the
+// host permutes them for the new emitter)
+static kwk_status same_layout_epoch(const kwk_emitter* em) {
+  if (kwk_layout_epoch(em->eng) == em->layout_epoch) return KWK_OK;
+  return fail(KWK_ESTATE, "the engine's slot layout changed (kwk_relayout, epoch " + std::to_string(kwk_layout_epoch(em->eng)) +
+                              ", emitter created at " + std::to_string(em->layout_epoch) +
+                              "): create an emitter for the new layout (kwk_emitter_create) and set its words and columns");
+}
+
 kwk_status kwk_emit(kwk_emitter* em, int64_t now_ns, uint32_t source) {
   ErrScope es_(em ? &em->err : nullptr);
   if (!em) return fail(KWK_EINVAL, "null emitter");
+  if (kwk_status st = same_layout_epoch(em)) return st;
   EmitArgs a{};
   const uint32_t from = source & 0xFFu;
   if (from != KWK_EMIT_FROM_RECORDS && from != KWK_EMIT_FROM_PACKED)
@@ -2219,6 +2232,7 @@ kwk_status kwk_emit(kwk_emitter* em, int64_t now_ns, uint32_t source) {
 kwk_status kwk_emit_step(kwk_emitter* em, uint64_t step, int64_t now_ns) {
   ErrScope es_(em ? &em->err : nullptr);
   if (!em) return fail(KWK_EINVAL, "null emitter");
+  if (kwk_status st = same_layout_epoch(em)) return st;
   kwk_fired_view v;
   if (kwk_ring_view(em->eng, step, &v) != KWK_OK)
     return fail(KWK_ESTATE, std::string("kwk_ring_view: ") + kwk_last_error(em->eng));

@@ -37,6 +37,7 @@
 #include "errscope.hpp"
 #include "devmem.hpp"
 #include "usage_rows.hpp"
+#include "relayout.hpp"
 
 namespace {
 
@@ -5127,6 +5128,16 @@ struct kwk_engine {
   DevBuf<unsigned long long> d_lease_stats;
   uint64_t lease_steps = 0;
 
+  // kwk_relayout: the layout's number, the run lists on the device, one scratch buffer sized to the
+  // widest column a call gathers (kept), and a pinned staging buffer for the lists and the node
+  // layout (rewritten once its last copy is done)
+  uint64_t layout_epoch = 0;
+  DevBuf<kwk_move> d_moves, d_node_moves;
+  DevBuf<void> d_scratch;
+  HostBuf<char> relayout_stage;
+  Event relayout_copied;
+  bool relayout_pending = false;
+
   std::vector<Event> events;
   std::string err;            // message of the last failing call on this engine (kwk_last_error)
 };
@@ -8207,7 +8218,7 @@ kwk_status kwk_lease_config(kwk_engine* e, const kwk_lease_params* cfg) {
   if (!e->d_lease) {
     DevBuf<kwk_lease> d_lease;  // the engine's at the end: the test above looks at it
     HIP_TRY(d_lease.alloc(e->capacity));
-    HIP_TRY(e->d_lease_op.alloc(e->capacity));
+    HIP_TRY(e->d_lease_op.alloc((size_t)e->capacity + 16));  // (kwk_relayout reads whole 16-byte chunks)
     HIP_TRY(e->d_lease_ops.alloc(e->capacity));
     HIP_TRY(e->d_lease_nops.alloc(2));
     HIP_TRY(e->d_lease_stats.alloc(5));
@@ -8494,5 +8505,316 @@ kwk_status kwk_event_elapsed(kwk_engine* e, uint32_t a, uint32_t b, float* ms) {
 
 uint32_t kwk_abi_version(void) { return KWK_ABI_VERSION; }
 uint32_t kwk_tile_objects(void) { return (uint32_t)(kBlock * kMinObjPerThread); }
+
+
+// ------------------------------------------------------------------ slot layout (kwk_relayout)
+// (the kernel and its launches are named after every other kernel of this file: the order in which
+// the host code first names kernels decides their order in the code object)
+}  // extern "C"
+
+namespace {
+
+constexpr uint32_t kGatherChunks = 4;     // 16-byte destination chunks per lane
+constexpr uint32_t kGatherSpan = kBlock * kGatherChunks;  // chunks per workgroup: 16 KiB of the new column
+constexpr uint32_t kGatherLdsRuns = 1024;  // runs staged in LDS (12 KiB); a span that meets more reads them in place
+
+struct GatherArgs {
+  const unsigned char* src;   // the old column
+  unsigned char* dst;         // where chunk `chunk0` of the new column goes
+  const kwk_move* runs;
+  uint32_t n_runs;
+  uint64_t chunk0, chunk_end; // the chunks gathered (an identity prefix is left where it is)
+  relayout::Fill fill;
+};
+
+// One column of EB-byte elements gathered out of place (relayout.hpp).  Each workgroup owns
+// kGatherSpan consecutive destination chunks; it looks the span's first and last slot up in the
+// dst-sorted run list once, stages that slice in LDS, and every lane assembles and stores whole
+// 16-byte chunks.  A lane past the end works on the last chunk again and keeps its store to
+// itself: no divergent exit before the barriers.
+template <uint32_t EB>
+__global__ __launch_bounds__(kBlock) void relayout_gather_kernel(GatherArgs a) {
+  __shared__ kwk_move s_runs[kGatherLdsRuns];
+  __shared__ uint32_t s_r0, s_cnt;
+  const uint64_t base = a.chunk0 + (uint64_t)blockIdx.x * kGatherSpan;
+  if (threadIdx.x == 0) {
+    const uint64_t last = base + kGatherSpan < a.chunk_end ? base + kGatherSpan : a.chunk_end;  // one past the span's last chunk
+    const uint32_t slot_lo = (uint32_t)(base * 16u / EB);
+    const uint64_t slot_hi = (last * 16u + EB - 1) / EB;
+    const uint32_t r0 = relayout::find_run(a.runs, a.n_runs, slot_lo);
+    const uint32_t r1 = slot_hi > 0xFFFFFFFFull ? a.n_runs : relayout::first_run_from(a.runs, a.n_runs, (uint32_t)slot_hi);
+    s_r0 = r0;
+    s_cnt = r1 > r0 ? r1 - r0 : 0u;
+  }
+  __syncthreads();
+  const uint32_t r0 = s_r0, cnt = s_cnt;
+  const bool staged = cnt <= kGatherLdsRuns;
+  if (staged)
+    for (uint32_t j = threadIdx.x; j < cnt; j += kBlock) s_runs[j] = a.runs[r0 + j];
+  __syncthreads();
+  const kwk_move* runs = staged ? s_runs : a.runs + r0;
+#pragma unroll
+  for (uint32_t j = 0; j < kGatherChunks; ++j) {
+    const uint64_t c = base + (uint64_t)j * kBlock + threadIdx.x;
+    const bool in = c < a.chunk_end;
+    const uint64_t cc = in ? c : a.chunk_end - 1;
+    const relayout::V16 v = relayout::gather_chunk<EB>(a.src, cc, runs, cnt, a.fill);
+    if (in) *reinterpret_cast<relayout::V16*>(a.dst + 16u * (cc - a.chunk0)) = v;
+  }
+}
+
+const void* gather_pick(uint32_t eb) {
+  switch (eb) {
+    case 1: return (const void*)relayout_gather_kernel<1>;
+    case 2: return (const void*)relayout_gather_kernel<2>;
+    case 4: return (const void*)relayout_gather_kernel<4>;
+    case 8: return (const void*)relayout_gather_kernel<8>;
+    case 16: return (const void*)relayout_gather_kernel<16>;
+    default: return (const void*)relayout_gather_kernel<32>;
+  }
+}
+
+// what one kwk_relayout call moves a family of columns by (the slots' runs or the nodes')
+struct MovePlan {
+  const kwk_move* d_runs = nullptr;  // on the device
+  uint32_t n_runs = 0, n_old = 0, n_new = 0;
+  uint32_t keep = 0;                 // slots [0, keep) stay where they are (relayout::identity_prefix)
+};
+
+// One column: `buf` holds n_old elements of eb bytes and n_new afterwards, `room` elements are
+// allocated (0: buf.size() counts them).  Where the allocation has room for the new column's whole
+// chunks, the part past the identity prefix is gathered into the scratch buffer and copied back;
+// else into a new allocation that takes the column's place (releasing the old block waits for the
+// device).  Slots [n_new, n_old) of a column that shrinks are zeroed with zero_tail (the state
+// column: the sweeps read whole tiles).
+template <class T>
+kwk_status move_column(kwk_engine* e, DevBuf<T>& buf, size_t room_bytes, uint32_t eb, const MovePlan& mp, const void* fill_elem,
+                       bool zero_tail = false) {
+  const uint64_t chunk_end = relayout::chunks_of(mp.n_new, eb);
+  const uint64_t chunk0 = std::min((uint64_t)mp.keep * eb / 16u, chunk_end);
+  GatherArgs a{reinterpret_cast<const unsigned char*>(buf.get()), nullptr, mp.d_runs, mp.n_runs, chunk0, chunk_end,
+               relayout::fill_of(fill_elem, eb)};
+  const bool in_place = (size_t)eb * mp.n_new <= room_bytes;
+  DevBuf<T> grown;
+  if (in_place) {
+    a.dst = reinterpret_cast<unsigned char*>(e->d_scratch.get());
+  } else {  // (with room for whole chunks and some growth)
+    constexpr size_t el = sizeof(typename std::conditional<std::is_void<T>::value, char, T>::type);
+    const size_t bytes = 16u * (size_t)chunk_end;
+    HIP_TRY(grown.alloc((bytes + bytes / 4 + 64u) / el));
+    if (chunk0) HIP_TRY(hipMemcpyAsync(grown.get(), buf.get(), 16u * (size_t)chunk0, hipMemcpyDeviceToDevice, e->stream));
+    a.dst = reinterpret_cast<unsigned char*>(grown.get()) + 16u * (size_t)chunk0;
+  }
+  if (chunk_end > chunk0) {
+    const uint32_t grid = (uint32_t)((chunk_end - chunk0 + kGatherSpan - 1) / kGatherSpan);
+    void* args[] = {&a};
+    HIP_TRY(hipLaunchKernel(gather_pick(eb), dim3(grid), dim3(kBlock), args, 0, e->stream));
+    if (in_place) {  // (the last chunk's padding too, where the allocation has room for it)
+      const size_t from = 16u * (size_t)chunk0, to = std::min(16u * (size_t)chunk_end, room_bytes);
+      HIP_TRY(hipMemcpyAsync(reinterpret_cast<unsigned char*>(buf.get()) + from, e->d_scratch.get(), to - from,
+                             hipMemcpyDeviceToDevice, e->stream));
+    }
+  }
+  if (!in_place) buf = std::move(grown);
+  if (zero_tail && mp.n_old > mp.n_new) {
+    const size_t from = (size_t)eb * mp.n_new, to = (size_t)eb * mp.n_old;
+    if (to > from) HIP_TRY(hipMemsetAsync(reinterpret_cast<unsigned char*>(buf.get()) + from, 0, to - from, e->stream));
+  }
+  return KWK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+uint64_t kwk_layout_epoch(const kwk_engine* e) { return e ? e->layout_epoch : 0; }
+
+kwk_status kwk_relayout(kwk_engine* e, const kwk_layout* to) {
+  ErrScope es_(e ? &e->err : nullptr);
+  if (!e || !to) return fail(KWK_EINVAL, "null argument");
+  const bool usage = e->d_node_ptr != nullptr;
+  const uint32_t n_old = e->n_active, n_new = to->n_active;
+  // ---- every check first: nothing has changed when the call refuses
+  {
+    const relayout::Verdict v = relayout::check_layout(*to, n_old, e->capacity, usage, e->n_nodes, e->ub.n_cpu + e->ub.n_cpu_progs,
+                                                       e->ub.n_mem + e->ub.n_mem_progs);
+    if (v.status) return fail(v.status, v.msg);
+  }
+  if (usage) {
+    if (e->n_usage_pods != n_old)
+      return fail(KWK_ESTATE, "the usage configuration covers " + std::to_string(e->n_usage_pods) + " pods, the engine has " +
+                                  std::to_string(n_old) + " slots: kwk_relayout moves both together");
+    if (e->has_mixed_keys && !e->d_mixed) return fail(KWK_ESTATE, "kwk_usage_mixed must be called first");
+  }
+  if (kwk_status st = set_dev(e)) return st;
+  const uint32_t nn_old = e->n_nodes, nn_new = usage ? to->n_nodes : 0u;
+  const uint32_t keep = relayout::identity_prefix(to->moves, to->n_moves, n_new);
+  const uint32_t nkeep = usage ? relayout::identity_prefix(to->node_moves, to->n_node_moves, nn_new) : 0u;
+  const bool same_nodes = !usage || (nn_new == nn_old && nkeep == nn_new &&
+                                     memcmp(e->h_node_ptr.data(), to->node_ptr, 4 * ((size_t)nn_new + 1)) == 0);
+  // what the call invalidates whatever it moves: the hand-back ring, the last list, a tick binding
+  auto new_epoch = [&]() {
+    for (kwk_engine::HbSlot& h : e->hb) h.valid = false;
+    e->compacted = false;
+    e->last_blocks = 0;
+    {
+      std::lock_guard<std::mutex> lk(g_live_mu);
+      kwk_engine* tn = const_cast<kwk_engine*>(e->tick_nodes);
+      if (tn && g_live.count(tn) && tn->tick_pods == e) tn->tick_pods = nullptr;
+      e->tick_nodes = nullptr;
+      e->tick_n_nodes = 0;
+      if (e->tick_pods && g_live.count(e->tick_pods) && e->tick_pods->tick_nodes == e) {  // a node engine's pods
+        e->tick_pods->tick_nodes = nullptr;
+        e->tick_pods->tick_n_nodes = 0;
+      }
+      e->tick_pods = nullptr;
+    }
+    ++e->layout_epoch;
+  };
+  if (keep == n_new && n_new == n_old && same_nodes) {  // every run an identity, the same layout: no launch
+    new_epoch();
+    return KWK_OK;
+  }
+  // fresh slots hold the zero row's word: in the 1-byte format it joins the dictionary as an upsert's does
+  if (keep < n_new)
+    if (kwk_status st = admit_rows(e, std::vector<uint2>(1, make_uint2(0u, 0u)))) return st;
+  // ---- the usage book: mirrors, counts, the 1-byte dictionary
+  usage_rows::Effects fx;
+  uint32_t fresh_k8 = 0;
+  bool kv_dirty = false;
+  if (usage) {
+    const std::string bad = e->ub.relayout(to->moves, to->n_moves, n_new, to->fresh_usage_key, fx, &fresh_k8);
+    if (!bad.empty()) return fail(KWK_EINVAL, bad);
+    e->has_mixed_keys = e->ub.has_mixed();
+    e->rows_tmp.clear();
+  }
+  // ---- the lists, the node layout and its chunks through the pinned staging buffer
+  std::vector<uint4> chunks;
+  if (usage) {
+    const uint32_t chunk_pods = kUChunkRows * kURow - 8u;  // (as kwk_usage_config_dyn)
+    for (uint32_t n = 0; n < nn_new;) {
+      const uint32_t c0 = to->node_ptr[n];
+      uint32_t nb = n + 1;
+      while (nb < nn_new && nb - n < kUChunkNodes && to->node_ptr[nb + 1] - c0 <= chunk_pods) ++nb;
+      chunks.push_back(make_uint4(c0, to->node_ptr[nb], n, nb));
+      n = nb;
+    }
+  }
+  constexpr size_t kv_bytes = sizeof(double2) * kUKeyDict;
+  const size_t mv_bytes = sizeof(kwk_move) * (size_t)to->n_moves, nmv_bytes = sizeof(kwk_move) * (size_t)to->n_node_moves;
+  const size_t ptr_bytes = usage ? 4 * ((size_t)nn_new + 1) : 0, ch_bytes = sizeof(uint4) * chunks.size();
+  auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
+  const size_t o_mv = kv_bytes, o_nmv = o_mv + up16(mv_bytes), o_ptr = o_nmv + up16(nmv_bytes), o_ch = o_ptr + up16(ptr_bytes);
+  const size_t stage_need = o_ch + up16(ch_bytes);
+  if (e->relayout_pending) {
+    HIP_TRY(hipEventSynchronize(e->relayout_copied));
+    e->relayout_pending = false;
+  }
+  if (e->relayout_stage.size() < stage_need) HIP_TRY(e->relayout_stage.alloc(std::max(2 * stage_need, (size_t)65536)));
+  HIP_TRY(e->relayout_copied.create(hipEventDisableTiming));
+  if (e->d_moves.size() < to->n_moves + 1u) HIP_TRY(e->d_moves.alloc(std::max((size_t)2 * to->n_moves, (size_t)256)));
+  if (e->d_node_moves.size() < to->n_node_moves + 1u)
+    HIP_TRY(e->d_node_moves.alloc(std::max((size_t)2 * to->n_node_moves, (size_t)256)));
+  char* const sg = e->relayout_stage.get();
+  if (mv_bytes) {
+    memcpy(sg + o_mv, to->moves, mv_bytes);
+    HIP_TRY(hipMemcpyAsync(e->d_moves, sg + o_mv, mv_bytes, hipMemcpyHostToDevice, e->stream));
+  }
+  if (nmv_bytes) {
+    memcpy(sg + o_nmv, to->node_moves, nmv_bytes);
+    HIP_TRY(hipMemcpyAsync(e->d_node_moves, sg + o_nmv, nmv_bytes, hipMemcpyHostToDevice, e->stream));
+  }
+  // the scratch buffer: the widest column this call gathers, sized once
+  {
+    uint32_t widest = (uint32_t)word_bytes(e->fmt) < 8u ? 8u : (uint32_t)word_bytes(e->fmt);  // state, due / deletion
+    if (e->lease_on) widest = 32u;
+    if (usage && e->d_pod_out) widest = 32u;
+    const size_t need = std::max(16u * (size_t)relayout::chunks_of(n_new, widest),
+                                 usage ? 16u * (size_t)relayout::chunks_of(nn_new, 32u) : (size_t)0) + 16u;
+    if (e->d_scratch.size() < need) HIP_TRY(e->d_scratch.alloc(need));
+  }
+  // ---- the engine's columns
+  MovePlan mp{e->d_moves, to->n_moves, n_old, n_new, keep};
+  const uint64_t zero8 = 0;
+  const int64_t unset = INT64_MIN;
+  const unsigned char zero32[32] = {};
+  const uint32_t wb = (uint32_t)word_bytes(e->fmt);
+  // (a fused record of the zero row, due 0: its D says "in the column", as kwk_load's fold leaves it)
+  const uint2 st_fill = e->fmt.dw ? dw_put(make_uint2(0u, 0u), dw_enc(0, e->fmt.epoch)) : make_uint2(0u, 0u);
+  if (kwk_status st = move_column(e, e->d_st, e->d_st.size(), wb, mp, e->fmt.dw ? (const void*)&st_fill : (const void*)zero32, true))
+    return st;
+  if (kwk_status st = move_column(e, e->d_due, 8 * e->d_due.size(), 8, mp, &zero8)) return st;
+  if (kwk_status st = move_column(e, e->d_del, 8 * e->d_del.size(), 8, mp, &unset)) return st;
+  if (kwk_status st = move_column(e, e->d_rec, 4 * e->d_rec.size(), 4, mp, &zero8)) return st;
+  if (e->d_lease) {
+    if (kwk_status st = move_column(e, e->d_lease, sizeof(kwk_lease) * e->d_lease.size(), 32, mp, zero32)) return st;
+    if (kwk_status st = move_column(e, e->d_lease_op, e->d_lease_op.size(), 1, mp, zero32)) return st;
+  }
+  e->n_active = n_new;
+  if (usage) {
+    // ---- the usage columns
+    const uint32_t fkey = to->fresh_usage_key;
+    if (kwk_status st = move_column(e, e->d_ukey, 4 * e->d_ukey.size(), 4, mp, &fkey)) return st;
+    if (e->d_mixed)
+      if (kwk_status st = move_column(e, e->d_mbase, 4 * e->d_mbase.size(), 4, mp, &zero8)) return st;
+    if (e->d_pod_out) {
+      if (kwk_status st = move_column(e, e->d_pod_out, 8 * e->d_pod_out.size(), 32, mp, zero32)) return st;
+      if (kwk_status st = move_column(e, e->d_pod_cum, 8 * e->d_pod_cum.size(), 16, mp, zero32)) return st;
+      if (kwk_status st = move_column(e, e->d_pod_last, 8 * e->d_pod_last.size(), 8, mp, &unset)) return st;
+      if (e->d_unit_val)
+        if (kwk_status st = move_column(e, e->d_unit_val, 8 * e->d_unit_val.size(), 16, mp, zero32)) return st;
+    }
+    const bool inputs = e->d_pod_created && e->inputs_pods == n_old && e->inputs_nodes == nn_old;
+    if (inputs) {
+      if (kwk_status st = move_column(e, e->d_pod_created, 8 * e->d_pod_created.size(), 8, mp, &unset)) return st;
+    } else {
+      e->d_pod_created.reset(), e->d_node_created.reset(), e->d_node_started.reset();  // (inputs of another configuration)
+      e->inputs_pods = e->inputs_nodes = 0;
+    }
+    // the 1-byte key column: moved as it is (the dictionary keeps its entries' numbers), ended, or
+    // built anew where the keys left allow one again
+    const bool had8 = e->d_ukey8 != nullptr && !fx.key8_dropped && e->ub.key8;
+    if (had8) {
+      const uint8_t f8 = (uint8_t)fresh_k8;
+      if (kwk_status st = move_column(e, e->d_ukey8, e->d_ukey8.size(), 1, mp, &f8)) return st;
+    }
+    if (kwk_status st = refresh_fast_tables(e, fx, false, &kv_dirty)) return st;
+    if (kv_dirty && e->d_kv) {
+      memcpy(sg, e->h_kv.data(), kv_bytes);
+      HIP_TRY(hipMemcpyAsync(e->d_kv, sg, kv_bytes, hipMemcpyHostToDevice, e->stream));
+    }
+    // ---- the per-node arrays
+    MovePlan np{e->d_node_moves, to->n_node_moves, nn_old, nn_new, nkeep};
+    if (kwk_status st = move_column(e, e->d_node_cum, 8 * e->d_node_cum.size(), 16, np, zero32)) return st;
+    if (kwk_status st = move_column(e, e->d_node_last, 8 * e->d_node_last.size(), 8, np, &unset)) return st;
+    if (kwk_status st = move_column(e, e->d_node_out, 8 * e->d_node_out.size(), 32, np, zero32)) return st;
+    if (inputs) {
+      if (kwk_status st = move_column(e, e->d_node_created, 8 * e->d_node_created.size(), 8, np, &unset)) return st;
+      if (kwk_status st = move_column(e, e->d_node_started, 8 * e->d_node_started.size(), 8, np, &zero8)) return st;
+      e->inputs_pods = n_new, e->inputs_nodes = nn_new;
+    }
+    // ---- the node layout and what is derived from it
+    if (e->d_node_ptr.size() < (size_t)nn_new + 1) HIP_TRY(e->d_node_ptr.alloc((size_t)nn_new + 1 + nn_new / 4));
+    memcpy(sg + o_ptr, to->node_ptr, ptr_bytes);
+    HIP_TRY(hipMemcpyAsync(e->d_node_ptr, sg + o_ptr, ptr_bytes, hipMemcpyHostToDevice, e->stream));
+    if (e->d_uchunk.size() < chunks.size() + 1) HIP_TRY(e->d_uchunk.alloc(chunks.size() + 1 + chunks.size() / 4));
+    if (ch_bytes) {
+      memcpy(sg + o_ch, chunks.data(), ch_bytes);
+      HIP_TRY(hipMemcpyAsync(e->d_uchunk, sg + o_ch, ch_bytes, hipMemcpyHostToDevice, e->stream));
+    }
+    e->n_uchunks = (uint32_t)chunks.size();
+    const uint32_t ublocks = ((uint32_t)chunks.size() + kWavesPerBlock - 1) / kWavesPerBlock;
+    if (e->d_usage_part.size() < 2 * ((size_t)ublocks + 1)) HIP_TRY(e->d_usage_part.alloc(2 * ((size_t)ublocks + 1)));
+    e->n_nodes = nn_new;
+    e->n_usage_pods = n_new;
+    e->h_node_ptr.assign(to->node_ptr, to->node_ptr + nn_new + 1);
+    e->h_cptr.clear();
+    e->d_cptr.reset();  // rebuilt by the next reader (ensure_cptr)
+  }
+  HIP_TRY(hipEventRecord(e->relayout_copied, e->stream));
+  e->relayout_pending = true;
+  new_epoch();
+  return KWK_OK;
+}
 
 }  // extern "C"

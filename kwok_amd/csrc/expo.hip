@@ -536,6 +536,7 @@ inline uint64_t up8(uint64_t x) { return (x + 7ull) & ~7ull; }
 struct kwk_expo {
   std::string err;
   kwk_engine* eng = nullptr;  // must outlive the writer
+  uint64_t layout_epoch = 0;  // the engine's kwk_layout_epoch at create: the slot and node layout the writer is for
   hipStream_t stream = nullptr;  // the engine's stream as of the current call (it may be re-created)
   int device = 0;
   uint32_t n_nodes = 0, n_pods = 0, n_cont = 0, width = 0;
@@ -746,6 +747,7 @@ kwk_status create(kwk_engine* pods, uint32_t n_nodes, const kwk_expo_program* pr
   ex->eng = pods;
   ex->stream = static_cast<hipStream_t>(s);
   ex->n_nodes = n_nodes;
+  ex->layout_epoch = kwk_layout_epoch(pods);
   ex->fam = std::move(fam);
   ex->hist = std::move(hist);
   ex->max_lines = max_lines;
@@ -804,11 +806,23 @@ kwk_status kwk_expo_destroy(kwk_expo* ex) {
   return KWK_OK;
 }
 
+// A writer is for one slot layout: its node count is fixed at kwk_expo_create and its rows, arenas,
+// permutations and pod_of are placed by that layout's node_ptr.  After a kwk_relayout (nodes added
+// or removed, series moved) every call that places or reads rows refuses: a new writer is created
+// for the new layout.  No incremental relayout.
+static kwk_status same_layout_epoch(const kwk_expo* ex) {
+  if (kwk_layout_epoch(ex->eng) == ex->layout_epoch) return KWK_OK;
+  return fail(KWK_ESTATE, "the engine's slot layout changed (kwk_relayout, epoch " + std::to_string(kwk_layout_epoch(ex->eng)) +
+                              ", writer created at " + std::to_string(ex->layout_epoch) +
+                              "): create a writer for the new layout (kwk_expo_create), set the rows of the new layout and kwk_expo_commit");
+}
+
 kwk_status kwk_expo_set_labels(kwk_expo* ex, uint32_t group, uint32_t first, uint32_t n, const uint32_t* block_offsets,
                                const char* blocks, const uint32_t* key_offsets, const char* keys) {
   ErrScope es_(ex ? &ex->err : nullptr);
   if (!ex || (n && (!block_offsets || !key_offsets))) return fail(KWK_EINVAL, "null argument");
   if (group >= ex->groups.size()) return fail(KWK_EINVAL, "label group out of range");
+  if (kwk_status st = same_layout_epoch(ex)) return st;
   Group& g = ex->groups[group];
   if ((uint64_t)first + n > g.blocks.size()) return fail(KWK_EINVAL, "rows beyond the group's objects");
   for (uint32_t i = 0; i < n; ++i) {
@@ -832,6 +846,7 @@ kwk_status kwk_expo_set_labels(kwk_expo* ex, uint32_t group, uint32_t first, uin
 kwk_status kwk_expo_commit(kwk_expo* ex) {
   ErrScope es_(ex ? &ex->err : nullptr);
   if (!ex) return fail(KWK_EINVAL, "null writer");
+  if (kwk_status st = same_layout_epoch(ex)) return st;
   if (kwk_status st = bind(ex)) return st;
   if (kwk_status st = refresh_layout(ex)) return st;
   HIP_TRY(hipStreamSynchronize(ex->stream));
@@ -879,6 +894,7 @@ kwk_status kwk_expo_commit_rows(kwk_expo* ex) {
   ErrScope es_(ex ? &ex->err : nullptr);
   if (!ex) return fail(KWK_EINVAL, "null writer");
   if (!ex->full) return fail(KWK_ESTATE, "kwk_expo_commit must come first: kwk_expo_commit_rows updates a full commit's layout");
+  if (kwk_status st = same_layout_epoch(ex)) return st;
   if (kwk_status st = bind(ex)) return st;
   // the engine's layout is the one the arenas and permutations were laid out for: its two totals, read on a
   // stream of this writer's own (the engine's stream is not waited for)
@@ -1108,6 +1124,7 @@ kwk_status kwk_expo_scrape(kwk_expo* ex, int64_t now_ns, uint32_t node_first, ui
   ErrScope es_(ex ? &ex->err : nullptr);
   if (!ex) return fail(KWK_EINVAL, "null writer");
   if (!ex->committed) return fail(KWK_ESTATE, "kwk_expo_commit must come first");
+  if (kwk_status st = same_layout_epoch(ex)) return st;
   if ((uint64_t)node_first + n_nodes > ex->n_nodes) return fail(KWK_EINVAL, "nodes beyond the writer's");
   if (kwk_status st = bind(ex)) return st;
   if (!ex->d_out)

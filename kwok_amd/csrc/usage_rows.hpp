@@ -369,6 +369,75 @@ struct Book {
     if (fx.key8_dropped) fx.kv_set.clear();
     return "";
   }
+
+  // kwk_relayout: the mirrors permuted by the slot runs (checked by relayout::check_moves: sorted
+  // by dst, disjoint, inside the old and the new pods), slots no run covers given fresh_key, pods
+  // no run names released — a dropped mixed pod's range is abandoned.  What is derived stays what
+  // configure() of the final columns derives; the dictionary keeps its entries' numbers (the device's
+  // 1-byte column moves as it is), frees those of keys out of use and gives fresh_key one, or ends
+  // as in apply() when that is a 256th distinct key.  *fresh_k8: fresh_key's entry while the
+  // dictionary lives.  "" or what is wrong with fresh_key; the book is unchanged then.
+  std::string relayout(const kwk_move* moves, uint32_t n_moves, uint32_t n_new, uint32_t fresh_key, Effects& fx,
+                       uint32_t* fresh_k8) {
+    fx = Effects{};
+    if (fresh_k8) *fresh_k8 = 0;
+    if (!(fresh_key >> 28)) return "fresh_usage_key " + std::to_string(fresh_key) + ": a mixed key (0 containers)";
+    if (!key_ids_ok(fresh_key)) return "fresh_usage_key " + std::to_string(fresh_key) + ": value id out of range";
+    const uint32_t n_old = n_pods();
+    // slots [0, keep) stay where they are (a prefix of identity runs without a gap): only what lies
+    // past it is copied and counted, so appending nodes costs the new slots alone.  The sources of
+    // the other runs lie past the prefix too (runs are disjoint in src).
+    uint32_t keep = 0, first = 0;
+    for (; first < n_moves; ++first) {
+      const kwk_move& m = moves[first];
+      if (m.n && (m.dst != keep || m.src != keep)) break;
+      keep += m.n;
+    }
+    const size_t tail_new = (size_t)n_new - keep, tail_old = (size_t)n_old - keep;
+    std::vector<uint32_t> nk(tail_new, fresh_key), nb, nc;
+    if (mixed_tables) nb.assign(tail_new, 0u), nc.assign(tail_new, 0u);
+    std::vector<uint8_t> named(tail_old, 0);
+    uint64_t covered = keep;
+    for (uint32_t i = first; i < n_moves; ++i) {
+      const kwk_move& m = moves[i];
+      if (!m.n) continue;
+      std::copy(ukey.begin() + m.src, ukey.begin() + m.src + m.n, nk.begin() + (m.dst - keep));
+      if (mixed_tables) {
+        std::copy(mbase.begin() + m.src, mbase.begin() + m.src + m.n, nb.begin() + (m.dst - keep));
+        std::copy(mcap.begin() + m.src, mcap.begin() + m.src + m.n, nc.begin() + (m.dst - keep));
+      }
+      std::fill(named.begin() + (m.src - keep), named.begin() + (m.src - keep) + m.n, (uint8_t)1);
+      covered += m.n;
+    }
+    for (size_t q = 0; q < tail_old; ++q)
+      if (!named[q]) release(ukey[keep + q]);
+    const uint64_t fresh = (uint64_t)n_new - covered;
+    if (fresh) {
+      nc_hist[fresh_key >> 28] += fresh;
+      Ref& ref = keys[fresh_key];
+      ref.count += fresh;
+      if (key8 && ref.idx < 0) {
+        if (!dict_free.empty()) {
+          ref.idx = (int32_t)dict_free.back(), dict_free.pop_back();
+          dict[ref.idx] = fresh_key;
+        } else if (dict.size() < kDictMax) {
+          ref.idx = (int32_t)dict.size(), dict.push_back(fresh_key);
+        }
+        if (ref.idx >= 0) fx.kv_set.push_back((uint32_t)ref.idx);
+        else drop_dict(), fx.key8_dropped = true;  // the 256th distinct key
+      }
+      if (key8 && fresh_k8) *fresh_k8 = (uint32_t)ref.idx;
+    }
+    auto retail = [&](std::vector<uint32_t>& col, const std::vector<uint32_t>& tail) {
+      col.resize(keep);
+      col.insert(col.end(), tail.begin(), tail.end());
+    };
+    retail(ukey, nk);
+    if (mixed_tables) retail(mbase, nb), retail(mcap, nc);
+    if (key8 && ukey.empty()) drop_dict(), fx.key8_dropped = true;  // (no pods: no column, as configure())
+    fx.layout_changed = true;  // cptr follows the slots whatever the counts
+    return "";
+  }
 };
 
 }  // namespace usage_rows

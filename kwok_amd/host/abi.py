@@ -184,6 +184,21 @@ class HistogramDesc(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
+class Move(C.Structure):
+    """kwk_move: slots (or node indices) [src, src + n) -> [dst, dst + n)."""
+    _fields_ = [("dst", C.c_uint32), ("src", C.c_uint32), ("n", C.c_uint32)]
+
+
+class Layout(C.Structure):
+    """kwk_layout (kwk_relayout)."""
+    _fields_ = [("n_active", C.c_uint32), ("n_moves", C.c_uint32), ("moves", C.c_void_p),
+                ("n_nodes", C.c_uint32), ("node_ptr", C.c_void_p),
+                ("n_node_moves", C.c_uint32), ("node_moves", C.c_void_p), ("fresh_usage_key", C.c_uint32)]
+
+
+MOVE_DTYPE = np.dtype([("dst", "<u4"), ("src", "<u4"), ("n", "<u4")])  # kwk_move
+
+
 class Backoff(C.Structure):
     """kwk_backoff = wait.Backoff; default = defaultBackoff (controllers/utils.go:133-135)."""
     _fields_ = [("duration_ns", C.c_int64), ("factor", C.c_double), ("jitter", C.c_double), ("cap_ns", C.c_int64)]
@@ -196,6 +211,7 @@ assert C.sizeof(MetricBucket) == 24 and C.sizeof(HistogramDesc) == 16
 assert C.sizeof(Hot) == 16 and C.sizeof(Value) == 16 and C.sizeof(StageDesc) == 96
 assert C.sizeof(Lease) == 32 == LEASE_DTYPE.itemsize and C.sizeof(LeaseParams) == 32
 assert USAGE_ROW_DTYPE.itemsize == 24 and C.sizeof(UsageInfo) == 88
+assert C.sizeof(Move) == 12 == MOVE_DTYPE.itemsize and C.sizeof(Layout) == 56
 assert HOT_DTYPE.itemsize == 16 and VALUE_DTYPE.itemsize == 16 and FIRED_DTYPE.itemsize == 8
 
 # every symbol include/kwok_engine.h declares (checked by the CPU test suite)
@@ -212,6 +228,7 @@ EXPORTS = [
     "kwk_fired_fetch", "kwk_fired_fetch_wait", "kwk_fired_keep",
     "kwk_metrics_eval_device", "kwk_histograms_eval_device", "kwk_metrics_series_device", "kwk_ring_view",
     "kwk_usage_config_dyn", "kwk_usage_set_rows", "kwk_usage_append", "kwk_usage_mixed_append", "kwk_usage_info_get",
+    "kwk_relayout",
 ]
 ABI_VERSION = 3  # KWK_ABI_VERSION of include/kwok_engine.h: the library must match the structs above
 TICK_COMPACT = 1 << 0  # KWK_TICK_COMPACT
@@ -325,6 +342,9 @@ def lib():
     L.kwk_tick.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64, C.c_uint64, C.c_uint32]
     L.kwk_tick_n.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int64, C.c_int64, C.c_uint64, C.c_uint64,
                              C.c_uint32]
+    L.kwk_relayout.argtypes = [C.c_void_p, _p(Layout)]
+    L.kwk_layout_epoch.argtypes = [C.c_void_p]  # (returns the number itself, not a status: not in EXPORTS)
+    L.kwk_layout_epoch.restype = C.c_uint64
     L.kwk_abi_version.restype = C.c_uint32
     L.kwk_tile_objects.restype = C.c_uint32
     for name in EXPORTS:

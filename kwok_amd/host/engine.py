@@ -371,6 +371,34 @@ class Engine:
         self._check(abi.lib().kwk_read(self.h, first, n, abi.ptr(hot), abi.ptr(dels)), "kwk_read")
         return hot, dels
 
+    def relayout(self, moves, n_active: int, node_ptr=None, node_moves=None, fresh_usage_key: int = 0):
+        """kwk_relayout: move the slot runs `moves` (rows of abi.MOVE_DTYPE or (dst, src, n) triples,
+        sorted by dst; layout.plan_layout computes them) on the engine's stream, leaving n_active
+        slots; with a usage configuration also the new node_ptr, the node-index runs and the usage key
+        of fresh slots.  Everything an object or node owns on the device travels with it."""
+        from . import layout
+        mv = layout.as_moves(moves)
+        nm = layout.as_moves(node_moves if node_moves is not None else [])
+        ptr = None if node_ptr is None else np.ascontiguousarray(node_ptr, dtype=np.uint32)
+        lay = abi.Layout(n_active=int(n_active), n_moves=len(mv), moves=abi.ptr(mv) if len(mv) else None,
+                         n_nodes=0 if ptr is None else len(ptr) - 1, node_ptr=abi.ptr(ptr),
+                         n_node_moves=len(nm), node_moves=abi.ptr(nm) if len(nm) else None,
+                         fresh_usage_key=int(fresh_usage_key))
+        self._check(abi.lib().kwk_relayout(self.h, C.byref(lay)), "kwk_relayout")
+        self.n = int(n_active)
+        if ptr is not None:
+            self.n_nodes = len(ptr) - 1
+            if getattr(self, "_uargs", None) is not None:  # usage_config's node_ptr and keys, as the engine holds them now
+                self._uargs[1] = layout.apply_moves(self._uargs[1], mv, int(n_active), np.uint32(fresh_usage_key))
+                self._uargs[0] = ptr
+            if getattr(self, "usage_containers", None) is not None:  # containers per pod, as usage_config keeps them
+                self.usage_containers = layout.apply_moves(self.usage_containers, mv, int(n_active),
+                                                           int(fresh_usage_key) >> 28)
+
+    def layout_epoch(self) -> int:
+        """kwk_layout_epoch: 0 at create, +1 per successful relayout."""
+        return int(abi.lib().kwk_layout_epoch(self.h))
+
     def count(self, masks) -> np.ndarray:
         """kwk_count: alive objects with (pred & mask) != 0 per mask (0 = all alive)."""
         m = np.ascontiguousarray(masks, dtype=np.uint32)
